@@ -2,6 +2,13 @@
 """Constrained-draw likelihood throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload horns|nothing|muse] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`ms_per_step` = wall time of
+one timed step).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64, at most 64 MB in all: a fixed, seeded sample of columns where an output is larger); the
+inputs are seeded, so two builds can be compared output for output.  --full adds everything else the
+line can carry (below): extra legs, per-kernel figures and the checks after the timed region.
 
 Workload horns / nothing (BASELINE.json configs[1] / configs[2]; default horns)
 -------------------------------------------------------------------------------
@@ -31,16 +38,23 @@ resident in HBM when the timed region starts and every decision taken on the dev
 `value` = (candidate, spectrum) likelihood evaluations per second over all ranks.  N > 1: weak
 scaling, 10 000 spectra per GPU cut from horns(10 000 N), one process per GPU.
 
-The same run also reports (N = 1): `e2e_full` -- the complete analysis of the same spectra to its
+With --full the same run also checks the decision and the likelihood row of one more step, times
+the geometry kernels in a few extra steps (`count_within_us`, `bootstrap_us`) and reports (N = 1):
+`e2e_full` -- the complete analysis of the same spectra to its
 termination criterion; `e2e` -- a complete analysis of the same 10 000 spectra capped
 at 400 iterations through the real host orchestration, i.e. SURVEY 8(d)'s "evals inside
 draw_constrained / wall time of those draws"; `roofline_hbm_regime` -- K1 one pass over 1.6 GB;
 `cpu_baseline` -- the reference's own clike.so on the host cores.
+--dump-outputs: `live_loglike` (the live likelihoods of every data set after the step's advance),
+`thresholds`, `counts` (K3), `radius` (K6), `accepted`, `fill_bits`.
 
 Workload muse (BASELINE.json configs[4], one GPU's share: 6 250 spectra x 4096 channels)
 -----------------------------------------------------------------------------------------
 One STEP = B templates (default 1) scored against the 6 250 spectra with per-pixel variances
 (cmuselike.c:45-64): 410 MB of y and 1/v streamed from HBM (beyond the 256 MiB Infinity Cache).
+With --full (N = 1): the capped complete analyses (`e2e`, `e2e_no_noise`) and `cpu_baseline` with the
+parity check of the kernel's likelihoods against it.  --dump-outputs: `loglike` [B, spectra] (N = 1);
+`accepted`, `fill_bits` (N > 1, the draw chunk).
 """
 import argparse
 import ctypes as C
@@ -504,6 +518,24 @@ def read_profile(lib, which):
     return int(n.value), (1e3 * ms.value / n.value if n.value else 0.0)
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: below 64 MB in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64.  An array larger than its
+    even share of DUMP_BYTES keeps a fixed sample of its last axis (sorted indices drawn with
+    RandomState(0)), the same for every run of the same shape."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.array(a, dtype=np.float64, ndmin=1)
+        if a.nbytes > share:
+            n = a.shape[-1]
+            keep = max(1, share // (a.nbytes // n))
+            a = a[..., np.sort(np.random.RandomState(0).choice(n, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def bench_gauss(args):
     world, rank, use_dist, torch, dist, lib, _lib = setup_dist(args)
     from massivedatans_amd import gen
@@ -644,45 +676,34 @@ def bench_gauss(args):
     elapsed = timed(step, fence, args, use_dist, torch, dist, lib, _lib)
     n_launch, k1_us = read_profile(lib, 0)
     kernel = (lib.mdns_profile_kernel(0) or b"").decode()      # e.g. "k_gauss_cols_accept<8>"
-    # the geometry kernels of the step, timed in a few extra (unreported) steps
-    lib.mdns_profile_every(1)
-    lib.mdns_profile(4 | 8)
-    for _ in range(min(args.steps, 50)):
-        step()
-    other = {"count_within_us": read_profile(lib, 2)[1], "bootstrap_us": read_profile(lib, 3)[1]}
     lib.mdns_profile(0)
-    fence()
-
-    # sanity: the timed steps decided what they were built to decide, with the right numbers
-    # (one more step that also writes the likelihood row, which is recomputed for the check)
-    polled_accepted, polled_fill = accepted_now.value, fill_now.copy()
-    step(with_row=True)
-    fence()
-    assert accepted_now.value == polled_accepted and np.array_equal(fill_now, polled_fill), \
-        "bench draw: the commit with and without the likelihood row disagree"
-    _lib.check(lib.mdns_d2h(_lib.ptr(result), d_result, nres), "result")       # now with the likelihood row
-    live_now = np.empty((NLIVE, nd))
-    _lib.check(lib.mdns_joint_undo_advance_dev(joint), "undo advance")
-    _lib.check(lib.mdns_joint_get_live(joint, _lib.ptr(live_now)), "get live")
-    live_first = np.empty((NLIVE, nd))
-    _lib.check(lib.mdns_d2h(_lib.ptr(live_first), d_saved, live_first.nbytes), "d2h")
-    assert np.array_equal(live_now, live_first), "taking back the advance did not restore the live matrix"
-    accepted = int(result[:4].view(np.int32)[0])
-    status = int(result[4:8].view(np.int32)[0])
-    nbw = (nd + 63) // 64
-    bits = np.unpackbits(result[16:16 + 8 * nbw], bitorder="little")[:nd]
-    Lrow = result[16 + 8 * nbw:].view(np.float64)
-    ypred = params[B - 1, 0] * np.exp(-0.5 * ((params[B - 1, 1] - data["x"]) / params[B - 1, 2]) ** 2)
-    want = -0.5 * (((ypred.reshape((-1, 1)) - shard[:, :64]) / 0.01) ** 2).sum(axis=0)
-    assert accepted == B - 1 and status == 0, ("bench draw: accepted %d status %d" % (accepted, status))
-    assert accepted_now.value == B - 1, "bench draw: the polled outcome differs from the result buffer"
-    if not use_dist:
-        assert np.array_equal(fill_now.view(np.uint8), result[16:16 + 8 * nbw]), "bench draw: polled fill bits differ"
-    assert bits.all(), "bench draw: the accepted candidate must fill every shelf"
-    if use_dist:
-        every = np.unpackbits(allbits.view(np.uint8).reshape(world, -1), axis=1, bitorder="little")[:, :nd]
-        assert every.all(), "bench draw: the gathered fill bits of some rank are incomplete"
-    assert np.allclose(Lrow[:64], want, rtol=1e-10), "bench output check failed"
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step holds: the draw's outcome, the radius and the K3 counts;
+        # and the joint state that step left on the device (live likelihoods after the advance, thresholds)
+        live_out, higher = np.empty((NLIVE, nd)), np.empty(nd)
+        counts = np.empty(NCAND, dtype=np.int32)
+        _lib.check(lib.mdns_joint_get_live(joint, _lib.ptr(live_out)), "get live")
+        _lib.check(lib.mdns_joint_get_thresholds(joint, _lib.ptr(higher), None), "get thresholds")
+        _lib.check(lib.mdns_d2h(_lib.ptr(counts), d_counts, counts.nbytes), "counts")
+        if use_dist:
+            fill = np.unpackbits(allbits.view(np.uint8).reshape(world, -1), axis=1, bitorder="little")[:, :nd].ravel()
+        else:
+            fill = np.unpackbits(fill_now.view(np.uint8), bitorder="little")[:nd]
+        dump_outputs(args.dump_outputs, {"live_loglike": live_out, "thresholds": higher, "counts": counts,
+                                         "radius": lib.mdns_region_radius(region), "accepted": accepted_now.value,
+                                         "fill_bits": fill})
+    other = {}
+    if args.full:
+        # the geometry kernels of the step, timed in a few extra (unreported) steps
+        lib.mdns_profile_every(1)
+        lib.mdns_profile(4 | 8)
+        for _ in range(min(args.steps, 50)):
+            step()
+        other = {"count_within_us": read_profile(lib, 2)[1], "bootstrap_us": read_profile(lib, 3)[1]}
+        lib.mdns_profile(0)
+        fence()
+        check_gauss_step(step, fence, lib, _lib, joint, d_saved, d_result, result, nres, accepted_now, fill_now,
+                         params, data, shard, nd, B, use_dist, world, allbits if use_dist else None)
 
     if rank == 0:
         evals_per_step = B * nd * world
@@ -740,16 +761,16 @@ def bench_gauss(args):
                                          "bytes that have to move once"}},
         }
         res.update(other)
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             res["e2e"] = e2e_leg(data, args.e2e_iterations)
             res["e2e_graph"] = e2e_leg(data, args.e2e_iterations, use_graph=True)
             if not args.no_e2e_full:
                 # the whole analysis, not only its cheap first iterations (about 40 s)
                 res["e2e_full"] = e2e_leg(data, 0, use_graph=True)
-        if world == 1 and not args.no_hbm_leg:
+        if world == 1 and args.full and not args.no_hbm_leg:
             res["roofline_hbm_regime"] = hbm_regime_leg(lib, _lib)
             res["muse"] = muse_leg(lib, _lib)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_gauss(data, priortransform(np.random.RandomState(2).uniform(size=(64, NDIM))))
             if not args.no_e2e:
                 # like for like: the first iterations of the SAME analysis on the CPU oracle's kernels and, with
@@ -765,6 +786,40 @@ def bench_gauss(args):
         if direct is not None:
             direct.destroy()
         dist.destroy_process_group()
+
+
+def check_gauss_step(step, fence, lib, _lib, joint, d_saved, d_result, result, nres, accepted_now, fill_now,
+                     params, data, shard, nd, B, use_dist, world, allbits):
+    """--full: the timed steps decided what they were built to decide, with the right numbers
+    (one more step that also writes the likelihood row, which is recomputed for the check)."""
+    polled_accepted, polled_fill = accepted_now.value, fill_now.copy()
+    step(with_row=True)
+    fence()
+    assert accepted_now.value == polled_accepted and np.array_equal(fill_now, polled_fill), \
+        "bench draw: the commit with and without the likelihood row disagree"
+    _lib.check(lib.mdns_d2h(_lib.ptr(result), d_result, nres), "result")       # now with the likelihood row
+    live_now = np.empty((NLIVE, nd))
+    _lib.check(lib.mdns_joint_undo_advance_dev(joint), "undo advance")
+    _lib.check(lib.mdns_joint_get_live(joint, _lib.ptr(live_now)), "get live")
+    live_first = np.empty((NLIVE, nd))
+    _lib.check(lib.mdns_d2h(_lib.ptr(live_first), d_saved, live_first.nbytes), "d2h")
+    assert np.array_equal(live_now, live_first), "taking back the advance did not restore the live matrix"
+    accepted = int(result[:4].view(np.int32)[0])
+    status = int(result[4:8].view(np.int32)[0])
+    nbw = (nd + 63) // 64
+    bits = np.unpackbits(result[16:16 + 8 * nbw], bitorder="little")[:nd]
+    Lrow = result[16 + 8 * nbw:].view(np.float64)
+    ypred = params[B - 1, 0] * np.exp(-0.5 * ((params[B - 1, 1] - data["x"]) / params[B - 1, 2]) ** 2)
+    want = -0.5 * (((ypred.reshape((-1, 1)) - shard[:, :64]) / 0.01) ** 2).sum(axis=0)
+    assert accepted == B - 1 and status == 0, ("bench draw: accepted %d status %d" % (accepted, status))
+    assert accepted_now.value == B - 1, "bench draw: the polled outcome differs from the result buffer"
+    if not use_dist:
+        assert np.array_equal(fill_now.view(np.uint8), result[16:16 + 8 * nbw]), "bench draw: polled fill bits differ"
+    assert bits.all(), "bench draw: the accepted candidate must fill every shelf"
+    if use_dist:
+        every = np.unpackbits(allbits.view(np.uint8).reshape(world, -1), axis=1, bitorder="little")[:, :nd]
+        assert every.all(), "bench draw: the gathered fill bits of some rank are incomplete"
+    assert np.allclose(Lrow[:64], want, rtol=1e-10), "bench output check failed"
 
 
 # ------------------------------------------------------------------------------------------
@@ -881,6 +936,13 @@ def bench_muse(args):
     if dist_step is None:
         _lib.check(lib.mdns_d2h(_lib.ptr(L), d_L, B * nd * 8), "d2h")
     L = L.reshape(B, nd)
+    if args.dump_outputs and rank == 0:
+        if dist_step is None:
+            dump_outputs(args.dump_outputs, {"loglike": L})
+        else:
+            allbits = t_allbits.cpu().numpy().view(np.uint8).reshape(world, -1)
+            dump_outputs(args.dump_outputs, {"accepted": accepted.value,
+                                             "fill_bits": np.unpackbits(allbits, axis=1, bitorder="little")[:, :nd].ravel()})
 
     if rank == 0:
         value = B * nd * world * args.steps / elapsed
@@ -919,10 +981,10 @@ def bench_muse(args):
                           "flops_per_launch": flops, "hbm_frac_physical": gbs / HBM_PEAK_GBS,
                           "note": "10 flops per (template, channel, spectrum): two dot products and the residual sum"}),
         }
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             res["e2e"] = e2e_muse_leg(x, y_t, v_t, args.e2e_iterations, jitter=True)
             res["e2e_no_noise"] = e2e_muse_leg(x, y_t, v_t, args.e2e_iterations, jitter=False)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"], ref_L, which = cpu_baseline_muse(y_t, v_t, templates)
             err = np.max(np.abs(L[which] - ref_L) / np.abs(ref_L))
             assert err < 1e-9, ("K2 bench output differs from the CPU path", err)
@@ -944,12 +1006,16 @@ def main():
     ap.add_argument("--ndata", type=int, default=10000, help="spectra per GPU (horns / nothing)")
     ap.add_argument("--muse-ndata", type=int, default=6250, help="spectra per GPU (muse)")
     ap.add_argument("--pool", type=int, default=4 * NLIVE, help="unique live points in the pool (K)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-leg", action="store_true", help="skip the 1.6 GB one-pass HBM-regime measurement")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the capped complete analysis")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks after the timed region, the geometry kernel timings and the legs below")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-hbm-leg", action="store_true", help="(--full) skip the 1.6 GB one-pass HBM-regime measurement")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the capped complete analysis")
     ap.add_argument("--e2e-iterations", type=int, default=400)
     ap.add_argument("--cpu-e2e-iterations", type=int, default=100, help="cap of the CPU-oracle run of the same analysis (cpu_baseline.e2e)")
-    ap.add_argument("--no-e2e-full", action="store_true", help="skip the complete analysis (about 40 s)")
+    ap.add_argument("--no-e2e-full", action="store_true", help="(--full) skip the complete analysis (about 40 s)")
     ap.add_argument("--event-every", type=int, default=4, help="time every n-th launch of the dominant kernel")
     ap.add_argument("--no-events", action="store_true", help="no per-launch events in the timed loop (roofline empty)")
     ap.add_argument("--workload", default="horns", choices=["horns", "nothing", "muse"])

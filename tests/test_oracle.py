@@ -1,5 +1,5 @@
 """The CPU oracle against (a) the committed golden vectors made from the reference's own C
-and (b) the compiled reference itself when oracle/_ref is present.  Bit-exact everywhere."""
+and (b) the compiled reference itself when oracle/_ref is present as well.  Bit-exact everywhere."""
 import numpy as np
 import pytest
 
@@ -90,33 +90,22 @@ def test_k5_k6_golden(orc, golden):
         float(golden["k6_quirk_radius"])
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built (no /root/reference)")
 def test_port_vs_compiled_reference_random(orc):
-    """Wider seeded sweep, straight against the reference's own C."""
-    ref = Oracle("reference")
-    rng = np.random.RandomState(7)
-    for trial in range(12):
-        nd, nx = int(rng.randint(1, 70)), int(rng.randint(1, 50))
-        x = np.sort(rng.uniform(400, 800, nx))
-        yy = np.ascontiguousarray(rng.normal(0, 0.05, size=(nx, nd)))
-        m = rng.uniform(size=nd) < rng.uniform()
-        a, mu, sig = rng.uniform(0.01, 1), rng.uniform(400, 800), 10 ** rng.uniform(0, 2)
-        assert np.array_equal(orc.gauss_like(x, yy, a, mu, sig, 0.01, m),
-                              ref.gauss_like(x, yy, a, mu, sig, 0.01, m))
-        vv = np.ascontiguousarray(rng.uniform(0.5, 2, size=(nx, nd)) * 1e-4)
-        yp = rng.uniform(0, 2, nx)
-        la, lb = np.full(nd, -1.0), np.full(nd, -1.0)
-        orc.muse_like(yy, vv, yp, m, Lout=la)
-        ref.muse_like(yy, vv, yp, m, Lout=lb)
-        assert np.array_equal(la, lb)
-        ndim, K, M = int(rng.randint(1, 7)), int(rng.randint(2, 90)), int(rng.randint(1, 60))
-        pts, cand = rng.uniform(size=(K, ndim)), rng.uniform(size=(M, ndim))
-        r = rng.uniform(0.05, 0.6)
-        for cm in (0, 1, 2):
-            assert np.array_equal(orc.count_within_distance_of(pts, r, cand, cm),
-                                  ref.count_within_distance_of(pts, r, cand, cm))
-        assert orc.most_distant_nearest_neighbor(pts) == ref.most_distant_nearest_neighbor(pts)
-        chosen = np.zeros((K, 10))
-        for b in range(10):
-            chosen[rng.choice(np.arange(K), size=K, replace=True), b] = 1.
-        assert orc.bootstrapped_maxdistance(pts, chosen) == ref.bootstrapped_maxdistance(pts, chosen)
+    """Wider seeded sweep, straight against the reference's own C: its outputs are recorded in
+    tests/golden/reference_sweep.npz (oracle/make_reference_sweep.py), and where oracle/_ref is
+    built the compiled reference is asked again."""
+    from oracle.make_reference_sweep import PATH, sweep_inputs, sweep_outputs
+    ref = Oracle("reference") if have_reference() else None
+    with np.load(PATH) as f:
+        stored = {k: f[k] for k in f.files}
+    trials = sweep_inputs()
+    assert len(stored) == len(trials) * 17
+    for i, t in enumerate(trials):
+        for k, v in t.items():
+            assert np.array_equal(v, stored["t%d_%s" % (i, k)]), (i, k)
+        got = sweep_outputs(orc, t)
+        want = sweep_outputs(ref, t) if ref is not None else None
+        for k, v in got.items():
+            assert np.array_equal(v, stored["t%d_%s" % (i, k)]), (i, k)
+            if want is not None:
+                assert np.array_equal(v, want[k]), (i, k)

@@ -8,7 +8,7 @@ set -e
 out=gpurun_out/$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf "$out" && mkdir -p "$out"
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-e2e --no-hbm-leg $*"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-e2e --no-hbm-leg $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py $ARGS > "$out/kt.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py $ARGS > "$out/fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write" -- python3 bench.py $ARGS > "$out/write.log" 2>&1

@@ -9,9 +9,9 @@ cd "$repo"
 tag=${1:?usage: tools/collect_round.sh <tag>}
 out=gpurun_out/$tag
 mkdir -p "$out"
-python bench.py > "$out/bench.json" 2> "$out/bench.err"
-python bench.py --workload nothing --no-e2e-full > "$out/bench_nothing.json" 2> "$out/bench_nothing.err"
-python bench.py --workload muse > "$out/bench_muse_b1.json" 2> "$out/bench_muse_b1.err"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
+python bench.py --full --workload nothing --no-e2e-full > "$out/bench_nothing.json" 2> "$out/bench_nothing.err"
+python bench.py --full --workload muse > "$out/bench_muse_b1.json" 2> "$out/bench_muse_b1.err"
 python bench.py --workload muse --batch 64 --steps 50 --warmup 5 --no-cpu-baseline --no-e2e > "$out/bench_muse_b64.json" 2> "$out/bench_muse_b64.err"
 USE_GRAPH=1 python tools/e2e_run.py horns 10000 100 0 > "$out/e2e_c2_full_graph.json" 2> "$out/e2e_c2_full_graph.err"
 USE_GRAPH=0 python tools/e2e_run.py horns 10000 100 0 > "$out/e2e_c2_full.json" 2> "$out/e2e_c2_full.err"
