@@ -687,6 +687,41 @@ int mdns_core_get_superpoints(const mdns_core *c, int32_t *out, int cap);
 #define MDNS_CORE_COUNTERS 36
 void mdns_core_stats(const mdns_core *c, long long *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 7 -- posterior summaries and resampling of finished runs (csrc/mdns_posterior.hip).
+ *
+ * Replaces the reference's per-spectrum post-processing loop (musefuse_postprocess.py:112-140,
+ * checkoutput.py:27-44).  Input: what save_results writes, host arrays in C order,
+ * w, L double[nsamp][ndata] and x double[nsamp][ndata][ndim] (1 <= ndim <= 8); they are uploaded
+ * once and serve every call on the handle.  Per data set d, with lw = w + L and F its rows where lw
+ * is finite, p = exp(lw[F] - max) / sum:
+ *   nfinite[d] = |F|, log_norm[d] = max + log(sum), ess[d] = 1 / sum p^2 (Kish),
+ *   mean / std [ndata][ndim]: the exact weighted moments (std: centred second pass),
+ *   quant [ndata][ndim][nq]: for each q[j] in (0, 1], the smallest sample value whose cumulative
+ *     weight in value order reaches q[j] (a sample value; weights in 2^-52 fixed point),
+ *   imaxL[d]: the row of F with the largest L (the first on ties).
+ * A data set with nfinite = 0 gets NaN statistics, imaxL = -1 and draws of -1.  Every output is
+ * optional (NULL: not fetched; std and quant are not computed either).  No float atomics: the
+ * same input gives the same bytes.  0 on success, message in mdns_last_error().
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mdns_posterior mdns_posterior;
+mdns_posterior *mdns_posterior_create(const double *w, const double *L, const double *x,
+                                      int nsamp, int ndata, int ndim);
+void mdns_posterior_destroy(mdns_posterior *h);
+int mdns_posterior_summary(mdns_posterior *h, const double *q, int nq, int *nfinite,
+                           double *log_norm, double *ess, double *mean, double *std,
+                           double *quant, int *imaxL);
+/* numpy.random.choice(F, n, p=p) of musefuse_postprocess.py:121 with numpy's own generator per data
+ * set: index int32[ndata][n] equals Generator(Philox(key=[seed, first_column + d])).choice(F, size=n,
+ * p=p) -- first_column: where the handle's columns start in the whole run (a .cols part of a sharded
+ * run draws what the whole file would); xdraws double[ndata][n][ndim] (may be NULL) the drawn
+ * x[index, d, :]. */
+int mdns_posterior_resample(mdns_posterior *h, unsigned long long seed, long long first_column,
+                            int n, int *index, double *xdraws);
+/* device milliseconds of the last calls, from events: [0] max and weighted sums, [1] std,
+ * [2] quantiles, [3] resampling (ms double[4]) */
+int mdns_posterior_timings(const mdns_posterior *h, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

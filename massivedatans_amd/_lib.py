@@ -44,6 +44,9 @@ ABI_SYMBOLS = (
     "mdns_backend_draw_score", "mdns_joint_votes_dev", "mdns_backend_draw_commit", "mdns_get_stream",
     "mdns_backend_draw_band", "mdns_backend_draw_band_commit", "mdns_muse_filter_mode", "mdns_muse_filter_stats", "mdns_muse_filter_dev",
     "mdns_backend_draw_band_begin", "mdns_backend_draw_band_ready", "mdns_backend_draw_band_end",
+    # Part 7 (csrc/mdns_posterior.hip)
+    "mdns_posterior_create", "mdns_posterior_destroy", "mdns_posterior_summary", "mdns_posterior_resample",
+    "mdns_posterior_timings",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -184,6 +187,11 @@ def _declare(lib):
         "mdns_muse_filter_dev": (i, [vp, vp, i, vp, i, vp, vp, vp]),
         "mdns_muse_filter_mode": (None, [i]),
         "mdns_muse_filter_stats": (None, [vp]),
+        "mdns_posterior_create": (vp, [vp, vp, vp, i, i, i]),
+        "mdns_posterior_destroy": (None, [vp]),
+        "mdns_posterior_summary": (i, [vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "mdns_posterior_resample": (i, [vp, C.c_ulonglong, C.c_longlong, i, vp, vp]),
+        "mdns_posterior_timings": (i, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -171,7 +171,10 @@ def main(argv=None):
         max_samples=int(os.environ.get('MAXSAMPLES', 100000)), min_samples=int(os.environ.get('MINSAMPLES', 0)))
     from .sample import write_outputs
     prefix = '%s_full_.out_%d' % (argv[1], ndata)
-    if not write_outputs(prefix, results, sampler, duration, ndata):
+    first = write_outputs(prefix, results, sampler, duration, ndata)
+    from .postprocess import run_posterior_outputs
+    run_posterior_outputs(prefix, results)                            # MDNS_POSTERIOR=N; unset: nothing
+    if not first:
         return
     print('logZ = %.1f +- %.1f' % (results['logZ'][0], results['logZerr'][0]))
     print('ndraws:', sampler.ndraws, 'niter:', len(results['weights']), 'in %.1f s' % duration)

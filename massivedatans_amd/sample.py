@@ -374,7 +374,10 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     prefix = '%s_%s_nlive%d_%d.out8' % (argv[1], constrainer_type, nlive_points, ndata)
-    if not write_outputs(prefix, results, sampler, duration, ndata):
+    first = write_outputs(prefix, results, sampler, duration, ndata)
+    from .postprocess import run_posterior_outputs
+    run_posterior_outputs(prefix, results)                            # MDNS_POSTERIOR=N; unset: nothing
+    if not first:
         return
     print('logZ = %.1f +- %.1f' % (results['logZ'][0], results['logZerr'][0]))
     print('ndraws:', sampler.ndraws, 'niter:', len(results['weights']), 'likelihood evals:', sampler.nevals,
