@@ -17,6 +17,7 @@ joint state / member-set implementation in Python -- the CPU oracle in tests), t
 transform and the two numpy operations the constrainer leaves to numpy.
 """
 import ctypes as C
+import math
 import os
 
 import numpy
@@ -69,6 +70,12 @@ class Prior(C.Structure):                  # mdns_prior
     _fields_ = [("ndim", C.c_int), ("nparams", C.c_int), ("a", C.c_double * MAX_DIM), ("b", C.c_double * MAX_DIM),
                 ("pow10", C.c_int * MAX_DIM), ("kernel_pow10", C.c_int * MAX_DIM), ("custom", _CUSTOM_PRIOR),
                 ("user", C.c_void_p), ("jitter_sigma", C.c_double)]
+
+
+class ChainRequest(C.Structure):           # mdns_chain_request
+    _fields_ = [("n", C.c_int), ("ndim", C.c_int), ("u", C.POINTER(C.c_double)), ("mn", C.POINTER(C.c_double)),
+                ("mx", C.POINTER(C.c_double)), ("identity", C.c_int), ("mean", C.POINTER(C.c_double)),
+                ("scale", C.POINTER(C.c_double)), ("prior", C.POINTER(Prior)), ("limit", C.c_int)]
 
 
 class NumpyOps(C.Structure):               # mdns_numpy_ops
@@ -176,6 +183,69 @@ def joint_kind_gauss(joint):
     return getattr(joint, "nparams", 3) == 3
 
 
+#: 10**v of the chain's numpy statement: None -- the C library's pow, one argument at a time, like the
+#: host's own prior transform (host_constrainer.cpp, transform()); tests put ``pow10_dd`` of
+#: csrc/mdns_pow10.h here (a function of an array), which is what the device computes.  Looked up per call.
+CHAIN_POW10 = None
+
+
+def _libm_pow10(v):
+    return numpy.array([math.pow(10.0, float(t)) for t in v], dtype=float)
+
+
+def chain_params(v, prior, pow10=None):
+    """Kernel parameters [B, 3] of unit-cube points ``v`` [B, ndim] by ``prior`` (mdns_prior), in the host's
+    operation order (host_constrainer.cpp, transform()): ``a * v``, ``+ b`` where ``b != 0``, ``10 **`` where
+    ``pow10``, again where ``kernel_pow10``; ``pow10``: the power function of an array (None: the C library's)."""
+    power = pow10 or _libm_pow10
+    v = numpy.asarray(v, dtype=float)
+    params = numpy.zeros((len(v), 3))
+    for k in range(v.shape[1]):
+        x = prior.a[k] * v[:, k]
+        if prior.b[k] != 0.0:
+            x = x + prior.b[k]
+        if prior.pow10[k]:
+            x = power(x)
+        if k < 3:
+            params[:, k] = power(x) if prior.kernel_pow10[k] else x
+    return params
+
+
+def chain_statement(u, mn, mx, radius, count, mean, scale, prior, limit, pow10=None):
+    """What ``chain_begin`` / ``chain_end`` (include/mdns.h Part 5; csrc/mdns_chain.hip on the device) mean,
+    in numpy and in the host's operation order, one rounding per operation:
+
+    * proposals ``lo + (hi - lo) * u`` with ``lo = mn - radius``, ``hi = mx + radius``
+      (radfriendsregion.py:69-70,135), ``u`` [n, ndim] the raw doubles;
+    * ``counts = count(proposals)``, the members within the radius of each;
+    * a proposal is kept when its count is positive and ``v`` -- the proposal itself, or
+      ``proposal * scale + mean`` where a metric is given (``scale`` not None) -- lies strictly inside
+      the unit cube (hiermetriclearn.py:111-119);
+    * with ``limit > 0`` the first ``B = min(kept, limit)`` kept ones, in proposal order, get kernel
+      parameters: ``a * v``, ``+ b`` where ``b != 0``, ``10 **`` where ``pow10``, again where
+      ``kernel_pow10`` (mdns_prior), three per candidate.
+
+    Returns ``(proposals, counts, kept, params)``; ``params`` is None for ``limit <= 0``."""
+    u = numpy.asarray(u, dtype=float)
+    n, ndim = u.shape
+    mn, mx = numpy.asarray(mn, dtype=float), numpy.asarray(mx, dtype=float)
+    lo = mn - radius
+    hi = mx + radius
+    span = hi - lo
+    t = span * u
+    props = numpy.ascontiguousarray(lo + t)
+    counts = numpy.asarray(count(props)).astype(numpy.int32)
+    v = props
+    if scale is not None:
+        t = props * numpy.asarray(scale, dtype=float)
+        v = t + numpy.asarray(mean, dtype=float)
+    kept = (counts > 0) & ((v > 0) & (v < 1)).all(axis=1)
+    if limit <= 0:
+        return props, counts, kept, None
+    params = chain_params(v[kept][:limit], prior, pow10)
+    return props, counts, kept, params
+
+
 def hip_backend(joint):
     """The device entry points of libmdns_hip.so for a :class:`jointstate.GaussJointState`."""
     lib = _lib.require_device()
@@ -210,7 +280,9 @@ def python_backend(joint, member_set_factory=None):
     """The same table over Python objects: ``joint`` with ``draw(params-less xs?)`` -- any joint state of
     :mod:`massivedatans_amd.jointstate` -- and ``member_set_factory(members) -> object`` with
     ``bootstrap_radius_packed(masks, n)``, ``set_radius(r)``, ``count(points)`` (default:
-    ``clustering.neighbors.MemberSet``, resolved at call time so that tests can patch it)."""
+    ``clustering.neighbors.MemberSet``, resolved at call time so that tests can patch it).
+    ``MDNS_PYTHON_BACKEND_CHAIN=1`` (a test switch, off by default) adds ``chain_begin`` / ``chain_end``
+    as :func:`chain_statement`, so that the host half of the hand-over runs without a device."""
     from .clustering import neighbors
     regions = {}
     state = {"rows": None, "M": 0, "next": 1}
@@ -380,6 +452,56 @@ def python_backend(joint, member_set_factory=None):
     def chunk_size(_user, offered, M, hint):
         return int(joint.chunk_size(offered, M, hint))
 
+    # the first batch of a region in one piece (MDNS_PYTHON_BACKEND_CHAIN=1): chain_statement over the
+    # region's member set, with the radius region_begin kept; the chunk goes through joint.draw_params
+    # exactly as a draw_chunk would.  It rides along under the conditions of mdns_backend_chain_begin:
+    # Gaussian-line state, the library's own prior transform, no likelihood noise.
+    chained = {}
+
+    def chain_begin(_user, key, rq_ptr):
+        try:
+            rq = C.cast(rq_ptr, C.POINTER(ChainRequest)).contents
+            prior = rq.prior.contents
+            n, ndim = rq.n, rq.ndim
+            ms = regions[key]
+            full = (rq.limit > 0 and joint_kind_gauss(joint) and not prior.custom and prior.nparams == 3 and
+                    prior.jitter_sigma == 0 and state["M"] > 0)
+            metric = not rq.identity and bool(rq.mean) and bool(rq.scale)
+            _, counts, kept, params = chain_statement(
+                numpy.ctypeslib.as_array(rq.u, (n, ndim)), numpy.ctypeslib.as_array(rq.mn, (ndim,)),
+                numpy.ctypeslib.as_array(rq.mx, (ndim,)), radii[key], ms.count,
+                numpy.ctypeslib.as_array(rq.mean, (ndim,)) if metric else None,
+                numpy.ctypeslib.as_array(rq.scale, (ndim,)) if metric else None, prior, rq.limit if full else 0,
+                pow10=CHAIN_POW10)
+            out = {"counts": counts, "nkept": -1, "B": 0, "accepted": -1, "beats": None, "params": None}
+            if full:
+                out.update(nkept=int(kept.sum()), B=len(params), params=params)
+                if len(params):
+                    idx, _, beats, _ = joint.draw_params(params, state["rows"])
+                    out.update(accepted=int(idx), beats=beats)
+            chained[key] = out
+            return 0
+        except Exception:       # noqa: BLE001
+            import traceback
+            traceback.print_exc()
+            return 1
+
+    def chain_end(_user, key, counts_ptr, nkept_ptr, B_ptr, accepted_ptr, bits_ptr, params_ptr):
+        out = chained.pop(key, None)
+        if out is None:
+            return 1
+        numpy.ctypeslib.as_array(counts_ptr, (len(out["counts"]),))[:] = out["counts"]
+        nkept_ptr[0], B_ptr[0], accepted_ptr[0] = out["nkept"], out["B"], out["accepted"]
+        if out["accepted"] >= 0:
+            M = state["M"]
+            words = numpy.zeros((M + 63) // 64, dtype=numpy.uint64)
+            packed = numpy.packbits(numpy.asarray(out["beats"], dtype=numpy.uint8), bitorder='little')
+            words.view(numpy.uint8)[:len(packed)] = packed
+            numpy.ctypeslib.as_array(bits_ptr, (len(words),))[:] = words
+        if params_ptr and out["B"] > 0:
+            numpy.ctypeslib.as_array(params_ptr, (out["B"], 3))[:] = out["params"]
+        return 0
+
     be = DrawBackend()
     be.user = None
     be.region_create = _REGION_CREATE(region_create)
@@ -398,8 +520,11 @@ def python_backend(joint, member_set_factory=None):
             be.draw_band_begin = _DRAW_BAND_BEGIN(draw_band_begin)
             be.draw_band_ready = _DRAW_BAND_READY(draw_band_ready)
             be.draw_band_end = _DRAW_BAND_END(draw_band_end)
+    if os.environ.get("MDNS_PYTHON_BACKEND_CHAIN", "0") == "1":
+        be.chain_begin = _CHAIN_BEGIN(chain_begin)
+        be.chain_end = _CHAIN_END(chain_end)
     be._keep = (region_create, region_destroy, region_count, draw_begin, draw_chunk, chunk_size, regions, joint, draw_band, draw_band_commit,
-                draw_band_begin, draw_band_ready, draw_band_end)
+                draw_band_begin, draw_band_ready, draw_band_end, chain_begin, chain_end)
     return be
 
 
@@ -520,4 +645,4 @@ class NativeConstrainer(object):
 
 
 __all__ = ['NativeConstrainer', 'NativeContext', 'available', 'hip_backend', 'python_backend', 'sample_py_prior',
-           'custom_prior']
+           'custom_prior', 'ChainRequest', 'chain_statement', 'chain_params']

@@ -19,8 +19,9 @@
 //
 // Arithmetic: the proposals and the inverse transform are single IEEE operations in the host's order
 // (this file is compiled with -ffp-contract=off), the counts use the squared-distance test of
-// mdns_neighbors.hip; 10**v is mdns_pow10.h (correctly rounded but for one argument in ~10^4; the C
-// library's own pow is off by an ulp more often).  The sum of a (candidate, spectrum) pair is the chain
+// mdns_neighbors.hip; 10**v is mdns_pow10.h (on the prior's exponents [-2, 2] correctly rounded but for
+// fewer than one argument in 10^4, never off by more than an ulp; the C library's own pow is off by an
+// ulp more often).  The sum of a (candidate, spectrum) pair is the chain
 // of every other K1 form: channels ascending, d = m - y, acc = fma(d, d, acc).
 #include "mdns_internal.h"
 #include "mdns_pow10.h"

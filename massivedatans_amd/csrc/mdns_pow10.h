@@ -6,9 +6,12 @@
 // results, are still computed by the host with the C library's pow, like the reference.  The
 // likelihood of a candidate depends on the parameters to a relative 1e-16 per ulp, the same order
 // as the difference between the device's exp and the C library's, so the device value only has to
-// be as good as an ulp; this one is correctly rounded except in about one argument in 10^4 (internal
-// relative error ~2^-67), and the host counts the accepted candidates whose device parameters are
-// not bit for bit its own (mdns_constrainer_stats).
+// be as good as an ulp; this one is a faithful rounding everywhere (the correctly rounded double or
+// its neighbour on the side of the exact value; internal relative error ~2^-67) and, on the draw
+// path's exponents [-2, 2], correctly rounded except in fewer than one argument in 10^4 (about 1.5e-5
+// of them on [-2, 0], 5e-6 on [0, 2]; over the whole [-300, 300] it accepts about 5e-4, the error of
+// y = v log2(10) growing with |v|: tests/test_pow10.py).  The host counts the accepted candidates
+// whose device parameters are not bit for bit its own (mdns_constrainer_stats).
 //
 // Method: y = v log2(10) as a double-double; y = e + j/64 + r with integers e, j in [0, 64) and
 // |r| <= 1/128; 2^(j/64) from a table of 64 double-doubles; 2^r = exp(r ln2) by its series, the terms

@@ -11,22 +11,9 @@ import pytest
 
 from massivedatans_amd import gen, jointstate, sample
 from massivedatans_amd.like import GaussLineSpectra
+from chain_support import LaneScorer
 
 pytestmark = pytest.mark.gpu
-
-
-class LaneScorer(object):
-    """``loglike_batch`` that always runs the lane kernel (B >= 32 forces it)."""
-
-    def __init__(self, spectra):
-        self.spectra, self.ndata = spectra, spectra.ndata
-
-    def loglike_batch(self, params, data_mask=None):
-        params = np.atleast_2d(params)
-        B = len(params)
-        if B < 32:
-            params = np.vstack([params] + [params[-1:]] * (32 - B))
-        return self.spectra.loglike_batch(params, data_mask)[:B]
 
 
 def _drive(dev, host, ndata, rng, iterations, exact):

@@ -34,7 +34,7 @@ def _run(g, backend, fused, native, jitter=True):
 
 
 @pytest.mark.parametrize("case", ["muse6", "muse10_graph"])
-@pytest.mark.parametrize("mode", ["single", "native", "native-block", "native-far-ahead", "native-not-ahead", "native-threads"])
+@pytest.mark.parametrize("mode", ["single", "native", "native-block", "native-far-ahead", "native-not-ahead", "native-threads", "native-chain"])
 def test_muse_trace_bit_exact(case, mode, oracle, monkeypatch):
     """``single``: one candidate per likelihood call, the noise from numpy.random.normal -- the
     reference's loop.  ``native``: whole chunks, the noise drawn in C from numpy's own Mersenne
@@ -51,6 +51,16 @@ def test_muse_trace_bit_exact(case, mode, oracle, monkeypatch):
         monkeypatch.setenv("MDNS_JITTER_BAND", "0")
         mode = "native"
     ahead = None
+    chain = mode == "native-chain"
+    if chain:
+        # the first batch of a fresh region handed over in one piece (constrainer.python_backend with
+        # MDNS_PYTHON_BACKEND_CHAIN=1: the numpy statement of chain_begin / chain_end).  This problem has five
+        # parameters and likelihood noise, so only proposals and membership counts ride along: the
+        # counts-only route of the host (csrc/host_constrainer.cpp, BOX phase) -- the same trace
+        if case != "muse6":
+            pytest.skip("on the short trace only")
+        monkeypatch.setenv("MDNS_PYTHON_BACKEND_CHAIN", "1")
+        mode = "native"
     if mode == "native-threads":
         # the blocks of the noise stream made by two helper threads ahead of the scan (host_constrainer.cpp,
         # BlockProducer; opt-in): the blocks are a function of the stream alone, so the same trace
@@ -89,6 +99,7 @@ def test_muse_trace_bit_exact(case, mode, oracle, monkeypatch):
         assert (st["band_pairs"] + st["band_replays"] > 0) == (os.environ.get("MDNS_JITTER_BAND", "1") != "0") or st["band_pairs"] == 0
         if os.environ.get("MDNS_JITTER_BAND", "1") != "0":
             assert (st["band_ahead"] > 0) == (ahead is not False), st
+        assert (st["chain_counts"] > 0) == chain and st["chains"] == 0 and st["param_mismatch"] == 0, st
 
 
 @pytest.mark.gpu
