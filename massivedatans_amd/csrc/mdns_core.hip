@@ -944,7 +944,8 @@ static bool pool_fit(void **p, size_t *cap, size_t need)
 
 static bool region_fetch(mdns_region *r);
 
-bool mdns::poll_expired(long long *started_ns)
+// *started_ns: 0 before the first call of a wait
+static bool poll_expired(long long *started_ns)
 {
 	static const double limit_s = [] { const char *v = getenv("MDNS_POLL_TIMEOUT_S"); const double t = v ? atof(v) : 120.0; return t > 0 ? t : 120.0; }();
 	struct timespec ts;
@@ -952,6 +953,29 @@ bool mdns::poll_expired(long long *started_ns)
 	const long long now = (long long) ts.tv_sec * 1000000000LL + ts.tv_nsec;
 	if (*started_ns == 0) { *started_ns = now; return false; }
 	return (double) (now - *started_ns) * 1e-9 > limit_s;
+}
+
+Wait mdns::wait_seq(const volatile unsigned long long *at, unsigned long long want, hipError_t *err)
+{
+	// The number usually is there already (the caller has launched other work meanwhile).
+	// While polling, look at the stream now and then: once it has drained, everything the
+	// kernel wrote is visible, and a failed launch shows up as an error instead of a hang.
+	long long started = 0;
+	for (unsigned spin = 0; *at != want; spin++) {
+		if ((spin & 1023) != 1023) continue;
+		const hipError_t e = hipStreamQuery(g_ctx.stream);
+		if (e == hipErrorNotReady) {
+			if (poll_expired(&started)) return Wait::timeout;
+			continue;
+		}
+		if (e != hipSuccess) {
+			if (err) *err = e;
+			return Wait::failed;
+		}
+		if (*at != want) return Wait::empty;
+	}
+	std::atomic_thread_fence(std::memory_order_acquire);
+	return Wait::ok;
 }
 
 static mdns_region *region_new(const double *d_members, double *owned, int K, int ndim)
@@ -1087,23 +1111,13 @@ extern "C" int mdns_region_set_radius(mdns_region *r, double maxdistance)
 static bool region_fetch(mdns_region *r)
 {
 	if (!r->pending) return true;
-	Context *c = ctx();
-	volatile unsigned long long *seq = &r->h_res->seq;
-	// The result usually is there already (the caller has launched other work meanwhile).
-	// While polling, look at the stream now and then: once it has drained, everything the
-	// kernel wrote is visible, and a failed launch shows up as an error instead of a hang.
-	long long started = 0;
-	for (unsigned spin = 0; *seq != r->seq; spin++) {
-		if ((spin & 1023) != 1023) continue;
-		const hipError_t e = hipStreamQuery(c->stream);
-		if (e == hipErrorNotReady) {
-			if (poll_expired(&started)) { set_error("radius computation: no result within MDNS_POLL_TIMEOUT_S"); return false; }
-			continue;
-		}
-		if (e != hipSuccess) { set_error("radius computation failed: %s", hipGetErrorString(e)); return false; }
-		if (*seq != r->seq) { set_error("radius computation finished without a result"); return false; }
+	hipError_t e = hipSuccess;
+	switch (wait_seq(&r->h_res->seq, r->seq, &e)) {
+	case Wait::ok: break;
+	case Wait::timeout: set_error("radius computation: no result within MDNS_POLL_TIMEOUT_S"); return false;
+	case Wait::failed: set_error("radius computation failed: %s", hipGetErrorString(e)); return false;
+	case Wait::empty: set_error("radius computation finished without a result"); return false;
 	}
-	std::atomic_thread_fence(std::memory_order_acquire);
 	r->radius = r->h_res->radius;
 	r->thresh_sq = sqrt_threshold(r->radius);     // the device derived the same number (tested)
 	r->pending = false;
@@ -1222,25 +1236,18 @@ extern "C" int mdns_region_count_polled(mdns_region *r, const double *points, in
 	// device memory (stream order)
 	if (!launch_count_within(r->d_members, r->K, r->ndim, r->thresh_sq, r->on_device ? r->d_res : nullptr,
 	                         (const double *) (g_stage_dev + off_points), M, (int *) (g_stage_dev + off_counts), &mail)) return 1;
-	volatile unsigned long long *at = (volatile unsigned long long *) g_stage;
-	long long started = 0;
-	for (unsigned spin = 0; *at != seq; spin++) {
-		if ((spin & 1023) != 1023) continue;
-		const hipError_t e = hipStreamQuery(c->stream);
-		if (e == hipErrorNotReady) {
-			if (poll_expired(&started)) { set_error("membership count: no result within MDNS_POLL_TIMEOUT_S"); return 1; }
-			continue;
-		}
-		if (e != hipSuccess) { set_error("membership count failed: %s", hipGetErrorString(e)); return 1; }
-		if (*at != seq) {
-			// (the stream drained and the number is not there: the launch failed; the ticket counter
-			// may be anywhere)
-			(void) hipMemsetAsync(g_stage_ticket, 0, sizeof(int), c->stream);
-			set_error("membership count finished without a result");
-			return 1;
-		}
+	hipError_t e = hipSuccess;
+	switch (wait_seq((const volatile unsigned long long *) g_stage, seq, &e)) {
+	case Wait::ok: break;
+	case Wait::timeout: set_error("membership count: no result within MDNS_POLL_TIMEOUT_S"); return 1;
+	case Wait::failed: set_error("membership count failed: %s", hipGetErrorString(e)); return 1;
+	case Wait::empty:
+		// (the stream drained and the number is not there: the launch failed; the ticket counter
+		// may be anywhere)
+		(void) hipMemsetAsync(g_stage_ticket, 0, sizeof(int), c->stream);
+		set_error("membership count finished without a result");
+		return 1;
 	}
-	std::atomic_thread_fence(std::memory_order_acquire);
 	memcpy(counts, g_stage + off_counts, (size_t) M * sizeof(int));
 	return 0;
 }

@@ -38,7 +38,6 @@
 // most one per wave.
 #include "mdns_internal.h"
 
-#include <atomic>
 #include <cstddef>
 #include <cstring>
 
@@ -503,19 +502,13 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 		if (!MDNS_HIP(hipGetLastError())) return 1;
 		// counts, flags and the list arrive in mapped host memory: poll for `seq` (looking at the
 		// stream now and then: a failed launch shows up as an error instead of a hang)
-		volatile unsigned long long *seq = &g->h_box->seq;
-		long long started = 0;
-		for (unsigned spin = 0; *seq != g->box_seq; spin++) {
-			if ((spin & 1023) != 1023) continue;
-			const hipError_t e = hipStreamQuery(c->stream);
-			if (e == hipErrorNotReady) {
-				if (poll_expired(&started)) { set_error("mdns_groups_components: no result within MDNS_POLL_TIMEOUT_S"); return 1; }
-				continue;
-			}
-			if (e != hipSuccess) { set_error("mdns_groups_components: %s", hipGetErrorString(e)); return 1; }
-			if (*seq != g->box_seq) { set_error("mdns_groups_components: finished without a result"); return 1; }
+		hipError_t e = hipSuccess;
+		switch (wait_seq(&g->h_box->seq, g->box_seq, &e)) {
+		case Wait::ok: break;
+		case Wait::timeout: set_error("mdns_groups_components: no result within MDNS_POLL_TIMEOUT_S"); return 1;
+		case Wait::failed: set_error("mdns_groups_components: %s", hipGetErrorString(e)); return 1;
+		case Wait::empty: set_error("mdns_groups_components: finished without a result"); return 1;
 		}
-		std::atomic_thread_fence(std::memory_order_acquire);
 		if (h->status) {
 			const int status = h->status;
 			(void) hipMemsetAsync(&hdr_of(g)->status, 0, sizeof(int), c->stream);

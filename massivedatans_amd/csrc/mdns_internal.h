@@ -14,8 +14,13 @@ bool hip_ok(hipError_t e, const char *what, const char *file, int line);
 
 // Busy polls of mapped mailboxes give up after MDNS_POLL_TIMEOUT_S seconds (default 120): a wedged
 // kernel or a lost mailbox store becomes an error the caller can act on instead of a core spinning
-// forever.  *started_ns: 0 before the first call of a wait.
-bool poll_expired(long long *started_ns);
+// forever.
+// wait_seq polls *at (mapped host memory a kernel on the context's stream raises last) until it holds `want`, looking
+// at the stream now and then: a failed launch shows up as an error instead of a hang.  ok: everything the kernel
+// stored before `want` can be read; timeout: the limit passed (the kernel may still be running); failed: the stream
+// reports *err; empty: the stream drained and the number is not there.  The error text is the caller's.
+enum class Wait { ok, timeout, failed, empty };
+Wait wait_seq(const volatile unsigned long long *at, unsigned long long want, hipError_t *err = nullptr);
 
 // ---- per-process context (one process drives one GPU) -----------------------------------
 struct Context {

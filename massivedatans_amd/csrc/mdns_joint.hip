@@ -18,7 +18,6 @@
 // pass when an accepted point joins a shelf (k_gauss_cols_commit in mdns_like.hip).
 #include "mdns_internal.h"
 
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -418,6 +417,11 @@ __global__ void k_joint_fill(double *__restrict__ p, size_t n, double value)
 
 using namespace mdns;
 
+// what the accept pass of a backend chunk leaves for its commit.  path 0: none (-1: nothing of this handle's was
+// selected); 1: dense block (kind 1); 2: two launches; 3: lane kernels.  flag: what the pass wrote into d_flags for
+// a candidate that beats a threshold.
+struct ChunkScore { int path, B, flag; };
+
 struct mdns_joint {
 	mdns_spectra *s = nullptr;
 	int nlive = 0, cap = 0, ndata = 0;
@@ -498,7 +502,7 @@ struct mdns_joint {
 	// a chunk in two halves (mdns_backend_draw_score / _commit): one 0 / 1 vote per candidate, what the ranks
 	// of a sharded run MAX-reduce in between
 	int *d_votes = nullptr;
-	int half_path = 0, half_B = 0, half_flag = 0;       // 0: none; 1: dense block (kind 1); 2: two launches; 3: lane kernels
+	ChunkScore half = {0, 0, 0};       // what the score of the halves left for their commit
 	unsigned long long chain_seq = 0;
 	int chain_state = 0;               // 0 none, 1 counts only (poll h_chain->seq), 2 full (poll the commit's mailbox)
 	int chain_n = 0;
@@ -516,27 +520,12 @@ extern "C" void mdns_joint_destroy(mdns_joint *j)
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
 	void *bufs[] = {j->st.live, j->st.shelfL, j->st.shelfn, j->st.higher, j->d_running, j->d_Lmin, j->d_argmin_run,
-	                j->d_argmin, j->d_keep, j->d_status, j->d_flags, j->d_params};
+	                j->d_argmin, j->d_keep, j->d_status, j->d_flags, j->d_params, j->d_sel_rows, j->d_dense, j->d_msq,
+	                j->d_filter_scratch, j->d_jitter, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket,
+	                j->d_commit_ticket, j->d_votes, j->d_band, j->d_bound, j->d_trail_stamp, j->d_trail_word, j->d_trail_L};
 	for (void *b : bufs) if (b) (void) hipFree(b);
-	if (j->d_sel_rows) (void) hipFree(j->d_sel_rows);
-	if (j->d_dense) (void) hipFree(j->d_dense);
-	if (j->d_msq) (void) hipFree(j->d_msq);
-	if (j->d_filter_scratch) (void) hipFree(j->d_filter_scratch);
-	if (j->d_jitter) (void) hipFree(j->d_jitter);
-	if (j->h_in) (void) hipHostFree(j->h_in);
-	if (j->h_chain) (void) hipHostFree(j->h_chain);
-	if (j->d_chain_props) (void) hipFree(j->d_chain_props);
-	if (j->d_chain_counts) (void) hipFree(j->d_chain_counts);
-	if (j->d_chain_ticket) (void) hipFree(j->d_chain_ticket);
-	if (j->d_commit_ticket) (void) hipFree(j->d_commit_ticket);
-	if (j->d_votes) (void) hipFree(j->d_votes);
-	if (j->h_band) (void) hipHostFree(j->h_band);
-	if (j->d_band) (void) hipFree(j->d_band);
-	if (j->d_bound) (void) hipFree(j->d_bound);
-	void *trail[] = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L};
-	for (void *b : trail) if (b) (void) hipFree(b);
-	if (j->h_box) (void) hipHostFree(j->h_box);
-	if (j->h_pin) (void) hipHostFree(j->h_pin);
+	void *pinned[] = {j->h_in, j->h_chain, j->h_band, j->h_box, j->h_pin};
+	for (void *b : pinned) if (b) (void) hipHostFree(b);
 	delete j;
 }
 
@@ -958,6 +947,31 @@ static bool commit_ticket(mdns_joint *j)
 	return MDNS_HIP(hipMalloc((void **) &j->d_commit_ticket, sizeof(int))) && MDNS_HIP(hipMemsetAsync(j->d_commit_ticket, 0, sizeof(int), c->stream));
 }
 
+// the fill words of a chunk's outcome: behind the header in d_result
+static unsigned long long *result_bits(const mdns_joint *j) { return (unsigned long long *) (j->d_result + sizeof(JointHeader)); }
+
+// header and fill words into the mailbox, behind a commit kernel that does not fill it itself
+static void launch_publish(mdns_joint *j, Context *c, int M)
+{
+	hipLaunchKernelGGL(k_joint_publish, dim3(1), dim3(kBlock), 0, c->stream, (const JointHeader *) j->d_result, result_bits(j), (M + 63) / 64,
+	                   j->h_box_dev, ++j->box_seq);
+}
+
+// The commit from the trail the last accept pass left (joint_trail: its stamp is the current one): the first candidate
+// b with decides[b] == value is the accepted one; the kernel fills the mailbox itself.
+// one_group: the pass was the two-launch chunk's, whose single-workgroup commit takes a selection of a tile or two
+static bool commit_from_trail(mdns_joint *j, const int *thr_rows, int M, int B, const int *decides, int value, bool one_group)
+{
+	const JointTrail trail = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L, j->trail_stamp};
+	if (one_group && M <= 128) {
+		// a tile or two: shelf appends, thresholds and the mailbox in ONE workgroup
+		return launch_chunk_commit(thr_rows, M, B, decides, value, trail, j->st, j->d_result, result_bits(j), j->h_box_dev, ++j->box_seq);
+	}
+	// (its last workgroup fills the mailbox)
+	return commit_ticket(j) && launch_joint_commit_trail(thr_rows, M, B, decides, trail, j->st, j->d_result, result_bits(j), value, j->h_box_dev,
+	                                                     ++j->box_seq, j->d_commit_ticket);
+}
+
 static int joint_commit_dev(mdns_joint *j, const int *d_row_ids, int M, bool want_row, const char *who)
 {
 	Context *c = ctx();
@@ -978,21 +992,15 @@ static int joint_commit_dev(mdns_joint *j, const int *d_row_ids, int M, bool wan
 		j->box_pending = true;
 		return 0;
 	}
-	char *base = j->d_result;
-	unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-	double *Lrow = (double *) (base + sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8);
 	if (!want_row && j->trail_valid) {
 		// who beats its threshold, and with which likelihood, is in the trail of the accept pass:
 		// nothing is computed again
-		const JointTrail trail = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L, j->trail_stamp};
-		// (its last workgroup fills the mailbox)
-		if (!commit_ticket(j) || !launch_joint_commit_trail(d_row_ids, M, j->last_B, j->d_flags, trail, j->st, base, bits, 1, j->h_box_dev,
-		                                                    ++j->box_seq, j->d_commit_ticket)) return 1;
+		if (!commit_from_trail(j, d_row_ids, M, j->last_B, j->d_flags, 1, false)) return 1;
 	} else {
+		double *Lrow = (double *) (j->d_result + sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8);
 		if (!launch_gauss_cols_commit(j->s, j->last_yT, j->s->d_model, j->last_bt, j->last_B, j->last_scale, j->last_gather,
-		                              d_row_ids, M, j->d_flags, j->st, base, bits, Lrow)) return 1;
-		hipLaunchKernelGGL(k_joint_publish, dim3(1), dim3(kBlock), 0, c->stream, (const JointHeader *) base, bits, (M + 63) / 64,
-		                   j->h_box_dev, ++j->box_seq);
+		                              d_row_ids, M, j->d_flags, j->st, j->d_result, result_bits(j), Lrow)) return 1;
+		launch_publish(j, c, M);
 	}
 	j->trail_valid = false;                                             // a chunk is committed once
 	j->box_pending = true;
@@ -1012,36 +1020,33 @@ extern "C" int mdns_joint_commit_bits_dev(mdns_joint *j, const int *d_row_ids, i
 // waits for the mailbox of the last commit (see JointMailbox)
 static bool joint_wait_box(mdns_joint *j, const char *who)
 {
-	Context *c = ctx();
 	if (!j->box_pending) { set_error("%s: no commit to wait for", who); return false; }
-	volatile unsigned long long *seq = &j->h_box->seq;
-	// While polling, look at the stream now and then: a failed launch shows up as an error
-	// instead of a hang.
-	long long started = 0;
-	for (unsigned spin = 0; *seq != j->box_seq; spin++) {
-		if ((spin & 1023) != 1023) continue;
-		const hipError_t e = hipStreamQuery(c->stream);
-		if (e == hipErrorNotReady) {
-			if (poll_expired(&started)) { set_error("%s: no outcome within MDNS_POLL_TIMEOUT_S", who); return false; }
-			continue;
-		}
-		if (e != hipSuccess) { set_error("%s: the commit failed: %s", who, hipGetErrorString(e)); return false; }
-		if (*seq != j->box_seq) { set_error("%s: the commit finished without an outcome", who); return false; }
+	hipError_t e = hipSuccess;
+	switch (wait_seq(&j->h_box->seq, j->box_seq, &e)) {
+	case Wait::ok: break;
+	case Wait::timeout: set_error("%s: no outcome within MDNS_POLL_TIMEOUT_S", who); return false;
+	case Wait::failed: set_error("%s: the commit failed: %s", who, hipGetErrorString(e)); return false;
+	case Wait::empty: set_error("%s: the commit finished without an outcome", who); return false;
 	}
-	std::atomic_thread_fence(std::memory_order_acquire);
 	j->box_pending = false;
 	return true;
+}
+
+// the outcome of the last commit from its mailbox: {accepted, status, fill words} -- no copy, no stream synchronisation
+static int joint_read_box(mdns_joint *j, int M, int *accepted, unsigned long long *fillbits, const char *who)
+{
+	if (!joint_wait_box(j, who)) return 1;
+	if (j->h_box->status) { status_error(who, j->h_box->status, j->cap); return 1; }
+	*accepted = j->h_box->accepted;
+	if (fillbits && j->h_box->accepted >= 0) memcpy(fillbits, (const void *) j->h_box->bits, (size_t) ((M + 63) / 64) * 8);
+	return 0;
 }
 
 extern "C" int mdns_joint_fetch(mdns_joint *j, int M, int *accepted, unsigned long long *fillbits)
 {
 	if (!ctx() || !j || !accepted) return 1;
 	if (M < 0 || M > j->ndata) { set_error("mdns_joint_fetch: M=%d", M); return 1; }
-	if (!joint_wait_box(j, "mdns_joint_fetch")) return 1;
-	if (j->h_box->status) { status_error("mdns_joint_fetch", j->h_box->status, j->cap); return 1; }
-	*accepted = j->h_box->accepted;
-	if (fillbits && j->h_box->accepted >= 0) memcpy(fillbits, (const void *) j->h_box->bits, (size_t) ((M + 63) / 64) * 8);
-	return 0;
+	return joint_read_box(j, M, accepted, fillbits, "mdns_joint_fetch");
 }
 
 // host-pointer halves of the draw: `score` stages candidates and selection and leaves the accept
@@ -1090,15 +1095,8 @@ static int joint_commit_and_fetch(mdns_joint *j, int *accepted, double *Lrow, un
 	j->staged_valid = false;
 	const int M = j->staged_M;
 	if (joint_commit_dev(j, j->staged_rows ? j->d_rows : nullptr, M, Lrow != nullptr, who) != 0) return 1;
-	if (!Lrow) {
-		// no likelihood row wanted: the kernel leaves {accepted, status, fill words} in mapped host
-		// memory -- no copy, no stream synchronisation
-		if (!joint_wait_box(j, who)) return 1;
-		if (j->h_box->status) { status_error(who, j->h_box->status, j->cap); return 1; }
-		*accepted = j->h_box->accepted;
-		if (fillbits && j->h_box->accepted >= 0) memcpy(fillbits, (const void *) j->h_box->bits, (size_t) ((M + 63) / 64) * 8);
-		return 0;
-	}
+	// no likelihood row wanted: the kernel leaves the outcome in mapped host memory
+	if (!Lrow) return joint_read_box(j, M, accepted, fillbits, who);
 	// the header says whether the rest matters, but one copy of at most 80 KB costs less than a
 	// second round trip; a caller that does not ask for the likelihood row gets header + bits
 	const size_t out_bytes = Lrow ? result_bytes(M) : sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8;
@@ -1220,48 +1218,145 @@ extern "C" int mdns_backend_draw_begin(void *joint, const int *rows, int M)
 	return 0;
 }
 
-// the chunk for kind 1: templates + K2 into the dense block, jitter, accept flags, commit, mailbox
-static int backend_chunk_muse(mdns_joint *j, const double *params, int B, const double *jitter, int M)
+// ---------------------------------------------------------------------------------------
+// the pieces of a backend chunk: selection, chunk flag, score, commit, fetch
+// ---------------------------------------------------------------------------------------
+// the selection of the draw in progress as the kernels take it: its row ids in device memory, or nullptr for every data set
+static const int *selection_rows(const mdns_joint *j) { return j->sel_rows ? j->d_sel_rows : nullptr; }
+
+// the same, uploaded if no chunk of this draw has put it there yet
+static bool selection_to_device(mdns_joint *j, Context *c, const int **d_rows)
 {
-	Context *c = ctx();
-	const size_t pbytes = (size_t) B * 5 * sizeof(double), n = (size_t) B * M;
+	if (j->sel_rows && !j->sel_on_device) {
+		// (the mapped block is pinned: a plain asynchronous copy)
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) j->sel_M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return false;
+		j->sel_on_device = true;
+	}
+	*d_rows = selection_rows(j);
+	return true;
+}
+
+// for the accept kernels that read the selection from the mapped block on the first chunk of a draw and leave it in
+// d_sel_rows on the way (out; the caller sets sel_on_device once its launch is out)
+struct SelectionIO { const int *in; int *out; };
+static SelectionIO selection_for_accept(const mdns_joint *j)
+{
+	SelectionIO rows = {nullptr, nullptr};
+	if (j->sel_rows) {
+		if (j->sel_on_device) rows.in = j->d_sel_rows;
+		else { rows.in = (const int *) (j->h_in_dev + kInParams); rows.out = j->d_sel_rows; }
+	}
+	return rows;
+}
+
+// the number of the next chunk, with which its accept pass flags candidates (mdns_joint::chunk_seq: the flags are cleared
+// only when the numbers start over); 0: the clearing failed
+static int next_chunk_flag(mdns_joint *j, Context *c)
+{
+	if (j->chunk_seq == 0x7fffffff) {
+		if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 0;
+		j->chunk_seq = 1;
+	}
+	return ++j->chunk_seq;
+}
+
+// First half of a chunk (B > 0 candidates over a selection of sel_M > 0): candidates, and likelihood noise if any, to the
+// device and the accept pass; *out tells the commit which pass it was.
+static int backend_score(mdns_joint *j, Context *c, const double *params, int B, const double *jitter, ChunkScore *out, const char *who)
+{
+	const int M = j->sel_M;
+	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
+	out->B = B;
+	if (j->kind == 1) {
+		// templates + K2 into the dense block, jitter, accept flags
+		const size_t pbytes = (size_t) B * 5 * sizeof(double), n = (size_t) B * M;
+		char *pin = joint_pin(j, pbytes);
+		if (!pin) return 1;
+		memcpy(pin, params, pbytes);
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+		const int *d_rows;
+		if (!selection_to_device(j, c, &d_rows)) return 1;
+		if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
+		if (jitter) {
+			if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
+			// (pageable source: the runtime stages it and returns when the caller's buffer is free)
+			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+		}
+		if (mdns_muse3_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
+		const int flag = next_chunk_flag(j, c);
+		if (!flag) return 1;
+		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
+		                   j->d_dense, jitter ? (const double *) j->d_jitter : nullptr, B, M, d_rows, (const double *) j->st.higher,
+		                   j->d_flags, flag, (JointHeader *) j->d_result);
+		out->path = 1; out->flag = flag;
+		return 0;
+	}
+	if (jitter) { set_error("%s: likelihood jitter is not part of the Gaussian-line problem", who); return 1; }
+	const size_t pbytes = (size_t) B * 24;
+	static const char *chunk_path = getenv("MDNS_CHUNK_PATH");        // "classic": the five-command chunk (experiments)
+	if (chunk_fits(j->s, M, B) && !(chunk_path && !strcmp(chunk_path, "classic"))) {
+		// two launches: the kernels read candidates and (first chunk of the draw) the selection
+		// from the mapped block; nothing is copied, nothing is cleared
+		memcpy(j->h_in, params, pbytes);
+		JointTrail trail;
+		if (!joint_trail(j, B, M, &trail)) return 1;
+		const SelectionIO rows = selection_for_accept(j);
+		const double scale = -0.5 / (j->noise_level * j->noise_level);
+		const int flag = next_chunk_flag(j, c);
+		if (!flag) return 1;
+		if (!launch_chunk_accept(j->s, (const double *) j->h_in_dev, B, scale, rows.in, rows.out, M, j->st.higher,
+		                         j->d_flags, flag, trail, j->d_result)) return 1;
+		if (j->sel_rows) j->sel_on_device = true;
+		out->path = 2; out->flag = flag;
+		return 0;
+	}
 	char *pin = joint_pin(j, pbytes);
 	if (!pin) return 1;
 	memcpy(pin, params, pbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	if (j->sel_rows && !j->sel_on_device) {
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-		j->sel_on_device = true;
+	const int *d_rows;
+	if (!selection_to_device(j, c, &d_rows)) return 1;
+	if (mdns_joint_score_dev(j, j->d_params, B, j->noise_level, d_rows, M) != 0) return 1;
+	out->path = 3; out->flag = 1;
+	return 0;
+}
+
+// Second half: the first candidate b with decides[b] == value is the accepted one -- its fill bits, shelf appends and
+// new thresholds, and the outcome into the mailbox.  A chunk in one piece decides on the accept flags as they are; the
+// halves on the votes, which are 0 / 1.
+static int backend_commit(mdns_joint *j, Context *c, const ChunkScore &sc, const int *decides, int value, const char *who)
+{
+	const int M = j->sel_M;
+	const int *thr_rows = selection_rows(j);
+	if (sc.path == 1) {
+		const int ntiles = (M + 63) / 64;
+		hipLaunchKernelGGL(k_joint_commit_dense, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
+		                   (const double *) j->d_dense, thr_rows, M, sc.B, ntiles, decides, value, j->st, (JointHeader *) j->d_result, result_bits(j));
+		launch_publish(j, c, M);
+		if (!MDNS_HIP(hipGetLastError())) return 1;
+	} else if (sc.path == 2) {
+		if (!commit_from_trail(j, thr_rows, M, sc.B, decides, value, true)) return 1;
+	} else {
+		// the lane kernels' flags are 0 / 1 themselves: votes go back into them
+		if (decides != j->d_flags &&
+		    !MDNS_HIP(hipMemcpyAsync(j->d_flags, decides, (size_t) sc.B * sizeof(int), hipMemcpyDeviceToDevice, c->stream))) return 1;
+		if (joint_commit_dev(j, thr_rows, M, false, who) != 0) return 1;
 	}
-	const int *d_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-	if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
-	if (jitter) {
-		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
-		// (pageable source: the runtime stages it and returns when the caller's buffer is free)
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	}
-	if (mdns_muse3_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
-	if (j->chunk_seq == 0x7fffffff) {
-		if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 1;
-		j->chunk_seq = 1;
-	}
-	const int flag = ++j->chunk_seq;
-	char *base = j->d_result;
-	unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-	                   j->d_dense, jitter ? (const double *) j->d_jitter : nullptr, B, M, d_rows, (const double *) j->st.higher,
-	                   j->d_flags, flag, (JointHeader *) base);
-	const int ntiles = (M + 63) / 64;
-	hipLaunchKernelGGL(k_joint_commit_dense, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-	                   (const double *) j->d_dense, d_rows, M, B, ntiles, (const int *) j->d_flags, flag, j->st, (JointHeader *) base, bits);
-	hipLaunchKernelGGL(k_joint_publish, dim3(1), dim3(kBlock), 0, c->stream, (const JointHeader *) base, bits, ntiles, j->h_box_dev, ++j->box_seq);
-	if (!MDNS_HIP(hipGetLastError())) return 1;
 	j->box_pending = true;
 	j->trail_valid = false;
 	j->last_B = 0;
 	return 0;
 }
 
+// the outcome of the chunk just committed; an accepted candidate lengthens some shelf
+static int backend_fetch(mdns_joint *j, int *accepted, unsigned long long *fillbits)
+{
+	if (mdns_joint_fetch(j, j->sel_M, accepted, fillbits) != 0) return 1;
+	if (*accepted >= 0) j->shelf_bound++;
+	return 0;
+}
+
+// one chunk: score, commit on the accept flags (no votes in between: mdns_backend_draw_score / _commit have those), outcome
 extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B, const double *jitter, int *accepted,
                                        unsigned long long *fillbits, int *nscored)
 {
@@ -1274,67 +1369,10 @@ extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B,
 	if (!check_draw(j, B, M, "mdns_backend_draw_chunk")) return 1;
 	if (nscored) *nscored = B;
 	if (B == 0 || M == 0) return 0;
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
-	if (j->kind == 1) {
-		if (backend_chunk_muse(j, params, B, jitter, M) != 0) return 1;
-		if (mdns_joint_fetch(j, M, accepted, fillbits) != 0) return 1;
-		if (*accepted >= 0) j->shelf_bound++;
-		return 0;
-	}
-	if (jitter) { set_error("mdns_backend_draw_chunk: likelihood jitter is not part of the Gaussian-line problem"); return 1; }
-	const size_t pbytes = (size_t) B * 24;
-	static const char *chunk_path = getenv("MDNS_CHUNK_PATH");        // "classic": the five-command chunk (experiments)
-	if (chunk_fits(j->s, M, B) && !(chunk_path && !strcmp(chunk_path, "classic"))) {
-		// two launches: the kernels read candidates and (first chunk of the draw) the selection
-		// from the mapped block; nothing is copied, nothing is cleared
-		memcpy(j->h_in, params, pbytes);
-		JointTrail trail;
-		if (!joint_trail(j, B, M, &trail)) return 1;
-		const int *rows_in = nullptr;
-		int *rows_out = nullptr;
-		if (j->sel_rows) {
-			if (j->sel_on_device) rows_in = j->d_sel_rows;
-			else { rows_in = (const int *) (j->h_in_dev + kInParams); rows_out = j->d_sel_rows; }
-		}
-		const double scale = -0.5 / (j->noise_level * j->noise_level);
-		if (j->chunk_seq == 0x7fffffff) {
-			if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 1;
-			j->chunk_seq = 1;
-		}
-		const int flag = ++j->chunk_seq;
-		char *base = j->d_result;
-		unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-		if (!launch_chunk_accept(j->s, (const double *) j->h_in_dev, B, scale, rows_in, rows_out, M, j->st.higher,
-		                         j->d_flags, flag, trail, base)) return 1;
-		if (j->sel_rows) j->sel_on_device = true;
-		const int *thr_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-		if (M <= 128) {
-			// a tile or two: shelf appends, thresholds and the mailbox in ONE workgroup
-			if (!launch_chunk_commit(thr_rows, M, B, j->d_flags, flag, trail, j->st, base, bits, j->h_box_dev, ++j->box_seq)) return 1;
-		} else {
-			if (!commit_ticket(j) || !launch_joint_commit_trail(thr_rows, M, B, j->d_flags, trail, j->st, base, bits, flag, j->h_box_dev,
-			                                                    ++j->box_seq, j->d_commit_ticket)) return 1;
-		}
-		j->box_pending = true;
-		j->trail_valid = false;
-		j->last_B = 0;
-	} else {
-		char *pin = joint_pin(j, pbytes);
-		if (!pin) return 1;
-		memcpy(pin, params, pbytes);
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-		if (j->sel_rows && !j->sel_on_device) {
-			// (the mapped block is pinned: a plain asynchronous copy)
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-			j->sel_on_device = true;
-		}
-		const int *d_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-		if (mdns_joint_score_dev(j, j->d_params, B, j->noise_level, d_rows, M) != 0) return 1;
-		if (joint_commit_dev(j, d_rows, M, false, "mdns_backend_draw_chunk") != 0) return 1;
-	}
-	if (mdns_joint_fetch(j, M, accepted, fillbits) != 0) return 1;
-	if (*accepted >= 0) j->shelf_bound++;
-	return 0;
+	ChunkScore sc;
+	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_chunk") != 0) return 1;
+	if (backend_commit(j, c, sc, j->d_flags, sc.flag, "mdns_backend_draw_chunk") != 0) return 1;
+	return backend_fetch(j, accepted, fillbits);
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,
@@ -1421,33 +1459,16 @@ extern "C" int mdns_backend_chain_begin(void *joint, void *region, const mdns_ch
 	if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props, j->d_chain_counts, nullptr)) return 1;
 	JointTrail trail;
 	if (!joint_trail(j, limit, M, &trail)) return 1;
-	const int *rows_in = nullptr;
-	int *rows_out = nullptr;
-	if (j->sel_rows) {
-		if (j->sel_on_device) rows_in = j->d_sel_rows;
-		else { rows_in = (const int *) (j->h_in_dev + kInParams); rows_out = j->d_sel_rows; }
-	}
+	const SelectionIO rows = selection_for_accept(j);
 	const double scale = -0.5 / (j->noise_level * j->noise_level);
-	if (j->chunk_seq == 0x7fffffff) {
-		if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 1;
-		j->chunk_seq = 1;
-	}
-	const int flag = ++j->chunk_seq;
-	char *base = j->d_result;
-	unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-	if (!launch_chain_accept(j->s, spec, j->d_chain_props, j->d_chain_counts, j->h_chain_dev, scale, rows_in, rows_out, M,
-	                         j->st.higher, j->d_flags, flag, trail, base)) return 1;
+	const int flag = next_chunk_flag(j, c);
+	if (!flag) return 1;
+	if (!launch_chain_accept(j->s, spec, j->d_chain_props, j->d_chain_counts, j->h_chain_dev, scale, rows.in, rows.out, M,
+	                         j->st.higher, j->d_flags, flag, trail, j->d_result)) return 1;
 	if (j->sel_rows) j->sel_on_device = true;
-	const int *thr_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-	if (M <= 128) {
-		if (!launch_chunk_commit(thr_rows, M, limit, j->d_flags, flag, trail, j->st, base, bits, j->h_box_dev, ++j->box_seq)) return 1;
-	} else {
-		if (!commit_ticket(j) || !launch_joint_commit_trail(thr_rows, M, limit, j->d_flags, trail, j->st, base, bits, flag, j->h_box_dev,
-		                                                    ++j->box_seq, j->d_commit_ticket)) return 1;
-	}
-	j->box_pending = true;
-	j->trail_valid = false;
-	j->last_B = 0;
+	// (committed as a two-launch chunk of `limit` candidates: the first min(kept, limit) proposals)
+	const ChunkScore sc = {2, limit, flag};
+	if (backend_commit(j, c, sc, j->d_flags, flag, "mdns_backend_chain_begin") != 0) return 1;
 	j->chain_state = 2;
 	return 0;
 }
@@ -1463,23 +1484,16 @@ extern "C" int mdns_backend_chain_end(void *joint, void *region, int *counts, in
 	j->chain_state = 0;
 	*accepted = -1; *nkept = -1; *B = 0;
 	if (state == 1) {
-		volatile unsigned long long *at = &j->h_chain->seq;
-		long long started = 0;
-		for (unsigned spin = 0; *at != j->chain_seq; spin++) {
-			if ((spin & 1023) != 1023) continue;
-			const hipError_t e = hipStreamQuery(c->stream);
-			if (e == hipErrorNotReady) {
-				if (poll_expired(&started)) { set_error("chain: no membership counts within MDNS_POLL_TIMEOUT_S"); return 1; }
-				continue;
-			}
-			if (e != hipSuccess) { set_error("chain: the membership count failed: %s", hipGetErrorString(e)); return 1; }
-			if (*at != j->chain_seq) {
-				(void) hipMemsetAsync(j->d_chain_ticket, 0, sizeof(int), c->stream);
-				set_error("chain: the membership count finished without a result");
-				return 1;
-			}
+		hipError_t e = hipSuccess;
+		switch (wait_seq(&j->h_chain->seq, j->chain_seq, &e)) {
+		case Wait::ok: break;
+		case Wait::timeout: set_error("chain: no membership counts within MDNS_POLL_TIMEOUT_S"); return 1;
+		case Wait::failed: set_error("chain: the membership count failed: %s", hipGetErrorString(e)); return 1;
+		case Wait::empty:
+			(void) hipMemsetAsync(j->d_chain_ticket, 0, sizeof(int), c->stream);
+			set_error("chain: the membership count finished without a result");
+			return 1;
 		}
-		std::atomic_thread_fence(std::memory_order_acquire);
 		memcpy(counts, (const void *) j->h_chain->counts, (size_t) j->chain_n * sizeof(int));
 		return 0;
 	}
@@ -1509,6 +1523,7 @@ __global__ void k_flags_to_votes(const int *__restrict__ flags, int value, int *
 
 extern "C" int *mdns_joint_votes_dev(mdns_joint *j) { return j ? j->d_votes : nullptr; }
 
+// first half: the score, then one 0 / 1 vote per candidate from its accept flags
 extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B, const double *jitter)
 {
 	Context *c = ctx();
@@ -1518,70 +1533,13 @@ extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B,
 	const int M = j->sel_M;
 	if (!check_draw(j, B, M, "mdns_backend_draw_score")) return 1;
 	if (!j->d_votes && !MDNS_HIP(hipMalloc((void **) &j->d_votes, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int)))) return 1;
-	j->half_path = 0; j->half_B = B;
+	j->half = {0, B, 0};
 	if (!MDNS_HIP(hipMemsetAsync(j->d_votes, 0, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int), c->stream))) return 1;
-	if (B == 0 || M == 0) { j->half_path = -1; return 0; }          // (nothing of this rank's is selected: no vote)
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
-	if (j->chunk_seq == 0x7fffffff) {
-		if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 1;
-		j->chunk_seq = 1;
-	}
-	char *base = j->d_result;
-	if (j->kind == 1) {
-		const size_t pbytes = (size_t) B * 5 * sizeof(double), n = (size_t) B * M;
-		char *pin = joint_pin(j, pbytes);
-		if (!pin) return 1;
-		memcpy(pin, params, pbytes);
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-		if (j->sel_rows && !j->sel_on_device) {
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-			j->sel_on_device = true;
-		}
-		const int *d_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-		if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
-		if (jitter) {
-			if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		}
-		if (mdns_muse3_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
-		const int flag = ++j->chunk_seq;
-		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-		                   j->d_dense, jitter ? (const double *) j->d_jitter : nullptr, B, M, d_rows, (const double *) j->st.higher,
-		                   j->d_flags, flag, (JointHeader *) base);
-		j->half_path = 1; j->half_flag = flag;
-	} else {
-		if (jitter) { set_error("mdns_backend_draw_score: likelihood jitter is not part of the Gaussian-line problem"); return 1; }
-		const size_t pbytes = (size_t) B * 24;
-		if (chunk_fits(j->s, M, B)) {
-			memcpy(j->h_in, params, pbytes);
-			JointTrail trail;
-			if (!joint_trail(j, B, M, &trail)) return 1;
-			const int *rows_in = nullptr;
-			int *rows_out = nullptr;
-			if (j->sel_rows) {
-				if (j->sel_on_device) rows_in = j->d_sel_rows;
-				else { rows_in = (const int *) (j->h_in_dev + kInParams); rows_out = j->d_sel_rows; }
-			}
-			const double scale = -0.5 / (j->noise_level * j->noise_level);
-			const int flag = ++j->chunk_seq;
-			if (!launch_chunk_accept(j->s, (const double *) j->h_in_dev, B, scale, rows_in, rows_out, M, j->st.higher,
-			                         j->d_flags, flag, trail, base)) return 1;
-			if (j->sel_rows) j->sel_on_device = true;
-			j->half_path = 2; j->half_flag = flag;
-		} else {
-			char *pin = joint_pin(j, pbytes);
-			if (!pin) return 1;
-			memcpy(pin, params, pbytes);
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-			if (j->sel_rows && !j->sel_on_device) {
-				if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-				j->sel_on_device = true;
-			}
-			if (mdns_joint_score_dev(j, j->d_params, B, j->noise_level, j->sel_rows ? j->d_sel_rows : nullptr, M) != 0) return 1;
-			j->half_path = 3; j->half_flag = 1;
-		}
-	}
-	hipLaunchKernelGGL(k_flags_to_votes, dim3((B + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const int *) j->d_flags, j->half_flag, j->d_votes, B);
+	if (B == 0 || M == 0) { j->half.path = -1; return 0; }          // (nothing of this rank's is selected: no vote)
+	ChunkScore sc;
+	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_score") != 0) return 1;
+	j->half = sc;
+	hipLaunchKernelGGL(k_flags_to_votes, dim3((B + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const int *) j->d_flags, sc.flag, j->d_votes, B);
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -1593,45 +1551,19 @@ extern "C" int mdns_backend_draw_commit(void *joint, int *accepted, unsigned lon
 	mdns_joint *j = (mdns_joint *) joint;
 	if (!c || !j || !accepted) return 1;
 	*accepted = -1;
-	const int path = j->half_path, B = j->half_B, M = j->sel_M;
-	j->half_path = 0;
-	if (path == 0) { set_error("mdns_backend_draw_commit: no mdns_backend_draw_score precedes"); return 1; }
-	if (path < 0) {
+	const ChunkScore sc = j->half;
+	j->half.path = 0;
+	if (sc.path == 0) { set_error("mdns_backend_draw_commit: no mdns_backend_draw_score precedes"); return 1; }
+	if (sc.path < 0) {
 		// nothing of this handle's was scored: the accepted candidate is whoever the votes name
+		const int B = sc.B;
 		std::vector<int> votes((size_t) (B > 0 ? B : 1), 0);
 		if (B > 0 && (!MDNS_HIP(hipMemcpyAsync(votes.data(), j->d_votes, (size_t) B * sizeof(int), hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c))) return 1;
 		for (int b = 0; b < B; b++) if (votes[b]) { *accepted = b; break; }
 		return 0;
 	}
-	char *base = j->d_result;
-	unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-	const int ntiles = (M + 63) / 64;
-	const int *thr_rows = j->sel_rows ? j->d_sel_rows : nullptr;
-	if (path == 1) {
-		hipLaunchKernelGGL(k_joint_commit_dense, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-		                   (const double *) j->d_dense, thr_rows, M, B, ntiles, (const int *) j->d_votes, 1, j->st, (JointHeader *) base, bits);
-		hipLaunchKernelGGL(k_joint_publish, dim3(1), dim3(kBlock), 0, c->stream, (const JointHeader *) base, bits, ntiles, j->h_box_dev, ++j->box_seq);
-		if (!MDNS_HIP(hipGetLastError())) return 1;
-		j->box_pending = true;
-	} else if (path == 2) {
-		const JointTrail trail = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L, j->trail_stamp};
-		if (M <= 128) {
-			if (!launch_chunk_commit(thr_rows, M, B, j->d_votes, 1, trail, j->st, base, bits, j->h_box_dev, ++j->box_seq)) return 1;
-		} else {
-			if (!commit_ticket(j) || !launch_joint_commit_trail(thr_rows, M, B, j->d_votes, trail, j->st, base, bits, 1, j->h_box_dev, ++j->box_seq,
-			                                                    j->d_commit_ticket)) return 1;
-		}
-		j->box_pending = true;
-	} else {
-		// the lane kernels' flags are 0 / 1 themselves: the votes go back into them
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_flags, j->d_votes, (size_t) B * sizeof(int), hipMemcpyDeviceToDevice, c->stream))) return 1;
-		if (joint_commit_dev(j, thr_rows, M, false, "mdns_backend_draw_commit") != 0) return 1;
-	}
-	j->trail_valid = false;
-	j->last_B = 0;
-	if (mdns_joint_fetch(j, M, accepted, fillbits) != 0) return 1;
-	if (*accepted >= 0) j->shelf_bound++;
-	return 0;
+	if (backend_commit(j, c, sc, j->d_votes, 1, "mdns_backend_draw_commit") != 0) return 1;
+	return backend_fetch(j, accepted, fillbits);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1646,7 +1578,7 @@ static int band_launch(mdns_joint *j, bool filtered)
 {
 	Context *c = ctx();
 	const int B = j->band_B, M = j->sel_M;
-	const int *d_rows = j->sel_rows ? j->d_sel_rows : nullptr;
+	const int *d_rows = selection_rows(j);
 	const double *d_p = j->d_bound, *d_b = j->d_bound + (size_t) B * 5;
 	if (filtered) {
 		const int ldm = model_ld(j->s->nx) + 16;            // (not a power of two: mdns_k2gemm.hip, muse_filter_ld)
@@ -1698,10 +1630,8 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 	memcpy(pin, params, pbytes);
 	memcpy(pin + pbytes, bound, bbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_bound, pin, pbytes + bbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	if (j->sel_rows && !j->sel_on_device) {
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-		j->sel_on_device = true;
-	}
+	const int *d_rows;
+	if (!selection_to_device(j, c, &d_rows)) return 1;              // (band_launch takes it from the handle)
 	if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
 	j->band_B = B;
 	j->trail_valid = false;
@@ -1730,19 +1660,13 @@ extern "C" int mdns_backend_draw_band_end(void *joint, int *status, int *npairs,
 	j->band_pending = false;
 	const int B = j->band_B;
 	for (;;) {
-		volatile unsigned long long *at = &j->h_band->seq;
-		long long started = 0;
-		for (unsigned spin = 0; *at != j->band_seq; spin++) {
-			if ((spin & 1023) != 1023) continue;
-			const hipError_t e = hipStreamQuery(c->stream);
-			if (e == hipErrorNotReady) {
-				if (poll_expired(&started)) { set_error("mdns_backend_draw_band: no outcome within MDNS_POLL_TIMEOUT_S"); return 1; }
-				continue;
-			}
-			if (e != hipSuccess) { set_error("mdns_backend_draw_band: %s", hipGetErrorString(e)); return 1; }
-			if (*at != j->band_seq) { set_error("mdns_backend_draw_band: finished without an outcome"); return 1; }
+		hipError_t e = hipSuccess;
+		switch (wait_seq(&j->h_band->seq, j->band_seq, &e)) {
+		case Wait::ok: break;
+		case Wait::timeout: set_error("mdns_backend_draw_band: no outcome within MDNS_POLL_TIMEOUT_S"); return 1;
+		case Wait::failed: set_error("mdns_backend_draw_band: %s", hipGetErrorString(e)); return 1;
+		case Wait::empty: set_error("mdns_backend_draw_band: finished without an outcome"); return 1;
 		}
-		std::atomic_thread_fence(std::memory_order_acquire);
 		if (j->band_exact || j->h_band->npairs == 0) break;
 		muse_filter_note(1);
 		if (band_launch(j, false) != 0) return 1;
@@ -1772,6 +1696,7 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 	if (!c || !j || !jitter_row) { set_error("mdns_backend_draw_band_commit: null argument"); return 1; }
 	if (j->kind != 1 || !j->sel_open || j->band_B <= 0 || b < 0 || b >= j->band_B) { set_error("mdns_backend_draw_band_commit: candidate %d of a chunk of %d", b, j->band_B); return 1; }
 	const int M = j->sel_M, ntiles = (M + 63) / 64;
+	const int *d_rows = selection_rows(j);
 	if (!j->band_exact) {
 		// the chunk went through the matrix-core filter: what the state keeps is the exact kernel's row --
 		// from the instantiation that would have scored the whole block, bit for bit (the templates of
@@ -1779,7 +1704,7 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 		const int ldm = model_ld(j->s->nx) + 16, Bc = j->band_B;
 		const int lo = muse_rows_variant(Bc, M) == 1 ? (b & ~1) : b;
 		const int nb = lo == b && muse_rows_variant(Bc, M) != 1 ? 1 : (Bc - lo < 2 ? Bc - lo : 2);
-		if (!launch_muse_rows(j->s, j->s->d_model + (size_t) lo * ldm, ldm, nb, j->sel_rows ? j->d_sel_rows : nullptr, M,
+		if (!launch_muse_rows(j->s, j->s->d_model + (size_t) lo * ldm, ldm, nb, d_rows, M,
 		                      j->d_dense + (size_t) lo * M, Bc)) return 1;
 		muse_filter_note(2);
 	}
@@ -1789,12 +1714,9 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 	if (!pin) return 1;
 	memcpy(pin, jitter_row, (size_t) M * sizeof(double));
 	if (!MDNS_HIP(hipMemcpyAsync(d_row, pin, (size_t) M * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	char *base = j->d_result;
-	unsigned long long *bits = (unsigned long long *) (base + sizeof(JointHeader));
-	const int *d_rows = j->sel_rows ? j->d_sel_rows : nullptr;
 	hipLaunchKernelGGL(k_joint_commit_band, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-	                   (const double *) j->d_dense, (const double *) d_row, d_rows, M, b, ntiles, j->st, (JointHeader *) base, bits);
-	hipLaunchKernelGGL(k_joint_publish, dim3(1), dim3(kBlock), 0, c->stream, (const JointHeader *) base, bits, ntiles, j->h_box_dev, ++j->box_seq);
+	                   (const double *) j->d_dense, (const double *) d_row, d_rows, M, b, ntiles, j->st, (JointHeader *) j->d_result, result_bits(j));
+	launch_publish(j, c, M);
 	if (!MDNS_HIP(hipGetLastError())) return 1;
 	j->box_pending = true;
 	int accepted = -1;
