@@ -23,23 +23,12 @@
 // fewer than one argument in 10^4, never off by more than an ulp; the C library's own pow is off by an
 // ulp more often).  The sum of a (candidate, spectrum) pair is the chain
 // of every other K1 form: channels ascending, d = m - y, acc = fma(d, d, acc).
-#include "mdns_internal.h"
+#include "mdns_quad.h"
 #include "mdns_pow10.h"
 
 #pragma clang fp contract(off)
 
 namespace mdns {
-
-static constexpr int kCH = 8;              // channels per stage (as mdns_chunk.hip)
-
-template <int Q>
-__device__ __forceinline__ double quad_bcast(double v)
-{
-	constexpr int ctrl = Q | (Q << 2) | (Q << 4) | (Q << 6);
-	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, true);
-	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, true);
-	return __hiloint2double(hi, lo);
-}
 
 // proposal i, dimension k: lo + (hi - lo) u with lo = mn - r, hi = mx + r (the host's operations, one
 // rounding each: host_constrainer.cpp, Region::box and the BOX phase)
@@ -145,17 +134,8 @@ __global__ __launch_bounds__(256) void k_chain_accept(
 	const int kk = live ? k : M - 1;
 	const int row = rows ? rows[kk] : kk;
 	if (rows_dev && bt == 0 && live && q == 0) rows_dev[k] = row;
-	const double *yr = Y + (size_t) row * ld;
-	const int nst = nxp / kCH;
 	double2 y[NST];
-#pragma unroll
-	for (int s = 0; s < NST; s++) {
-		const int j = s * kCH + 2 * q;
-		const double2 v = *reinterpret_cast<const double2 *>(yr + (j < ld ? j : 0));
-		y[s].x = j < ld ? v.x : 0.0;
-		y[s].y = j < ld ? v.y : 0.0;
-	}
-	const double thr = live ? higher[row] : __builtin_nan("");
+	const double thr = quad_load_row<NST>(Y, ld, row, live, q, higher, y);
 	// 2. which proposals are candidates, and this tile's four
 	if (threadIdx.x < 12) par[threadIdx.x] = 0.0;
 	int base = 0;
@@ -210,57 +190,13 @@ __global__ __launch_bounds__(256) void k_chain_accept(
 	const int B = base < spec.limit ? base : spec.limit;
 	if (blockIdx.x == 0 && threadIdx.x == 0) { box->nkept = base; box->B = B; }
 	if (bt * 4 >= B) return;                                    // (whole workgroups)
-	// 3. templates of the candidate tile (clike.c:65)
-	for (int e = threadIdx.x; e < nxp * 4; e += 256) {
-		const int j = e >> 2, bb = e & 3;
-		double m = 0.0;
-		if (j < nx && bt * 4 + bb < B) {
-			const double A = par[bb * 3], mu = par[bb * 3 + 1], sig = par[bb * 3 + 2];
-			const double t = (mu - xgrid[j]) / sig;
-			m = A * exp(-0.5 * (t * t));
-		}
-		lds[((size_t) (j >> 1) * 4 + bb) * 2 + (j & 1)] = m;
-	}
+	// 3. templates of the candidate tile
+	quad_templates(lds, par, xgrid, nx, nxp, bt * 4, B);
 	__syncthreads();
 	// 4. the sum of (candidate q, this spectrum)
-	double acc = 0.0;
-#pragma unroll
-	for (int s = 0; s < NST; s++) {
-		if (s < nst) {
-			const double2 *m = tpl + (size_t) s * 16 + q;
-			double d;
-#define QUARTER(QQ) { const double2 mv = m[QQ * 4]; \
-			d = mv.x - quad_bcast<QQ>(y[s].x); acc = fma(d, d, acc); \
-			d = mv.y - quad_bcast<QQ>(y[s].y); acc = fma(d, d, acc); }
-			QUARTER(0) QUARTER(1) QUARTER(2) QUARTER(3)
-#undef QUARTER
-		}
-	}
+	const double L = quad_sum<NST>(tpl, nxp / kCH, q, y) * scale;
 	// 5. accept test
-	const double L = acc * scale;
-	const bool beat = L > thr && bt * 4 + q < B;
-	const unsigned long long vote = __ballot(beat);
-	if (lane == 0) votes[wave] = vote;
-	if (beat) trail.L[((size_t) (bt * 4 + q) * ntiles + tile) * 64 + r] = L;
-	__syncthreads();
-	{
-		const int cand = wave;
-		const unsigned long long word = __ballot((votes[lane >> 4] >> (4 * (lane & 15) + cand)) & 1ull);
-		if (word != 0ull && lane == 0) {
-			const size_t at = (size_t) (bt * 4 + cand) * ntiles + tile;
-			flags[bt * 4 + cand] = stamp;
-			trail.word[at] = word;
-			trail.stamp_of[at] = trail.stamp;
-		}
-	}
-}
-
-static bool launched(const char *name)
-{
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) return true;
-	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
-	return false;
+	quad_vote(L, thr, bt * 4 + q < B, bt * 4 + q, true, bt * 4 + wave, ntiles, tile, r, votes, flags, stamp, trail);
 }
 
 bool launch_box_count(const RegionView &rv, const ChainSpec &spec, ChainBox *box_dev, double *d_props, int *d_counts,

@@ -17,34 +17,15 @@
 // Per (candidate, spectrum) the sum is the same chain as in the big lane kernel (mdns_like.hip):
 // channels in ascending order, d = m - y, acc = fma(d, d, acc), padding channels contributing
 // fma(0, 0, acc) -- so a likelihood does not depend on which kernel computed it.
-#include "mdns_internal.h"
+#include "mdns_quad.h"
 #include <cstdlib>
 
 namespace mdns {
 
-static constexpr int kCH = 8;              // channels per stage
-
 typedef JointMailbox ChunkMailbox;          // what the host finds in mapped memory after a chunk
 
-// quad broadcast: every lane of a quad gets the value lane Q of the quad holds (DPP quad_perm)
-template <int Q>
-__device__ __forceinline__ double quad_bcast(double v)
-{
-	constexpr int ctrl = Q | (Q << 2) | (Q << 4) | (Q << 6);
-	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, true);
-	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, true);
-	return __hiloint2double(hi, lo);
-}
-
-// Work of one workgroup: 64 selected spectra (one tile of the selection) x 4 candidates (one
-// candidate tile).  A quad of lanes shares ONE spectrum: lane q of the quad LOADS the q-th quarter
-// of every 64-byte stage of the row (so four adjacent lanes read one cache line and a wave's load
-// touches 16 lines -- with one lane per spectrum it would be 64 lines four times over, and the
-// texture-address unit, one line per clock, was the bound: 33 us measured), and SCORES candidate q
-// of the tile against the whole spectrum, the other three quarters of a stage arriving by quad
-// broadcasts (DPP moves inside the VALU).  The chain of a (candidate, spectrum) pair is unchanged:
-// one accumulator, channels ascending, d = m - y, acc = fma(d, d, acc).
-// NST = stages held in registers: the whole row is requested before the first sum starts.
+// Work of one workgroup: 64 selected spectra (one tile of the selection) x 4 candidates (one candidate tile), a quad
+// of lanes per spectrum, lane q scoring candidate q of the tile (mdns_quad.h).
 template <int NST>
 __global__ __launch_bounds__(256) void k_chunk_accept(
     const double *__restrict__ Y, int ld, int nx, int nxp, const double *__restrict__ xgrid,
@@ -73,64 +54,17 @@ __global__ __launch_bounds__(256) void k_chunk_accept(
 	const int kk = live ? k : M - 1;
 	const int row = rows ? rows[kk] : kk;
 	if (rows_dev && bt == 0 && live && q == 0) rows_dev[k] = row;      // for the commit kernel
-	const double *yr = Y + (size_t) row * ld;
-	const int nst = nxp / kCH;
 	double2 y[NST];
-#pragma unroll
-	for (int s = 0; s < NST; s++) {
-		const int j = s * kCH + 2 * q;
-		const double2 v = *reinterpret_cast<const double2 *>(yr + (j < ld ? j : 0));
-		// channels at or beyond the row's length are padding: zeros
-		y[s].x = j < ld ? v.x : 0.0;
-		y[s].y = j < ld ? v.y : 0.0;
-	}
-	const double thr = live ? higher[row] : __builtin_nan("");          // NaN compares false: no vote
-	// 3. templates of the candidate tile, computed here (clike.c:65: A exp(-0.5 ((mu - x)/sig)^2))
+	const double thr = quad_load_row<NST>(Y, ld, row, live, q, higher, y);
+	// 3. templates of the candidate tile
 	if (threadIdx.x < 12) par[threadIdx.x] = pv;
 	__syncthreads();
-	for (int e = threadIdx.x; e < nxp * 4; e += 256) {
-		const int j = e >> 2, bb = e & 3;
-		double m = 0.0;
-		if (j < nx && bt * 4 + bb < B) {
-			const double A = par[bb * 3], mu = par[bb * 3 + 1], sig = par[bb * 3 + 2];
-			const double t = (mu - xgrid[j]) / sig;
-			m = A * exp(-0.5 * (t * t));
-		}
-		lds[((size_t) (j >> 1) * 4 + bb) * 2 + (j & 1)] = m;
-	}
+	quad_templates(lds, par, xgrid, nx, nxp, bt * 4, B);
 	__syncthreads();
 	// 4. the sum of (candidate q, this spectrum)
-	double acc = 0.0;
-#pragma unroll
-	for (int s = 0; s < NST; s++) {
-		if (s < nst) {                                              // wave-uniform
-			const double2 *m = tpl + (size_t) s * 16 + q;           // 4 channel pairs x 4 candidates per stage
-			double d;
-#define QUARTER(QQ) { const double2 mv = m[QQ * 4]; \
-			d = mv.x - quad_bcast<QQ>(y[s].x); acc = fma(d, d, acc); \
-			d = mv.y - quad_bcast<QQ>(y[s].y); acc = fma(d, d, acc); }
-			QUARTER(0) QUARTER(1) QUARTER(2) QUARTER(3)
-#undef QUARTER
-		}
-	}
+	const double L = quad_sum<NST>(tpl, nxp / kCH, q, y) * scale;
 	// 5. accept test: lane (spectrum r, candidate q)
-	const double L = acc * scale;
-	const bool beat = L > thr && bt * 4 + q < B;
-	const unsigned long long vote = __ballot(beat);                 // bit 4 i + q: spectrum wave * 16 + i, candidate q
-	if (lane == 0) votes[wave] = vote;
-	if (beat) trail.L[((size_t) (bt * 4 + q) * ntiles + tile) * 64 + r] = L;
-	__syncthreads();
-	// wave w' puts together the word of candidate w': lane l = spectrum l of the tile
-	{
-		const int cand = wave;
-		const unsigned long long word = __ballot((votes[lane >> 4] >> (4 * (lane & 15) + cand)) & 1ull);
-		if (word != 0ull && lane == 0) {
-			const size_t at = (size_t) (bt * 4 + cand) * ntiles + tile;
-			flags[bt * 4 + cand] = stamp;
-			trail.word[at] = word;
-			trail.stamp_of[at] = trail.stamp;
-		}
-	}
+	quad_vote(L, thr, bt * 4 + q < B, bt * 4 + q, true, bt * 4 + wave, ntiles, tile, r, votes, flags, stamp, trail);
 }
 
 // The second half in one workgroup of 1024 threads (16 waves, each walking tiles wave, wave + 16,
@@ -141,12 +75,8 @@ __global__ __launch_bounds__(1024) void k_chunk_commit(
     ChunkMailbox *__restrict__ box, unsigned long long seq)
 {
 	__shared__ int s_first, s_status;
-	if (threadIdx.x == 0) { s_first = 0x7fffffff; s_status = 0; }
-	__syncthreads();
-	for (int b = threadIdx.x; b < B; b += 1024)
-		if (flags[b] == stamp) { atomicMin(&s_first, b); break; }
-	__syncthreads();
-	const int bstar = s_first;
+	if (threadIdx.x == 0) s_status = 0;
+	const int bstar = first_flagged<1024>(&s_first, flags, B, [=](int f) { return f == stamp; });
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	if (bstar < B) {
 		for (int tile = wave; tile < ntiles; tile += 16) {
@@ -155,35 +85,7 @@ __global__ __launch_bounds__(1024) void k_chunk_commit(
 			const int k = tile * 64 + lane;
 			if (k < M && (word >> lane & 1ull)) {
 				const int d = thr_rows ? thr_rows[k] : k;
-				const double L = trail.L[at * 64 + lane];
-				const double thr = st.higher[d];
-				const int n = st.shelfn[d];
-				if (n >= st.cap) {
-					atomicOr(&s_status, 1);
-				} else {
-					// (see k_joint_commit_trail: the (n+2)-th smallest of the enlarged set)
-					int at_most = 0;
-					double next = INFINITY;
-					int p = 0;
-					for (; p + 16 <= st.nlive; p += 16) {                 // sixteen loads in flight
-						double v[16];
-#pragma unroll
-						for (int u = 0; u < 16; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
-#pragma unroll
-						for (int u = 0; u < 16; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
-					}
-					for (; p < st.nlive; p++) {
-						const double v = st.live[(size_t) p * st.ndata + d];
-						if (v <= thr) at_most++; else next = fmin(next, v);
-					}
-					for (int e = 0; e < n; e++) {
-						const double v = st.shelfL[(size_t) e * st.ndata + d];
-						if (v <= thr) at_most++; else next = fmin(next, v);
-					}
-					st.shelfL[(size_t) n * st.ndata + d] = L;
-					st.shelfn[d] = n + 1;
-					st.higher[d] = at_most >= n + 2 ? thr : fmin(L, next);
-				}
+				if (!shelf_append<16>(st, d, trail.L[at * 64 + lane], st.higher[d])) atomicOr(&s_status, 1);
 			}
 			if (lane == 0) { fillbits[tile] = word; mail_store(&box->bits[tile], word); }
 		}
@@ -645,66 +547,17 @@ __global__ __launch_bounds__(256) void k_exact_list(
 	const bool live = k < M;
 	const int kk = live ? k : M - 1;
 	const int row = rows ? rows[kk] : kk;
-	const double *yr = Y + (size_t) row * ld;
-	const int nst = nxp / kCH;
 	double2 y[NST];
-#pragma unroll
-	for (int s = 0; s < NST; s++) {
-		const int j = s * kCH + 2 * q;
-		const double2 v = *reinterpret_cast<const double2 *>(yr + (j < ld ? j : 0));
-		y[s].x = j < ld ? v.x : 0.0;
-		y[s].y = j < ld ? v.y : 0.0;
-	}
-	const double thr = live ? higher[row] : __builtin_nan("");
+	const double thr = quad_load_row<NST>(Y, ld, row, live, q, higher, y);
 	for (int g = 0; g < n; g += 4) {
-		const int mine = g + q < n ? list[g + q] : -1;
-		// the listed candidates' template columns (tiled templates MT[tile16][channel][16]) into LDS
-		for (int e = threadIdx.x; e < nxp * 4; e += 256) {
-			const int j = e >> 2, bb = e & 3;
-			const int c = g + bb < n ? list[g + bb] : -1;
-			const double m = c >= 0 ? model_t[((size_t) (c >> 4) * nxp + j) * 16 + (c & 15)] : 0.0;
-			lds[((size_t) (j >> 1) * 4 + bb) * 2 + (j & 1)] = m;
-		}
+		quad_templates_listed(lds, model_t, nxp, list, g, n);
 		__syncthreads();
-		double acc = 0.0;
-#pragma unroll
-		for (int s = 0; s < NST; s++) {
-			if (s < nst) {
-				const double2 *m = tpl + (size_t) s * 16 + q;
-				double d;
-#define QUARTER(QQ) { const double2 mv = m[QQ * 4]; \
-				d = mv.x - quad_bcast<QQ>(y[s].x); acc = fma(d, d, acc); \
-				d = mv.y - quad_bcast<QQ>(y[s].y); acc = fma(d, d, acc); }
-				QUARTER(0) QUARTER(1) QUARTER(2) QUARTER(3)
-#undef QUARTER
-			}
-		}
-		const double L = acc * scale;
-		const bool beat = mine >= 0 && L > thr;
-		const unsigned long long vote = __ballot(beat);
-		if (lane == 0) votes[wave] = vote;
-		if (beat) trail.L[((size_t) mine * ntiles + tile) * 64 + r] = L;
-		__syncthreads();
-		{
-			const int c = g + wave < n ? list[g + wave] : -1;
-			const unsigned long long word = __ballot((votes[lane >> 4] >> (4 * (lane & 15) + wave)) & 1ull);
-			if (c >= 0 && word != 0ull && lane == 0) {
-				const size_t at = (size_t) c * ntiles + tile;
-				flags[c] = 1;
-				trail.word[at] = word;
-				trail.stamp_of[at] = trail.stamp;
-			}
-		}
+		const double L = quad_sum<NST>(tpl, nxp / kCH, q, y) * scale;
+		// (a candidate tile is four listed candidates: list[g .. g + 3], as far as the list goes)
+		const bool has_q = g + q < n, has_w = g + wave < n;
+		quad_vote(L, thr, has_q, has_q ? list[g + q] : -1, has_w, has_w ? list[g + wave] : -1, ntiles, tile, r, votes, flags, 1, trail);
 		__syncthreads();
 	}
-}
-
-static bool launched(const char *name)
-{
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) return true;
-	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
-	return false;
 }
 
 // whether a chunk of B candidates over M selected spectra takes the two-launch path

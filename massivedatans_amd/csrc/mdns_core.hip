@@ -35,6 +35,14 @@ bool hip_ok(hipError_t e, const char *what, const char *file, int line)
 	return false;
 }
 
+bool launched(const char *name)
+{
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) return true;
+	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
+	return false;
+}
+
 // ---------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------

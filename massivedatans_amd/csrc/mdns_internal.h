@@ -11,6 +11,8 @@ namespace mdns {
 void set_error(const char *fmt, ...);
 bool hip_ok(hipError_t e, const char *what, const char *file, int line);
 #define MDNS_HIP(call) ::mdns::hip_ok((call), #call, __FILE__, __LINE__)
+// behind every kernel launch: false (and the error set) when the launch of `name` was refused
+bool launched(const char *name);
 
 // Busy polls of mapped mailboxes give up after MDNS_POLL_TIMEOUT_S seconds (default 120): a wedged
 // kernel or a lost mailbox store becomes an error the caller can act on instead of a core spinning
@@ -310,6 +312,76 @@ __device__ __forceinline__ void handover_acquire() { __builtin_amdgcn_fence(__AT
 // a few microseconds that nobody needs: what the host reads is all in the mailbox.
 template <class T, class V> __device__ __forceinline__ void mail_store(T *at, V v) { __hip_atomic_store(at, (T) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ void mail_raise(unsigned long long *seq_at, unsigned long long seq) { handover_release(); mail_store(seq_at, seq); }
+
+// ---- what the commit kernels share (mdns_like.hip, mdns_chunk.hip, mdns_joint.hip) ----
+// Likelihood L, which beats the threshold `thr` of data set d, goes onto d's shelf, and d gets its next threshold
+// (multi_nested_sampler.py:482-485, :438-447; the numpy statement is HostJointState.commit / _threshold in
+// jointstate.py).  With n waiting the threshold was the (n+1)-th smallest of live + shelf, and L lies above it: the
+// (n+2)-th smallest of the enlarged set is the old threshold again when it occurs more than once, else the smaller of
+// L and the next value above it.  False, and nothing changed, when the shelf is full: the caller raises its status
+// bit.  One lane per data set: no two callers share state.  U live-point loads are in flight at a time (the latency
+// of a round trip, not the count, is what this pass costs); counts and fmin do not depend on the order, so neither
+// does the result on U.
+template <int U>
+__device__ __forceinline__ bool shelf_append(const JointArrays &st, int d, double L, double thr)
+{
+	const int n = st.shelfn[d];
+	if (n >= st.cap) return false;
+	int at_most = 0;
+	double next = INFINITY;
+	int p = 0;
+	for (; p + U <= st.nlive; p += U) {
+		double v[U];
+#pragma unroll
+		for (int u = 0; u < U; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
+#pragma unroll
+		for (int u = 0; u < U; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
+	}
+	for (; p < st.nlive; p++) {
+		const double v = st.live[(size_t) p * st.ndata + d];
+		if (v <= thr) at_most++; else next = fmin(next, v);
+	}
+	for (int e = 0; e < n; e++) {
+		const double v = st.shelfL[(size_t) e * st.ndata + d];
+		if (v <= thr) at_most++; else next = fmin(next, v);
+	}
+	st.shelfL[(size_t) n * st.ndata + d] = L;
+	st.shelfn[d] = n + 1;
+	st.higher[d] = at_most >= n + 2 ? thr : fmin(L, next);
+	return true;
+}
+
+// The first flagged candidate is THE accepted point (hiermetriclearn.py:193-196): the lowest b < B with
+// flagged(flags[b]), or INT_MAX.  Every thread of the workgroup (BLOCK threads) calls; s_first: an LDS int of the
+// caller's.
+template <int BLOCK, class Flagged>
+__device__ __forceinline__ int first_flagged(int *s_first, const int *__restrict__ flags, int B, Flagged flagged)
+{
+	if (threadIdx.x == 0) *s_first = 0x7fffffff;
+	__syncthreads();
+	for (int b = threadIdx.x; b < B; b += BLOCK)
+		if (flagged(flags[b])) { atomicMin(s_first, b); break; }      // ascending per thread: its first is its lowest
+	__syncthreads();
+	return *s_first;
+}
+
+// Accept test of a wave of the lane kernels (lane = spectrum `lane` of tile `tile`, all lanes on candidate `cand`):
+// when some lane beats its threshold (thr NaN: a lane past the selection, never) and cand < B, the candidate is flagged
+// and the trail keeps the ballot word and the 64 likelihoods.  Returns the word.
+__device__ __forceinline__ unsigned long long trail_vote(const JointTrail &trail, int *__restrict__ flags, int cand, int B,
+                                                         int ntiles, int tile, int lane, double L, double thr)
+{
+	const unsigned long long word = __ballot(L > thr);
+	if (word != 0ull && cand < B) {                                    // rare: a candidate some data set accepts
+		const size_t at = (size_t) cand * ntiles + tile;
+		if (trail.stamp_of) trail.L[at * 64 + lane] = L;
+		if (lane == 0) {
+			flags[cand] = 1;
+			if (trail.stamp_of) { trail.word[at] = word; trail.stamp_of[at] = trail.stamp; }
+		}
+	}
+	return word;
+}
 #endif
 
 

@@ -277,12 +277,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_dense(
     JointArrays st, JointHeader *__restrict__ header, unsigned long long *__restrict__ fillbits)
 {
 	__shared__ int s_first;
-	if (threadIdx.x == 0) s_first = 0x7fffffff;
-	__syncthreads();
-	for (int b = threadIdx.x; b < B; b += kBlock)
-		if (flags[b] == flag) { atomicMin(&s_first, b); break; }
-	__syncthreads();
-	const int bstar = s_first;
+	const int bstar = first_flagged<kBlock>(&s_first, flags, B, [=](int f) { return f == flag; });
 	if (blockIdx.x == 0 && threadIdx.x == 0) header->accepted = bstar < B ? bstar : -1;
 	if (bstar >= B) return;
 	const int lane = threadIdx.x & 63;
@@ -295,25 +290,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_dense(
 		const double v = L[(size_t) bstar * M + k];
 		const double thr = st.higher[d];
 		beats = v > thr;
-		if (beats) {
-			const int n = st.shelfn[d];
-			if (n >= st.cap) atomicOr(&header->status, 1);
-			else {
-				int at_most = 0;
-				double next = INFINITY;
-				for (int p = 0; p < st.nlive; p++) {
-					const double w = st.live[(size_t) p * st.ndata + d];
-					if (w <= thr) at_most++; else next = fmin(next, w);
-				}
-				for (int e = 0; e < n; e++) {
-					const double w = st.shelfL[(size_t) e * st.ndata + d];
-					if (w <= thr) at_most++; else next = fmin(next, w);
-				}
-				st.shelfL[(size_t) n * st.ndata + d] = v;
-				st.shelfn[d] = n + 1;
-				st.higher[d] = at_most >= n + 2 ? thr : fmin(v, next);
-			}
-		}
+		if (beats && !shelf_append<1>(st, d, v, thr)) atomicOr(&header->status, 1);
 	}
 	const unsigned long long word = __ballot(beats);
 	if (lane == 0) fillbits[tile] = word;
@@ -371,33 +348,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_band(
 		const double v = L[(size_t) bstar * M + k] + jrow[k];
 		const double thr = st.higher[d];
 		beats = v > thr;
-		if (beats) {
-			const int n = st.shelfn[d];
-			if (n >= st.cap) atomicOr(&header->status, 1);
-			else {
-				int at_most = 0;
-				double next = INFINITY;
-				int p = 0;
-				for (; p + 20 <= st.nlive; p += 20) {                   // 20 loads in flight (as in k_joint_commit_trail: the latency of a round trip is what this costs)
-					double w[20];
-#pragma unroll
-					for (int u = 0; u < 20; u++) w[u] = st.live[(size_t) (p + u) * st.ndata + d];
-#pragma unroll
-					for (int u = 0; u < 20; u++) { if (w[u] <= thr) at_most++; else next = fmin(next, w[u]); }
-				}
-				for (; p < st.nlive; p++) {
-					const double w = st.live[(size_t) p * st.ndata + d];
-					if (w <= thr) at_most++; else next = fmin(next, w);
-				}
-				for (int e = 0; e < n; e++) {
-					const double w = st.shelfL[(size_t) e * st.ndata + d];
-					if (w <= thr) at_most++; else next = fmin(next, w);
-				}
-				st.shelfL[(size_t) n * st.ndata + d] = v;
-				st.shelfn[d] = n + 1;
-				st.higher[d] = at_most >= n + 2 ? thr : fmin(v, next);
-			}
-		}
+		if (beats && !shelf_append<20>(st, d, v, thr)) atomicOr(&header->status, 1);
 	}
 	const unsigned long long word = __ballot(beats);
 	if (lane == 0) fillbits[tile] = word;

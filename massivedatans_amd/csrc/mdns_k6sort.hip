@@ -279,14 +279,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_nearest_culled(
 	mail_raise(&fin.h_res->seq, fin.seq);
 }
 
-static bool launched(const char *name)
-{
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) return true;
-	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
-	return false;
-}
-
 // whether the sorted form applies (pools of 1 024 .. 16 384 points in at most 5 dimensions, 10 or 16 rounds)
 bool bootstrap_sorted_applies(int K, int ndim, int nbootstraps)
 {

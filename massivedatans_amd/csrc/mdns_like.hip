@@ -635,18 +635,8 @@ __global__ __launch_bounds__(2 * kBlock) void k_gauss_cols_accept(
 	// a quiet NaN compares false with everything: lanes past the selection never vote
 	const double thr = live ? higher[thr_rows ? thr_rows[kk] : kk] : __builtin_nan("");
 #pragma unroll
-	for (int b = 0; b < BT; b++) {
-		const double L = acc[0][b] * scale;
-		const unsigned long long word = __ballot(L > thr);
-		if (word != 0ull && bt * BT + b < B) {                         // rare: a candidate some data set accepts
-			const size_t at = (size_t) (bt * BT + b) * ntiles + tile;
-			if (trail.stamp_of) trail.L[at * 64 + lane] = L;
-			if (lane == 0) {
-				flags[bt * BT + b] = 1;
-				if (trail.stamp_of) { trail.word[at] = word; trail.stamp_of[at] = trail.stamp; }
-			}
-		}
-	}
+	for (int b = 0; b < BT; b++)
+		trail_vote(trail, flags, bt * BT + b, B, ntiles, tile, lane, acc[0][b] * scale, thr);
 }
 
 // The accept test as a GUARDED FILTER, for launches that are bound by vector issue (hundreds of
@@ -712,17 +702,8 @@ __global__ __launch_bounds__(2 * kBlock) void k_gauss_cols_filter(
 		int k1[1];
 		double a1[1][1];
 		cols_accumulate<1, 1, true>(YT, nxp, mp + b, BT, rows, M, tile, lane, k1, a1);
-		const double L = a1[0][0] * scale;
-		const unsigned long long word = __ballot(L > thr);
-		if (word != 0ull) {
-			const size_t at = (size_t) cand * ntiles + tile;
-			if (trail.stamp_of) trail.L[at * 64 + lane] = L;
-			if (lane == 0) {
-				flags[cand] = 1;
-				atomicMax(lowest, B - cand);
-				if (trail.stamp_of) { trail.word[at] = word; trail.stamp_of[at] = trail.stamp; }
-			}
-		}
+		const unsigned long long word = trail_vote(trail, flags, cand, B, ntiles, tile, lane, a1[0][0] * scale, thr);
+		if (word != 0ull && lane == 0) atomicMax(lowest, B - cand);
 	}
 }
 
@@ -749,12 +730,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_trail(
 {
 	__shared__ int s_first;
 	__shared__ int s_last;
-	if (threadIdx.x == 0) s_first = 0x7fffffff;
-	__syncthreads();
-	for (int b = threadIdx.x; b < B; b += kBlock)
-		if (flags[b] == flag_value) { atomicMin(&s_first, b); break; }      // ascending per thread: its first is its lowest
-	__syncthreads();
-	const int bstar = s_first;
+	const int bstar = first_flagged<kBlock>(&s_first, flags, B, [=](int f) { return f == flag_value; });
 	if (blockIdx.x == 0 && threadIdx.x == 0) header->accepted = bstar < B ? bstar : -1;
 	const int lane = threadIdx.x & 63;
 	const int tile = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -766,37 +742,7 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_trail(
 	const int k = tile * 64 + lane;
 	if (mine && k < M && (word >> lane & 1ull)) {
 		const int d = thr_rows ? thr_rows[k] : k;
-		const double L = trail.L[at * 64 + lane];
-		const double thr = st.higher[d];
-		const int n = st.shelfn[d];
-		if (n >= st.cap) {
-			atomicOr(&header->status, 1);
-		} else {
-			// With n waiting the threshold was the (n+1)-th smallest of live + shelf, and L lies
-			// above it: the (n+2)-th smallest of the enlarged set is the old threshold again when
-			// it occurs more than once, else the smaller of L and the next value above it.
-			int at_most = 0;
-			double next = INFINITY;
-			int p = 0;
-			for (; p + 25 <= st.nlive; p += 25) {                    // 25 loads in flight (the latency of a round trip, not the count, is what this pass costs)
-				double v[25];
-#pragma unroll
-				for (int u = 0; u < 25; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
-#pragma unroll
-				for (int u = 0; u < 25; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
-			}
-			for (; p < st.nlive; p++) {
-				const double v = st.live[(size_t) p * st.ndata + d];
-				if (v <= thr) at_most++; else next = fmin(next, v);
-			}
-			for (int e = 0; e < n; e++) {
-				const double v = st.shelfL[(size_t) e * st.ndata + d];
-				if (v <= thr) at_most++; else next = fmin(next, v);
-			}
-			st.shelfL[(size_t) n * st.ndata + d] = L;
-			st.shelfn[d] = n + 1;
-			st.higher[d] = at_most >= n + 2 ? thr : fmin(L, next);
-		}
+		if (!shelf_append<25>(st, d, trail.L[at * 64 + lane], st.higher[d])) atomicOr(&header->status, 1);
 	}
 	if (!box) { if (lane == 0) fillbits[tile] = word; return; }
 	// box != nullptr: the mailbox is filled by the last workgroup to finish (hand-over of mdns_internal.h: the fill
@@ -839,13 +785,7 @@ __global__ __launch_bounds__(kBlock) void k_gauss_cols_commit(
 	// all LDS in the dynamic region (a static variable in front of it would leave the template
 	// column 4 bytes off its 8-byte alignment): [nxp] template doubles, then one int
 	extern __shared__ __attribute__((aligned(16))) double tpl[];
-	int &s_first = *reinterpret_cast<int *>(tpl + nxp);
-	if (threadIdx.x == 0) s_first = 0x7fffffff;
-	__syncthreads();
-	for (int b = threadIdx.x; b < B; b += kBlock)
-		if (flags[b]) { atomicMin(&s_first, b); break; }      // ascending per thread: its first is its lowest
-	__syncthreads();
-	const int bstar = s_first;
+	const int bstar = first_flagged<kBlock>(reinterpret_cast<int *>(tpl + nxp), flags, B, [](int f) { return f != 0; });
 	if (blockIdx.x == 0 && threadIdx.x == 0) header->accepted = bstar < B ? bstar : -1;
 	if (bstar >= B) return;
 	const int lane = threadIdx.x & 63;
@@ -866,37 +806,7 @@ __global__ __launch_bounds__(kBlock) void k_gauss_cols_commit(
 		Lrow[k[0]] = L;
 		const double thr = st.higher[d];
 		beats = L > thr;
-		if (beats) {
-			const int n = st.shelfn[d];
-			if (n >= st.cap) {
-				atomicOr(&header->status, 1);
-			} else {
-				// With n waiting the threshold was the (n+1)-th smallest of live + shelf, and L lies
-				// above it: the (n+2)-th smallest of the enlarged set is the old threshold again when
-				// it occurs more than once, else the smaller of L and the next value above it.
-				int at_most = 0;
-				double next = INFINITY;
-				int p = 0;
-				for (; p + 8 <= st.nlive; p += 8) {                  // eight loads in flight
-					double v[8];
-#pragma unroll
-					for (int u = 0; u < 8; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
-#pragma unroll
-					for (int u = 0; u < 8; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
-				}
-				for (; p < st.nlive; p++) {
-					const double v = st.live[(size_t) p * st.ndata + d];
-					if (v <= thr) at_most++; else next = fmin(next, v);
-				}
-				for (int e = 0; e < n; e++) {
-					const double v = st.shelfL[(size_t) e * st.ndata + d];
-					if (v <= thr) at_most++; else next = fmin(next, v);
-				}
-				st.shelfL[(size_t) n * st.ndata + d] = L;
-				st.shelfn[d] = n + 1;
-				st.higher[d] = at_most >= n + 2 ? thr : fmin(L, next);
-			}
-		}
+		if (beats && !shelf_append<8>(st, d, L, thr)) atomicOr(&header->status, 1);
 	}
 	const unsigned long long word = __ballot(beats);
 	if (lane == 0) fillbits[tile] = word;
@@ -1169,14 +1079,6 @@ __global__ __launch_bounds__(kBlock) void k_muse_rows_generic(
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static bool launched(const char *name)
-{
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) return true;
-	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
-	return false;
-}
-
 bool launch_gauss_model(const double *d_x, int nx, const double *d_params, int B, double *d_model, int ldm)
 {
 	Context *c = ctx();

@@ -581,14 +581,6 @@ __global__ __launch_bounds__(kBlock) void k_nearest_finish(
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static bool launched(const char *name)
-{
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) return true;
-	set_error("launch of %s failed: %s", name, hipGetErrorString(e));
-	return false;
-}
-
 // members per LDS tile: a multiple of 16, as many as fit beside `fixed_bytes`
 static int pick_tile(int ndim, size_t per_member_extra, size_t fixed_bytes)
 {
