@@ -24,6 +24,7 @@
 // ulp more often).  The sum of a (candidate, spectrum) pair is the chain
 // of every other K1 form: channels ascending, d = m - y, acc = fma(d, d, acc).
 #include "mdns_quad.h"
+#include "mdns_geom.h"
 #include "mdns_pow10.h"
 
 #pragma clang fp contract(off)
@@ -73,36 +74,15 @@ __global__ __launch_bounds__(256) void k_box_count(
 		for (int e = threadIdx.x; e < n * D; e += 256) tile[e] = members[(size_t) t0 * D + e];
 		__syncthreads();
 #pragma unroll 4
-		for (int i = slice; i < n; i += NSLICE) {
-			double acc = 0.0;
-#pragma unroll
-			for (int k = 0; k < D; k++) {
-				const double diff = tile[i * D + k] - c[k];
-				acc = acc + diff * diff;
-			}
-			hits += acc < thresh_sq ? 1 : 0;
-		}
+		for (int i = slice; i < n; i += NSLICE)
+			hits += sq_distance_fixed<D>(tile + i * D, c) < thresh_sq ? 1 : 0;
 	}
-#pragma unroll
-	for (int off = PTS; off < 64; off <<= 1) hits += __shfl_xor(hits, off, 64);
-	if (lane < PTS) part[wv * PTS + pt] = hits;
-	__syncthreads();
+	const int total = slice_total<PTS>(hits, part);
 	if (wv == 0 && lane < PTS && j < spec.n) {
-		const int total = (part[pt] + part[PTS + pt]) + (part[2 * PTS + pt] + part[3 * PTS + pt]);
 		counts[j] = total;
 		__hip_atomic_store(&box->counts[j], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 	}
-	if (mail.seq_at) {
-		if (wv == 0) handover_release();                           // (mdns_internal.h)
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			const int done = atomicAdd(mail.ticket, 1);
-			if (done == (int) gridDim.x - 1) {
-				__hip_atomic_store(mail.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				mail_raise(mail.seq_at, mail.seq);
-			}
-		}
-	}
+	count_mail_raise(mail, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -216,8 +196,7 @@ bool launch_box_count(const RegionView &rv, const ChainSpec &spec, ChainBox *box
 	note_kernel(2, "k_box_count<%d>", rv.ndim);
 #define BOX_LAUNCH(D) hipLaunchKernelGGL((k_box_count<D>), grid, dim3(256), lds, c->stream, rv.d_members, rv.K, rv.d_res, spec, \
 	box_dev, d_props, d_counts, tile_n, post)
-	switch (rv.ndim) { case 1: BOX_LAUNCH(1); break; case 2: BOX_LAUNCH(2); break; case 3: BOX_LAUNCH(3); break;
-	                   case 4: BOX_LAUNCH(4); break; default: BOX_LAUNCH(5); break; }
+	MDNS_DIM5_SWITCH(rv.ndim, BOX_LAUNCH)
 #undef BOX_LAUNCH
 	return launched("k_box_count");
 }

@@ -986,6 +986,20 @@ Wait mdns::wait_seq(const volatile unsigned long long *at, unsigned long long wa
 	return Wait::ok;
 }
 
+// A radius computation on r's members into r's result slot: `launch` is launch_bootstrap (choice matrix) or
+// launch_bootstrap_packed (bit masks).  Once it is in the stream the membership kernel takes its threshold from
+// d_res, and the host copies are to be fetched under the new `seq`.
+template <class Choice>
+static bool region_launch_radius(mdns_region *r, bool (*launch)(const double *, int, int, const Choice *, int, double *, const BootstrapFinish *),
+                                 const Choice *d_choice, int nbootstraps)
+{
+	const BootstrapFinish fin = {r->d_counter, r->d_res, r->h_res_dev, ++r->seq};
+	if (!launch(r->d_members, r->K, r->ndim, d_choice, nbootstraps, r->d_round, &fin)) return false;
+	r->on_device = true;
+	r->pending = true;
+	return true;
+}
+
 static mdns_region *region_new(const double *d_members, double *owned, int K, int ndim)
 {
 	mdns_region *r = new mdns_region();
@@ -1047,14 +1061,11 @@ static mdns_region *create_bootstrapped(const double *members, int K, int ndim, 
 	mdns_region *r = region_new((const double *) d, (double *) d, K, ndim);
 	if (!r) { (void) hipStreamSynchronize(c->stream); pool_give(d, got); return nullptr; }
 	r->owned_bytes = got;
-	const BootstrapFinish fin = {r->d_counter, r->d_res, r->h_res_dev, ++r->seq};
-	if (!launch_bootstrap_packed(r->d_members, K, ndim, (const unsigned *) (d + poff), nbootstraps, r->d_round, &fin)) {
+	if (!region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) (d + poff), nbootstraps)) {
 		(void) hipStreamSynchronize(c->stream);
 		mdns_region_destroy(r);
 		return nullptr;
 	}
-	r->on_device = true;
-	r->pending = true;
 	if (!wait) return r;
 	*radius = mdns_region_radius(r);          // waits: the pinned staging block is free again
 	if (*radius != *radius) { mdns_region_destroy(r); return nullptr; }
@@ -1151,11 +1162,7 @@ extern "C" int mdns_region_bootstrap_radius_async(mdns_region *r, const double *
 		if (!MDNS_HIP(hipMemsetAsync(r->d_round, 0, (size_t) nbootstraps * sizeof(double), c->stream))) return 1;
 		r->round_cap = nbootstraps;
 	}
-	const BootstrapFinish fin = {r->d_counter, r->d_res, r->h_res_dev, ++r->seq};
-	if (!launch_bootstrap(r->d_members, r->K, r->ndim, d_chosen, nbootstraps, r->d_round, &fin)) return 1;
-	r->on_device = true;
-	r->pending = true;
-	return 0;
+	return region_launch_radius(r, launch_bootstrap, d_chosen, nbootstraps) ? 0 : 1;
 }
 
 extern "C" double mdns_region_bootstrap_radius_dev(mdns_region *r, const double *d_chosen, int nbootstraps)
@@ -1184,10 +1191,7 @@ extern "C" double mdns_region_bootstrap_radius_packed(mdns_region *r, const unsi
 	const size_t bytes = (size_t) r->K * sizeof(unsigned);
 	if (!pool_fit(&r->d_chosen, &r->chosen_bytes, bytes)) return NAN;
 	if (!MDNS_HIP(hipMemcpyAsync(r->d_chosen, packed, bytes, hipMemcpyHostToDevice, c->stream))) return NAN;
-	const BootstrapFinish fin = {r->d_counter, r->d_res, r->h_res_dev, ++r->seq};
-	if (!launch_bootstrap_packed(r->d_members, r->K, r->ndim, (const unsigned *) r->d_chosen, nbootstraps, r->d_round, &fin)) return NAN;
-	r->on_device = true;
-	r->pending = true;
+	if (!region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) r->d_chosen, nbootstraps)) return NAN;
 	return mdns_region_radius(r);
 }
 

@@ -25,8 +25,7 @@
 // test_hip_parity.py k6 golden / sweep / quirk cases run both paths).  The reference's quirk that the
 // point with index 0 never contributes to a round's maximum (cneighbors.c:162) travels with the point as
 // a flag bit through the sort.
-#include "mdns_internal.h"
-#include "mdns_radius.h"
+#include "mdns_geom.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -39,19 +38,6 @@ static constexpr int kMostSorted = 16384;                 // points at most (128
 static constexpr int kTile = 64;
 static constexpr int kWaves = 8;                          // waves per group of 64 points
 static constexpr unsigned kFirstPointBit = 1u << 31;      // the pool's point 0 (cneighbors.c:162)
-
-__device__ __forceinline__ double wave_min_d(double v)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-	return v;
-}
-__device__ __forceinline__ double wave_max_d(double v)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-	return v;
-}
 
 template <int D>
 __global__ __launch_bounds__(kSortThreads) void k_morton_sort(
@@ -72,7 +58,7 @@ __global__ __launch_bounds__(kSortThreads) void k_morton_sort(
 	}
 #pragma unroll
 	for (int k = 0; k < D; k++) {
-		const double a = wave_min_d(mn[k]), b = wave_max_d(mx[k]);
+		const double a = wave_min(mn[k]), b = wave_max(mx[k]);
 		if (lane == 0) { red[k][wave] = a; red[D + k][wave] = b; }
 	}
 	__syncthreads();
@@ -136,17 +122,10 @@ __global__ __launch_bounds__(kSortThreads) void k_morton_sort(
 #pragma unroll
 		for (int k = 0; k < D; k++) {
 			const double v = members[(size_t) i * D + k];
-			const double a = wave_min_d(live ? v : 1e300), b = wave_max_d(live ? v : -1e300);
+			const double a = wave_min(live ? v : 1e300), b = wave_max(live ? v : -1e300);
 			if (lane == 0) { boxes[(size_t) t * 2 * D + k] = a; boxes[(size_t) t * 2 * D + D + k] = b; }
 		}
 	}
-}
-
-__device__ __forceinline__ double min_skip(double a, double b)
-{
-	double r;
-	asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-	return r;
 }
 
 // the wave's LDS writes before its LDS reads (no workgroup barrier inside the divergent tile loop)
@@ -183,7 +162,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_nearest_culled(
 	double glo[D], ghi[D];
 #pragma unroll
 	for (int k = 0; k < D; k++) { glo[k] = boxes[(size_t) t0 * 2 * D + k]; ghi[k] = boxes[(size_t) t0 * 2 * D + D + k]; }
-	const double PINF = __longlong_as_double(0x7ff0000000000000LL), NINF = __longlong_as_double((long long) 0xfff0000000000000ULL);
 	double *tile = tiles[wv];
 	unsigned *tmask = tmasks[wv];
 	auto process = [&](int t) {
@@ -197,27 +175,15 @@ __global__ __launch_bounds__(kWaves * 64) void k_nearest_culled(
 		}
 		MDNS_WAVE_LDS_SYNC();
 		for (int jn = 0; jn < n; jn++) {
-			double d = 0.0;
-#pragma unroll
-			for (int k = 0; k < D; k++) {
-				const double diff = tile[jn * D + k] - c[k];
-				d = d + diff * diff;
-			}
-			const unsigned m = (unsigned) __builtin_amdgcn_readfirstlane((int) tmask[jn]);
-#pragma unroll
-			for (int b = 0; b < RT; b++) {
-				const double S = (m >> b & 1u) ? NINF : PINF;         // scalar: s_bitcmp1 + s_cselect_b64
-				double tt;
-				asm("v_max_f64 %0, %1, %2" : "=v"(tt) : "v"(d), "s"(S));
-				nearest[b] = min_skip(nearest[b], tt);
-			}
+			const double d = sq_distance_fixed<D>(tile + jn * D, c);
+			offer_rounds<RT>(nearest, d, (unsigned) __builtin_amdgcn_readfirstlane((int) tmask[jn]));
 		}
 	};
 	auto worst_of_wave = [&]() {
 		double w = 0.0;
 #pragma unroll
 		for (int b = 0; b < RT; b++) w = fmax(w, counts[b] ? nearest[b] : 0.0);
-		return wave_max_d(w);
+		return wave_max(w);
 	};
 	// every wave meets the own tile first, then the waves share the others, nearer ones first
 	process(t0);
@@ -250,33 +216,10 @@ __global__ __launch_bounds__(kWaves * 64) void k_nearest_culled(
 #pragma unroll
 		for (int w = 1; w < kWaves; w++) v = fmin(v, meet[w][b][lane]);
 		const bool contributes = live && !((mymask >> b) & 1u) && !(mymask & kFirstPointBit);
-		v = wave_max_d(contributes ? v : 0.0);
-		if (lane == 0 && v > 0.0)
-			atomicMax(reinterpret_cast<unsigned long long *>(round_sq + b), (unsigned long long) __double_as_longlong(v));
+		v = wave_max(contributes ? v : 0.0);
+		if (lane == 0 && v > 0.0) atomic_max_nonneg(round_sq + b, v);
 	}
-	if (!fin.counter) return;
-	// the workgroup that finishes last turns the maxima into {radius, threshold} (as k_nearest_chosen)
-	handover_release();
-	__syncthreads();
-	if (wv != 0) return;
-	unsigned ticket = 0;
-	if (lane == 0) ticket = atomicAdd(fin.counter, 1u);
-	if (__shfl(ticket, 0, 64) != gridDim.x - 1) return;
-	handover_acquire();
-	double best = 0.0;
-	for (int b = lane; b < nround_all; b += 64)
-		best = fmax(best, __hip_atomic_load(round_sq + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-	best = wave_max_d(best);
-	for (int b = lane; b < nround_all; b += 64) round_sq[b] = 0.0;
-	if (lane != 0) return;
-	double radius, thresh;
-	radius_and_threshold(best, radius, thresh);
-	fin.d_res->radius = radius;
-	fin.d_res->thresh = thresh;
-	*fin.counter = 0;
-	mail_store(&fin.h_res->radius, radius);
-	mail_store(&fin.h_res->thresh, thresh);
-	mail_raise(&fin.h_res->seq, fin.seq);
+	finish_radius(fin, round_sq, nround_all);
 }
 
 // whether the sorted form applies (pools of 1 024 .. 16 384 points in at most 5 dimensions, 10 or 16 rounds)
@@ -320,8 +263,7 @@ bool launch_bootstrap_sorted(const double *d_members, int K, int ndim, const uns
 	if (rt == 10) hipLaunchKernelGGL((k_nearest_culled<D, 10>), dim3(ntiles), dim3(kWaves * 64), 0, c->stream, (const double *) sm, (const unsigned *) sk, (const double *) boxes, K, nbootstraps, d_round_sq, *finish, nbootstraps); \
 	else hipLaunchKernelGGL((k_nearest_culled<D, 16>), dim3(ntiles), dim3(kWaves * 64), 0, c->stream, (const double *) sm, (const unsigned *) sk, (const double *) boxes, K, nbootstraps, d_round_sq, *finish, nbootstraps); \
 	} while (0)
-	switch (ndim) { case 1: SORT_LAUNCH(1); break; case 2: SORT_LAUNCH(2); break; case 3: SORT_LAUNCH(3); break;
-	                case 4: SORT_LAUNCH(4); break; default: SORT_LAUNCH(5); break; }
+	MDNS_DIM5_SWITCH(ndim, SORT_LAUNCH)
 #undef SORT_LAUNCH
 	return launched("k_nearest_culled");
 }

@@ -12,8 +12,7 @@
 // of the bootstrap kernel's last workgroup (radius_and_threshold); the inner loops need no sqrt.  For the
 // radii (cneighbors.c:64-71,160-174) the root is taken once after the max of the min squared
 // distances -- the same number because sqrt is monotone.
-#include "mdns_internal.h"
-#include "mdns_radius.h"
+#include "mdns_geom.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -23,7 +22,6 @@ namespace mdns {
 
 static constexpr int kBlock = 256;          // 4 waves
 static constexpr int kMaxTile = 512;        // members per LDS tile (fewer when ndim is large)
-static constexpr int kMaxRegDim = 8;        // dimensions kept in registers
 static constexpr int kRounds = 16;          // bootstrap rounds per pass (cneighbors uses 10)
 static constexpr size_t kLdsBudget = 60 * 1024;
 
@@ -36,28 +34,6 @@ template <int SL> struct Geo {
 	static constexpr int PTS = 64 / SL;
 	static constexpr int NSLICE = 4 * SL;
 };
-
-__device__ __forceinline__ double sq_distance(const double *a, const double *b, int ndim)
-{
-	double acc = 0.0;
-	for (int k = 0; k < ndim; k++) {
-		const double diff = a[k] - b[k];
-		acc = acc + diff * diff;
-	}
-	return acc;
-}
-
-template <int D>
-__device__ __forceinline__ double sq_distance_fixed(const double *a, const double (&c)[D])
-{
-	double acc = 0.0;
-#pragma unroll
-	for (int k = 0; k < D; k++) {
-		const double diff = a[k] - c[k];
-		acc = acc + diff * diff;
-	}
-	return acc;
-}
 
 // Copies `count` words from global memory into LDS with all of a thread's loads in flight at
 // once (a plain strided copy loop is compiled to load -> wait -> store per trip, i.e. one full
@@ -131,59 +107,19 @@ __global__ __launch_bounds__(kBlock) void k_count_within(
 				hits += sq_distance(tile + i * ndim, cj, ndim) < thresh_sq ? 1 : 0;
 		}
 	}
-	// sum over the slices of this wave (lanes pt, pt + PTS, ...), then over the waves
-#pragma unroll
-	for (int off = PTS; off < 64; off <<= 1) hits += __shfl_xor(hits, off, 64);
-	if (lane < PTS) part[wv * PTS + pt] = hits;
-	__syncthreads();
+	const int total = slice_total<PTS>(hits, part);
 	if (wv == 0 && lane < PTS && j < M) {
-		const int total = (part[pt] + part[PTS + pt]) + (part[2 * PTS + pt] + part[3 * PTS + pt]);
 		if (accumulate) { if (total) atomicAdd(counts + j, total); }
 		else if (mail.seq_at) __hip_atomic_store(counts + j, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 		else counts[j] = total;
 	}
-	if (mail.seq_at) {
-		// `counts` is host memory mapped into the device (no member split; system-scope stores): once every
-		// workgroup's stores are out -- waited for, not fenced: see handover_release -- the last one to get here
-		// raises `seq` for the polling host
-		if (wv == 0) handover_release();                           // (only wave 0 stored)
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			const int done = atomicAdd(mail.ticket, 1);
-			if (done == (int) (gridDim.x * gridDim.y) - 1) {
-				__hip_atomic_store(mail.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next launch (stream order)
-				mail_raise(mail.seq_at, mail.seq);
-			}
-		}
-	}
+	// with a mailbox `counts` is host memory mapped into the device (no member split; system-scope stores)
+	count_mail_raise(mail, gridDim.x * gridDim.y);
 }
 
 // ---------------------------------------------------------------------------------------
 // K5 / K6: nearest "chosen" pool point of every "left-out" pool point, max over the left-out
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-	return v;
-}
-
-// min(a, b) where b may be a QUIET NaN meaning "not a candidate": v_min_f64 returns the other
-// operand for a quiet NaN.  Written as asm so that the compiler does not put a canonicalising
-// v_max_f64 in front of every use (it cannot know the operand is already quiet).
-__device__ __forceinline__ double min_or_skip(double a, double b)
-{
-	double r;
-	asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-	return r;
-}
-
-// non-negative doubles order like their bit patterns
-__device__ __forceinline__ void atomic_max_nonneg(double *addr, double v)
-{
-	atomicMax(reinterpret_cast<unsigned long long *>(addr), (unsigned long long) __double_as_longlong(v));
-}
-
 // chosen f64[K][nboot] (cneighbors.c:146 tests != 0) -> one bit per round of the window
 // [b0, b0+nb) for every pool point; also clears the window's slots of round_sq, which
 // k_nearest_chosen then raises with atomic max
@@ -330,31 +266,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest_chosen(
 		v = wave_max(v);
 		if (lane == 0 && v > 0.0) atomic_max_nonneg(round_sq + b, v);
 	}
-	if (!fin.counter) return;
-	// The workgroup that finishes last turns the maxima into {radius, threshold} for the
-	// membership kernel (device copy) and for the host (mapped memory, `seq` written last).
-	handover_release();                                   // this workgroup's atomics before its ticket
-	__syncthreads();
-	if (wv != 0) return;
-	unsigned ticket = 0;
-	if (lane == 0) ticket = atomicAdd(fin.counter, 1u);
-	if (__shfl(ticket, 0, 64) != gridDim.x - 1) return;
-	handover_acquire();
-	double best = 0.0;
-	for (int b = lane; b < nround_all; b += 64)
-		best = fmax(best, __hip_atomic_load(round_all + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-	best = wave_max(best);
-	// the slots go back to zero for the next computation (nobody else reads them any more)
-	for (int b = lane; b < nround_all; b += 64) round_all[b] = 0.0;
-	if (lane != 0) return;
-	double radius, thresh;
-	radius_and_threshold(best, radius, thresh);
-	fin.d_res->radius = radius;
-	fin.d_res->thresh = thresh;
-	*fin.counter = 0;
-	mail_store(&fin.h_res->radius, radius);
-	mail_store(&fin.h_res->thresh, thresh);
-	mail_raise(&fin.h_res->seq, fin.seq);
+	finish_radius(fin, round_all, nround_all);
 }
 
 // K6 again, for packed choices (the shape every region of a run has): the member a wave looks at
@@ -389,7 +301,6 @@ __global__ __launch_bounds__(kBlock) void k_nearest_uniform(
 #pragma unroll
 	for (int b = 0; b < RT; b++) nearest[b] = 1e300;                      // cneighbors.c:148
 	const int kbeg = blockIdx.y * kchunk, kend = min(K, kbeg + kchunk);
-	const double PINF = __longlong_as_double(0x7ff0000000000000LL), NINF = __longlong_as_double((long long) 0xfff0000000000000ULL);
 	for (int t0 = kbeg; t0 < kend; t0 += tile_n) {
 		const int n = min(tile_n, kend - t0);
 		__syncthreads();
@@ -398,22 +309,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest_uniform(
 		__syncthreads();
 		auto offer = [&](int jn) {
 			const double d = sq_distance_fixed<D>(tile + jn * D, c);
-			const unsigned m = (unsigned) __builtin_amdgcn_readfirstlane((int) tmask[jn]);
-			// (tried: `if (m >> b & 1u) nearest[b] = min(nearest[b], d)` -- a scalar branch around ONE
-			// v_min_f64, 14 vector instructions per step instead of 28: 47.7 / 124 / 409 / 2198 us at
-			// 5 000 / 9 000 / 20 000 / 50 000 points against 51 / 111 / 400 / 2130 -- the ten
-			// s_bitcmp1 + s_cbranch pairs per step cost what the skipped instructions save)
-#pragma unroll
-			for (int b = 0; b < RT; b++) {
-				const double S = (m >> b & 1u) ? NINF : PINF;             // scalar: s_bitcmp1 + s_cselect_b64
-				// (written as asm: left to itself the compiler turns max(d, +-inf) into two
-				// v_cndmask_b32 per round -- three vector instructions instead of two; so does the
-				// quiet-NaN form d.hi | 0x7ff80000 of the classic kernel with a scalar mask: it needs a
-				// copy of d.lo per round to form the register pair)
-				double t;
-				asm("v_max_f64 %0, %1, %2" : "=v"(t) : "v"(d), "s"(S));
-				nearest[b] = min_or_skip(nearest[b], t);
-			}
+			offer_rounds<RT>(nearest, d, (unsigned) __builtin_amdgcn_readfirstlane((int) tmask[jn]));
 		};
 		int jn = wv;
 		for (; jn + 4 < n; jn += 8) { offer(jn); offer(jn + 4); }
@@ -433,8 +329,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest_uniform(
 	}
 	if (!block_tickets) return;                        // (the merge is a kernel of its own: k_nearest_finish)
 	// Round 4: the merge rides in this kernel.  Of the gridDim.y workgroups that share these 64 points the
-	// one that arrives LAST takes the min over the member chunks and the max over the left-out points
-	// (cneighbors.c:160-168); of those, the last one finishes the radius (k_nearest_chosen's epilogue).
+	// one that arrives LAST merges their chunks (merge_chunks); of those, the last one finishes the radius.
 	__shared__ int s_last;
 	__shared__ double wmax[4][RT];
 	handover_release();
@@ -447,135 +342,20 @@ __global__ __launch_bounds__(kBlock) void k_nearest_uniform(
 	__syncthreads();
 	if (!s_last) return;
 	handover_acquire();
-	{
-		const int ny = (int) gridDim.y;
-		const int i2 = blockIdx.x * 64 + ((int) threadIdx.x >> 2), yq = threadIdx.x & 3;
-		double v[RT];
-#pragma unroll
-		for (int b = 0; b < RT; b++) v[b] = 0.0;
-		const bool counts = i2 < K && i2 >= 1;
-		if (counts) {
-#pragma unroll
-			for (int b = 0; b < RT; b++) v[b] = 1e300;
-			for (int y = yq; y < ny; y += 4) {
-				const double *row = part + ((size_t) y * K + i2) * RT;
-#pragma unroll
-				for (int b = 0; b < RT; b++) v[b] = fmin(v[b], __hip_atomic_load(row + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-			}
-		}
-#pragma unroll
-		for (int b = 0; b < RT; b++) {
-			v[b] = fmin(v[b], __shfl_xor(v[b], 1, 64));
-			v[b] = fmin(v[b], __shfl_xor(v[b], 2, 64));
-		}
-		if (counts) {
-			const unsigned m = mask[i2];
-#pragma unroll
-			for (int b = 0; b < RT; b++) if (b >= nb || (m >> b & 1u)) v[b] = 0.0;
-		}
-#pragma unroll
-		for (int b = 0; b < RT; b++) {
-			const double w = wave_max(v[b]);
-			if (lane == 0) wmax[wv][b] = w;
-		}
-		__syncthreads();
-		if ((int) threadIdx.x < RT && (int) threadIdx.x < nb) {
-			const double w = fmax(fmax(wmax[0][threadIdx.x], wmax[1][threadIdx.x]), fmax(wmax[2][threadIdx.x], wmax[3][threadIdx.x]));
-			if (w > 0.0) atomic_max_nonneg(round_sq + threadIdx.x, w);
-		}
-	}
-	if (!fin.counter) return;
-	handover_release();
-	__syncthreads();
-	if (wv != 0) return;
-	unsigned ticket = 0;
-	if (lane == 0) ticket = atomicAdd(fin.counter, 1u);
-	if (__shfl(ticket, 0, 64) != gridDim.x - 1) return;
-	handover_acquire();
-	double best = 0.0;
-	for (int b = lane; b < nround_all; b += 64)
-		best = fmax(best, __hip_atomic_load(round_sq + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-	best = wave_max(best);
-	for (int b = lane; b < nround_all; b += 64) round_sq[b] = 0.0;
-	if (lane != 0) return;
-	double radius, thresh;
-	radius_and_threshold(best, radius, thresh);
-	fin.d_res->radius = radius;
-	fin.d_res->thresh = thresh;
-	*fin.counter = 0;
-	mail_store(&fin.h_res->radius, radius);
-	mail_store(&fin.h_res->thresh, thresh);
-	mail_raise(&fin.h_res->seq, fin.seq);
+	merge_chunks<RT, true>(part, K, (int) gridDim.y, blockIdx.x * 64, mask, nb, round_sq, wmax);
+	finish_radius(fin, round_sq, nround_all);
 }
 
-// min over the member chunks, then per round the max over the left-out points with index >= 1
-// (cneighbors.c:160-168; the reference's loop starts at 1), and -- last workgroup -- radius and
-// threshold for the membership kernel and the host (see k_nearest_chosen)
+// the merge of k_nearest_uniform's member chunks, 64 points per workgroup, and -- last workgroup -- radius and
+// threshold for the membership kernel and the host (mdns_geom.h: merge_chunks, finish_radius)
 template <int RT>
 __global__ __launch_bounds__(kBlock) void k_nearest_finish(
     const double *__restrict__ part, int K, int ny, const unsigned *__restrict__ mask, int nb,
     double *__restrict__ round_sq, BootstrapFinish fin, int nround_all)
 {
 	__shared__ double wmax[4][RT];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	// four lanes per point, each with every fourth member chunk (one lane per point walking all
-	// chunks: 12 us at 5 000 points in 20 workgroups -- a chain of dependent row reads)
-	const int i = blockIdx.x * (kBlock / 4) + (threadIdx.x >> 2), yq = threadIdx.x & 3;
-	double v[RT];
-#pragma unroll
-	for (int b = 0; b < RT; b++) v[b] = 0.0;
-	const bool counts = i < K && i >= 1;
-	if (counts) {
-#pragma unroll
-		for (int b = 0; b < RT; b++) v[b] = 1e300;
-		for (int y = yq; y < ny; y += 4) {
-			const double *row = part + ((size_t) y * K + i) * RT;
-#pragma unroll
-			for (int b = 0; b < RT; b++) v[b] = fmin(v[b], row[b]);
-		}
-	}
-#pragma unroll
-	for (int b = 0; b < RT; b++) {
-		v[b] = fmin(v[b], __shfl_xor(v[b], 1, 64));
-		v[b] = fmin(v[b], __shfl_xor(v[b], 2, 64));
-	}
-	if (counts) {
-		const unsigned m = mask[i];
-#pragma unroll
-		for (int b = 0; b < RT; b++) if (b >= nb || (m >> b & 1u)) v[b] = 0.0;     // chosen points do not contribute
-	}
-#pragma unroll
-	for (int b = 0; b < RT; b++) {
-		const double w = wave_max(v[b]);
-		if (lane == 0) wmax[wv][b] = w;
-	}
-	__syncthreads();
-	if (threadIdx.x < RT && threadIdx.x < nb) {
-		const double w = fmax(fmax(wmax[0][threadIdx.x], wmax[1][threadIdx.x]), fmax(wmax[2][threadIdx.x], wmax[3][threadIdx.x]));
-		if (w > 0.0) atomic_max_nonneg(round_sq + threadIdx.x, w);
-	}
-	if (!fin.counter) return;
-	handover_release();
-	__syncthreads();
-	if (wv != 0) return;
-	unsigned ticket = 0;
-	if (lane == 0) ticket = atomicAdd(fin.counter, 1u);
-	if (__shfl(ticket, 0, 64) != gridDim.x - 1) return;
-	handover_acquire();
-	double best = 0.0;
-	for (int b = lane; b < nround_all; b += 64)
-		best = fmax(best, __hip_atomic_load(round_sq + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-	best = wave_max(best);
-	for (int b = lane; b < nround_all; b += 64) round_sq[b] = 0.0;      // the slots go back to zero
-	if (lane != 0) return;
-	double radius, thresh;
-	radius_and_threshold(best, radius, thresh);
-	fin.d_res->radius = radius;
-	fin.d_res->thresh = thresh;
-	*fin.counter = 0;
-	mail_store(&fin.h_res->radius, radius);
-	mail_store(&fin.h_res->thresh, thresh);
-	mail_raise(&fin.h_res->seq, fin.seq);
+	merge_chunks<RT, false>(part, K, ny, blockIdx.x * (kBlock / 4), mask, nb, round_sq, wmax);
+	finish_radius(fin, round_sq, nround_all);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -590,12 +370,6 @@ static int pick_tile(int ndim, size_t per_member_extra, size_t fixed_bytes)
 	if (n > (size_t) kMaxTile) n = kMaxTile;
 	return (int) (n & ~(size_t) 15);
 }
-
-#define MDNS_DIM_SWITCH(ndim, LAUNCH) \
-	switch ((ndim) <= kMaxRegDim ? (ndim) : 0) { \
-	case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; \
-	case 4: LAUNCH(4); break; case 5: LAUNCH(5); break; case 6: LAUNCH(6); break; \
-	case 7: LAUNCH(7); break; case 8: LAUNCH(8); break; default: LAUNCH(0); break; }
 
 bool launch_count_within(const double *d_members, int K, int ndim, double thresh_sq,
                          const RegionResult *d_res, const double *d_cands, int M, int *d_counts, const CountMail *mail)
@@ -660,7 +434,7 @@ static bool launch_nearest(const double *d_members, int K, int ndim, const doubl
 		d_mask = (unsigned *) mask_scratch((size_t) K * sizeof(unsigned));
 		if (!d_mask) return false;
 	}
-	// A finishing computation leaves its slots zeroed (see the kernel), so no launch has to
+	// A finishing computation leaves its slots zeroed (finish_radius), so no launch has to
 	// clear them; small pools then also read the choice matrix directly: one launch in all.
 	const bool fused = !NN && finish && K <= 2048 && !d_packed;
 	const int pts = small ? 16 : 64;
@@ -704,9 +478,8 @@ bool launch_bootstrap(const double *d_members, int K, int ndim, const double *d_
 // CUs three deep" picks (it chose 1 chunk at 50 000: 782 workgroups on 256 CUs, 3 217 us): sixteen
 // chunks wherever a chunk still has 128 members (fewer is all prologue).  At 50 000 points the pair
 // then runs within 12 % of the issue bound of its 28 vector instructions per pair and round set.
-static int uniform_chunks(int K, int num_cus)
+static int uniform_chunks(int K)
 {
-	(void) num_cus;
 	int most = K / 128;
 	if (most < 1) most = 1;
 	int best = most < 16 ? most : 16;
@@ -727,7 +500,7 @@ bool launch_bootstrap_packed(const double *d_members, int K, int ndim, const uns
 	// (pools of a few hundred points: one launch of the masked-NaN kernel is quicker than two of these)
 	if (ndim >= 1 && ndim <= 5 && K >= 640 && !classic) {
 		const int rt = nbootstraps <= 10 ? 10 : kRounds;
-		const int gy = uniform_chunks(K, c->num_cus);
+		const int gy = uniform_chunks(K);
 		int kchunk = (K + gy - 1) / gy;
 		kchunk = (kchunk + 3) & ~3;
 		const int ny = (K + kchunk - 1) / kchunk;
@@ -760,8 +533,7 @@ bool launch_bootstrap_packed(const double *d_members, int K, int ndim, const uns
 		unsigned *tickets = fold ? d_tickets : nullptr;
 #define UNI_LAUNCH(D) do { if (rt == 10) hipLaunchKernelGGL((k_nearest_uniform<D, 10>), grid, dim3(kBlock), lds, c->stream, d_members, K, d_packed, kchunk, tile_n, d_part, tickets, nbootstraps, d_round_sq, *finish, nbootstraps); \
 		else hipLaunchKernelGGL((k_nearest_uniform<D, kRounds>), grid, dim3(kBlock), lds, c->stream, d_members, K, d_packed, kchunk, tile_n, d_part, tickets, nbootstraps, d_round_sq, *finish, nbootstraps); } while (0)
-		switch (ndim) { case 1: UNI_LAUNCH(1); break; case 2: UNI_LAUNCH(2); break; case 3: UNI_LAUNCH(3); break;
-		                case 4: UNI_LAUNCH(4); break; default: UNI_LAUNCH(5); break; }
+		MDNS_DIM5_SWITCH(ndim, UNI_LAUNCH)
 #undef UNI_LAUNCH
 		if (!launched("k_nearest_uniform")) return false;
 		if (fold) return true;

@@ -814,3 +814,91 @@ def test_k6_in_morton_order_gives_the_all_pairs_radius(K, ndim, nboot, oracle, m
                              env=dict(os.environ, MDNS_K6_PATH="sorted"))
     assert out.returncode == 0, out.stderr[-1500:]
     assert float(out.stdout.strip().splitlines()[-1]) == want
+
+
+# (K, ndim, nboot): the smallest shapes at which the chunked K6 paths can still go wrong -- the lower bound of the
+# uniform path (5 chunks of 128: the four-lane chunk walk takes a second trip); K no multiple of 64 nor of the
+# chunk (last tile short, lanes past K); fewer rounds than the kernel carries (unused rounds must stay out of the
+# max); 16 rounds, 16 chunks, 5 dimensions
+K6_VARIANT_SHAPES = [(640, 1, 10), (705, 3, 10), (1300, 2, 3), (2111, 5, 16)]
+
+
+@pytest.fixture(scope="module")
+def k6_variant_cases(oracle):
+    """Point sets built as for the Morton test (dense core in a halo, duplicates, a degenerate last axis, the pool's
+    point 0 far outside), two different mask draws each, the oracle's radii for both, points near the second radius
+    and the oracle's counts for them."""
+    from massivedatans_amd.clustering import neighbors
+    cases = []
+    for K, ndim, nboot in K6_VARIANT_SHAPES:
+        rng = np.random.RandomState(K + ndim)
+        core = rng.normal(0.5, 0.002, size=(K // 2, ndim))
+        halo = rng.uniform(size=(K - K // 2, ndim))
+        pts = np.vstack((core, halo))
+        rng.shuffle(pts)
+        pts[7] = pts[3]                                       # duplicates: distance 0 pairs
+        pts[K // 3:K // 3 + 50] = pts[K // 3]
+        if ndim > 1:
+            pts[:, ndim - 1] = 0.25                           # a degenerate axis
+        pts[0] = 7.0                                          # far away: would set the radius if it counted
+        pts = np.ascontiguousarray(pts)
+        np.random.seed(K)
+        masks = [neighbors.draw_bootstrap_masks(K, nboot) for _ in range(2)]
+        assert not np.array_equal(masks[0], masks[1])
+        want = [oracle.bootstrapped_maxdistance(pts, np.ascontiguousarray(neighbors.unpack_bootstrap_masks(m, nboot))) for m in masks]
+        step = np.zeros(ndim)
+        step[0] = want[1]
+        near = np.ascontiguousarray(np.vstack((pts[1:4] + 0.999 * step, pts[1:4] + 1.001 * step, pts[:1])))
+        counts = oracle.count_within_distance_of(pts, want[1], near).astype(int)
+        cases.append(dict(pts=pts, masks=masks, nboot=nboot, want=want, near=near, counts=counts))
+    return cases
+
+
+def _k6_radii_and_counts(case):
+    """Two radius computations on ONE member set (the second runs on the round slots and the ticket counter the first
+    must have left zero), then one membership count."""
+    from massivedatans_amd.clustering import neighbors
+    s = neighbors.MemberSet(case["pts"])
+    radii = [s.bootstrap_radius_packed(m, case["nboot"]) for m in case["masks"]]
+    counts = s.count(case["near"])
+    s.close()
+    return radii, counts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", [{"MDNS_K6_MERGE": "fold"}, {"MDNS_K6_PATH": "classic"}], ids=["fold", "classic"])
+def test_k6_variant_paths_give_the_all_pairs_radius(variant, k6_variant_cases):
+    """The merge folded into k_nearest_uniform (MDNS_K6_MERGE=fold) and the masked-NaN kernel on packed choices at
+    K >= 640 (MDNS_K6_PATH=classic) against the oracle and the default path, bit for bit: radii of two computations
+    in a row on the same member set, and the counts of points near the radius.  One child process per variant for all
+    shapes (the path is chosen once per process)."""
+    import subprocess, sys, json, tempfile, time
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for case in k6_variant_cases:                             # the default path, in this process
+        radii, counts = _k6_radii_and_counts(case)
+        assert radii == case["want"]
+        assert np.array_equal(counts, case["counts"])
+    code = ("import sys, json, numpy as np; sys.path.insert(0, %r); from massivedatans_amd.clustering import neighbors\n"
+            "d = np.load(sys.argv[1]); out = []\n"
+            "for c in range(int(d['ncases'])):\n"
+            "    s = neighbors.MemberSet(d['pts%%d' %% c]); nboot = int(d['nboot%%d' %% c])\n"
+            "    radii = [s.bootstrap_radius_packed(d['masks%%d_%%d' %% (c, t)], nboot).hex() for t in range(2)]\n"
+            "    out.append([radii, s.count(d['near%%d' %% c]).tolist()]); s.close()\n"
+            "print(json.dumps(out))\n" % ROOT)
+    arrays = {"ncases": len(k6_variant_cases)}
+    for c, case in enumerate(k6_variant_cases):
+        arrays.update({"pts%d" % c: case["pts"], "nboot%d" % c: case["nboot"], "near%d" % c: case["near"],
+                       "masks%d_0" % c: case["masks"][0], "masks%d_1" % c: case["masks"][1]})
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "k6.npz")
+        np.savez(path, **arrays)
+        t0 = time.perf_counter()
+        out = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, timeout=120,
+                             env=dict(os.environ, MDNS_POLL_TIMEOUT_S="15", **variant))
+        print("k6 variant %r: child process for %d shapes took %.2f s" % (variant, len(k6_variant_cases), time.perf_counter() - t0))
+    assert out.returncode == 0, out.stderr[-1500:]
+    got = json.loads(out.stdout.strip().splitlines()[-1])
+    assert len(got) == len(k6_variant_cases)
+    for case, (radii, counts) in zip(k6_variant_cases, got):
+        assert [float.fromhex(r) for r in radii] == case["want"]
+        assert np.array_equal(counts, case["counts"])
