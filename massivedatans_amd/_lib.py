@@ -47,6 +47,9 @@ ABI_SYMBOLS = (
     # Part 7 (csrc/mdns_posterior.hip)
     "mdns_posterior_create", "mdns_posterior_destroy", "mdns_posterior_summary", "mdns_posterior_resample",
     "mdns_posterior_timings",
+    # caller-chosen line list of the MUSE-style template (csrc/mdns_like.hip k_lines_model)
+    "mdns_spectra_set_lines", "mdns_spectra_nparams", "mdns_lines_loglike_batch", "mdns_lines_loglike_batch_dev",
+    "mdns_lines_template_batch",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -192,6 +195,11 @@ def _declare(lib):
         "mdns_posterior_summary": (i, [vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
         "mdns_posterior_resample": (i, [vp, C.c_ulonglong, C.c_longlong, i, vp, vp]),
         "mdns_posterior_timings": (i, [vp, vp]),
+        "mdns_spectra_set_lines": (i, [vp, vp, i, i]),
+        "mdns_spectra_nparams": (i, [vp]),
+        "mdns_lines_loglike_batch": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_lines_loglike_batch_dev": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_lines_template_batch": (i, [vp, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -442,6 +442,32 @@ extern "C" void mdns_spectra_destroy(mdns_spectra *s)
 	delete s;
 }
 extern "C" int mdns_spectra_ndata(const mdns_spectra *s) { return s ? s->ndata : -1; }
+extern "C" int mdns_spectra_nparams(const mdns_spectra *s) { return s ? muse_nparams(s) : -1; }
+
+extern "C" int mdns_spectra_set_lines(mdns_spectra *s, const double *lines, int G, int ref)
+{
+	if (!s) { set_error("mdns_spectra_set_lines: null spectra handle"); return 1; }
+	if (s->njoint > 0) { set_error("mdns_spectra_set_lines: a joint state exists on these spectra (set the line list first)"); return 1; }
+	if (G == 0) { s->nlines = 0; return 0; }
+	if (G < 1 || G > kLinesMax || !lines) { set_error("mdns_spectra_set_lines: %d lines (1..%d)", G, kLinesMax); return 1; }
+	if (ref < 0 || ref >= G) { set_error("mdns_spectra_set_lines: ref=%d outside [0,%d)", ref, G); return 1; }
+	LineTable t = {};
+	for (int g = 0; g < G; g++) {
+		const double mu = lines[3 * g], a = lines[3 * g + 1], sg = lines[3 * g + 2];
+		if (!std::isfinite(mu) || !std::isfinite(a) || !std::isfinite(sg) || !(sg > 0)) {
+			set_error("mdns_spectra_set_lines: line %d = (%g, %g, %g): finite values and sigma > 0 are needed", g, mu, a, sg);
+			return 1;
+		}
+		t.mu[g] = mu; t.a[g] = a; t.sg[g] = sg;
+	}
+	for (int g = G; g < kLinesMax; g++) t.sg[g] = 1.0;
+	t.ref = ref;
+	Context *c = ctx();
+	if (c) (void) hipStreamSynchronize(c->stream);
+	s->lines = t;
+	s->nlines = G;
+	return 0;
+}
 extern "C" int mdns_spectra_nx(const mdns_spectra *s) { return s ? s->nx : -1; }
 
 // ---------------------------------------------------------------------------------------
@@ -529,16 +555,29 @@ extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypre
 	return launch_muse_rows(s, s->d_model, ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
-extern "C" int mdns_muse3_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
-                                            const int *d_row_ids, int M, double *d_Lout)
+// templates of the handle's model (the built-in three lines or its line list), then K2
+static int lines_loglike_dev(mdns_spectra *s, const double *d_params, int B, const int *d_row_ids, int M, double *d_Lout, const char *who)
 {
-	if (!ctx() || !check_batch(s, B, M, "mdns_muse3_loglike_batch_dev")) return 1;
+	if (!ctx() || !check_batch(s, B, M, who)) return 1;
 	if (!s->d_w || !s->d_x) { set_error("spectra need variances and a wavelength grid"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const int ldm = model_ld(s->nx);
 	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
-	if (!launch_muse3_model(s->d_x, s->nx, d_params, B, s->d_model, ldm)) return 1;
+	if (!launch_muse_model(s, d_params, B, s->d_model, ldm)) return 1;
 	return launch_muse_rows(s, s->d_model, ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
+}
+
+extern "C" int mdns_muse3_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
+                                            const int *d_row_ids, int M, double *d_Lout)
+{
+	if (s && s->nlines) { set_error("mdns_muse3_loglike_batch_dev: a line list is set on these spectra (mdns_lines_loglike_batch_dev)"); return 1; }
+	return lines_loglike_dev(s, d_params, B, d_row_ids, M, d_Lout, "mdns_muse3_loglike_batch_dev");
+}
+
+extern "C" int mdns_lines_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
+                                            const int *d_row_ids, int M, double *d_Lout)
+{
+	return lines_loglike_dev(s, d_params, B, d_row_ids, M, d_Lout, "mdns_lines_loglike_batch_dev");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -589,6 +628,8 @@ static int fn_muse(mdns_spectra *s, const double *p, int B, const int *r, int M,
 { return mdns_muse_loglike_batch_dev(s, p, B, r, M, o); }
 static int fn_muse3(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_muse3_loglike_batch_dev(s, p, B, r, M, o); }
+static int fn_lines(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
+{ return mdns_lines_loglike_batch_dev(s, p, B, r, M, o); }
 
 extern "C" int mdns_gauss_loglike_batch(mdns_spectra *s, const double *params, int B,
                                         double noise_level, const int *row_ids, int M, double *Lout)
@@ -604,6 +645,30 @@ extern "C" int mdns_muse3_loglike_batch(mdns_spectra *s, const double *params, i
                                         const int *row_ids, int M, double *Lout)
 {
 	return host_batch(s, params, B, 5, row_ids, M, Lout, 0, fn_muse3, "mdns_muse3_loglike_batch");
+}
+extern "C" int mdns_lines_loglike_batch(mdns_spectra *s, const double *params, int B,
+                                        const int *row_ids, int M, double *Lout)
+{
+	return host_batch(s, params, B, s ? muse_nparams(s) : 0, row_ids, M, Lout, 0, fn_lines, "mdns_lines_loglike_batch");
+}
+
+// the templates themselves: out [B][nx] on the host
+extern "C" int mdns_lines_template_batch(mdns_spectra *s, const double *params, int B, double *out)
+{
+	Context *c = ctx();
+	if (!c) return 1;
+	if (!s || !params || !out || B < 0) { set_error("mdns_lines_template_batch: bad arguments (B=%d)", B); return 1; }
+	if (!s->d_x) { set_error("mdns_lines_template_batch: spectra were created without a wavelength grid"); return 1; }
+	if (B == 0 || s->nx == 0) return 0;
+	const int ldm = model_ld(s->nx);
+	const size_t pbytes = (size_t) B * muse_nparams(s) * sizeof(double);
+	if (!grow(&s->d_params, &s->params_cap, (size_t) B * muse_nparams(s))) return 1;
+	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(s->d_params, params, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!launch_muse_model(s, s->d_params, B, s->d_model, ldm)) return 1;
+	if (!MDNS_HIP(hipMemcpy2DAsync(out, (size_t) s->nx * sizeof(double), s->d_model, (size_t) ldm * sizeof(double),
+	                               (size_t) s->nx * sizeof(double), (size_t) B, hipMemcpyDeviceToHost, c->stream))) return 1;
+	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -44,6 +44,12 @@ void *pinned_scratch(size_t bytes);
 void *mask_scratch(size_t bytes);      // packed bootstrap masks (separate from device_scratch)
 
 // ---- resident spectra -------------------------------------------------------------------
+// a caller-chosen emission-line list (mdns_spectra_set_lines): G rows (mu, a, sigma), line `ref` has its ratio fixed
+// to 1.  Travels to k_lines_model BY VALUE (152 bytes of kernel arguments: the wave reads it with scalar loads,
+// no lane touches memory for it).
+static constexpr int kLinesMax = 6;
+struct LineTable { double mu[kLinesMax], a[kLinesMax], sg[kLinesMax]; int ref; };
+static constexpr int kJointParamsMost = kLinesMax + 2;     // parameters of a candidate at most (joint state staging)
 }  // namespace mdns
 
 struct mdns_spectra {
@@ -73,6 +79,11 @@ struct mdns_spectra {
 	double *d_fyw_t = nullptr, *d_fw_t = nullptr;       // the same two in tiles of 16 rows (mdns_k2gemm.hip, tiled_at)
 	int ldf = 0;
 	bool fw_owned = false;
+	// the template model: nlines == 0 the built-in three lines (k_muse3_model, 5 parameters), else `lines`
+	// (k_lines_model, nlines + 2 parameters); fixed once a joint state exists on the handle (njoint)
+	int nlines = 0;
+	mdns::LineTable lines = {};
+	int njoint = 0;
 };
 
 namespace mdns {
@@ -179,8 +190,10 @@ bool launch_gauss_cols_commit(const mdns_spectra *s, const double *d_yT, const d
                               const JointArrays &st, void *d_header, unsigned long long *d_fillbits, double *d_Lrow);
 bool launch_gauss_cols(const mdns_spectra *s, const double *d_yT, const double *d_model_t, int bt, int B,
                        double scale, const int *d_rows, int M, double *d_out);
-bool launch_muse3_model(const double *d_x, int nx, const double *d_params, int B,
-                        double *d_model, int ldm);
+// templates of the handle's model for d_params [B][muse_nparams(s)] -> d_model [B][ldm], zero padded: the built-in
+// three lines (k_muse3_model) or the handle's line list (k_lines_model<G>)
+inline int muse_nparams(const mdns_spectra *s) { return s->nlines ? s->nlines + 2 : 5; }
+bool launch_muse_model(const mdns_spectra *s, const double *d_params, int B, double *d_model, int ldm);
 bool launch_gauss_rows(const mdns_spectra *s, const double *d_model, int ldm, int B,
                        double scale, const int *d_rows, int M, double *d_out);
 struct MuseBandFused;

@@ -417,7 +417,8 @@ struct mdns_joint {
 	// which likelihood: 0 = the Gaussian line (clike.c; lane kernels, trail), 1 = the three-line
 	// template scored with the scale-marginalised chi^2 (cmuselike.c; dense L[B, M] block)
 	int kind = 0;
-	int nparams = 3;
+	int nparams = 3;                   // kind 1: of the spectra's template model (5, or its line list's G + 2)
+	bool counted = false;              // this state is in the spectra's njoint (the model is fixed while it lives)
 	double *d_msq = nullptr;                                // templates' sums of squares (guarded accept filter, kind 0)
 	int *d_filter_scratch = nullptr;                        // matrix-core filter: ambiguous marks
 	double *d_dense = nullptr;  size_t dense_cap = 0;       // L[B, M] of a chunk (kind 1)
@@ -470,6 +471,7 @@ extern "C" void mdns_joint_destroy(mdns_joint *j)
 	if (!j) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
+	if (j->s && j->counted) j->s->njoint--;
 	void *bufs[] = {j->st.live, j->st.shelfL, j->st.shelfn, j->st.higher, j->d_running, j->d_Lmin, j->d_argmin_run,
 	                j->d_argmin, j->d_keep, j->d_status, j->d_flags, j->d_params, j->d_sel_rows, j->d_dense, j->d_msq,
 	                j->d_filter_scratch, j->d_jitter, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket,
@@ -491,7 +493,7 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	j->s = s; j->nlive = nlive; j->cap = shelf_cap; j->ndata = s->ndata;
 	// spectra with variances: the scale-marginalised likelihood against the three-line template
 	j->kind = s->d_w ? 1 : 0;
-	j->nparams = j->kind == 1 ? 5 : 3;
+	j->nparams = j->kind == 1 ? muse_nparams(s) : 3;
 	const size_t nd = (size_t) s->ndata;
 	const size_t res = (size_t) kFlagInts * sizeof(int) + result_bytes(s->ndata);
 	bool ok =
@@ -505,8 +507,8 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	    MDNS_HIP(hipMalloc((void **) &j->d_argmin, nd * sizeof(int))) &&
 	    MDNS_HIP(hipMalloc((void **) &j->d_status, sizeof(int))) &&
 	    MDNS_HIP(hipMalloc((void **) &j->d_flags, res)) &&
-	    // candidates [B, 3] followed by the selection's row ids: one staging block
-	    MDNS_HIP(hipMalloc((void **) &j->d_params, (size_t) MDNS_JOINT_MAX_BATCH * 5 * sizeof(double) + nd * sizeof(int) + 16)) &&
+	    // candidates [B, 3] followed by the selection's row ids: one staging block (kind 1: candidates [B, nparams] alone)
+	    MDNS_HIP(hipMalloc((void **) &j->d_params, (size_t) MDNS_JOINT_MAX_BATCH * kJointParamsMost * sizeof(double) + nd * sizeof(int) + 16)) &&
 	    MDNS_HIP(hipHostMalloc((void **) &j->h_box, sizeof(JointMailbox) + ((nd + 63) / 64) * 8, hipHostMallocMapped | hipHostMallocCoherent)) &&
 	    MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_box_dev, j->h_box, 0));
 	if (ok) {
@@ -527,6 +529,8 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 		j->nrun = s->ndata;
 	}
 	if (!ok) { mdns_joint_destroy(j); return nullptr; }
+	s->njoint++;
+	j->counted = true;
 	return j;
 }
 
@@ -606,12 +610,12 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 	if (!c || !j || !params) return 1;
 	if (j->kind != 1) { set_error("mdns_joint_init_muse3: the spectra carry no variances"); return 1; }
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_muse3: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
-	const size_t pbytes = (size_t) j->nlive * 5 * sizeof(double), n = (size_t) j->nlive * j->ndata;
+	const size_t pbytes = (size_t) j->nlive * j->nparams * sizeof(double), n = (size_t) j->nlive * j->ndata;
 	char *pin = joint_pin(j, pbytes);
 	if (!pin) return 1;
 	memcpy(pin, params, pbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	if (mdns_muse3_loglike_batch_dev(j->s, j->d_params, j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
+	if (mdns_lines_loglike_batch_dev(j->s, j->d_params, j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
 	if (jitter) {
 		// (musefuse.py:535 adds its noise to the initial points' likelihoods too)
 		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
@@ -1220,7 +1224,7 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 	out->B = B;
 	if (j->kind == 1) {
 		// templates + K2 into the dense block, jitter, accept flags
-		const size_t pbytes = (size_t) B * 5 * sizeof(double), n = (size_t) B * M;
+		const size_t pbytes = (size_t) B * j->nparams * sizeof(double), n = (size_t) B * M;
 		char *pin = joint_pin(j, pbytes);
 		if (!pin) return 1;
 		memcpy(pin, params, pbytes);
@@ -1233,7 +1237,7 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 			// (pageable source: the runtime stages it and returns when the caller's buffer is free)
 			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 		}
-		if (mdns_muse3_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
+		if (mdns_lines_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
 		const int flag = next_chunk_flag(j, c);
 		if (!flag) return 1;
 		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
@@ -1520,9 +1524,9 @@ extern "C" int mdns_backend_draw_commit(void *joint, int *accepted, unsigned lon
 // ---------------------------------------------------------------------------------------
 // the likelihood noise in band form (mdns.h Part 5: draw_band / draw_band_commit)
 // ---------------------------------------------------------------------------------------
-// candidates and their bounds travel as ONE block [B x 5 | B] into the head of d_bound; the noise row of a
+// candidates and their bounds travel as ONE block [B x nparams | B] into the head of d_bound; the noise row of a
 // commit lives behind it
-static constexpr size_t kBandRowAt = (size_t) MDNS_JOINT_MAX_BATCH * 6;
+static constexpr size_t kBandRowAt = (size_t) MDNS_JOINT_MAX_BATCH * (kJointParamsMost + 1);
 
 // launches of one scoring of the chunk in place (by the matrix-core filter or by the exact kernels)
 static int band_launch(mdns_joint *j, bool filtered)
@@ -1530,21 +1534,21 @@ static int band_launch(mdns_joint *j, bool filtered)
 	Context *c = ctx();
 	const int B = j->band_B, M = j->sel_M;
 	const int *d_rows = selection_rows(j);
-	const double *d_p = j->d_bound, *d_b = j->d_bound + (size_t) B * 5;
+	const double *d_p = j->d_bound, *d_b = j->d_bound + (size_t) B * j->nparams;
 	if (filtered) {
 		const int ldm = model_ld(j->s->nx) + 16;            // (not a power of two: mdns_k2gemm.hip, muse_filter_ld)
-		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse3_model(j->s->d_x, j->s->nx, d_p, B, j->s->d_model, ldm)) return 1;
+		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model, ldm)) return 1;
 		const MuseBandOut out = {&j->d_band->counter, j->d_band->clear, j->d_band->maybe, j->d_band->pair_b, j->d_band->pair_k,
 		                         j->d_band->pair_L, j->d_band->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_filter(j->s, j->s->d_model, ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
 	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w && j->s->d_x) {
 		// small chunks (pairs of candidates per workgroup): templates, then ONE kernel that scores, votes and publishes
 		const int ldm = model_ld(j->s->nx);
-		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse3_model(j->s->d_x, j->s->nx, d_p, B, j->s->d_model, ldm)) return 1;
+		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model, ldm)) return 1;
 		const MuseBandFused fused = {j->d_band, j->h_band_dev, ++j->band_seq, j->st.higher, d_b, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_rows(j->s, j->s->d_model, ldm, B, d_rows, M, j->d_dense, 0, &fused)) return 1;
 	} else {
-		if (mdns_muse3_loglike_batch_dev(j->s, d_p, B, d_rows, M, j->d_dense) != 0) return 1;
+		if (mdns_lines_loglike_batch_dev(j->s, d_p, B, d_rows, M, j->d_dense) != 0) return 1;
 		hipLaunchKernelGGL(k_joint_band, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream, (const double *) j->d_dense,
 		                   d_b, B, M, d_rows, (const double *) j->st.higher, j->d_band, (JointHeader *) j->d_result, j->h_band_dev, ++j->band_seq);
 	}
@@ -1575,7 +1579,7 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 		memset(j->h_band, 0, sizeof(BandBox));
 	}
 	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
-	const size_t pbytes = (size_t) B * 5 * sizeof(double), bbytes = (size_t) B * sizeof(double), n = (size_t) B * M;
+	const size_t pbytes = (size_t) B * j->nparams * sizeof(double), bbytes = (size_t) B * sizeof(double), n = (size_t) B * M;
 	char *pin = joint_pin(j, pbytes + bbytes);
 	if (!pin) return 1;
 	memcpy(pin, params, pbytes);

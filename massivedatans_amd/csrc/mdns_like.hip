@@ -232,6 +232,49 @@ __global__ void k_muse3_model(const double *__restrict__ x, int nx, const double
 	}
 }
 
+// the same family with the line list as run-time data (mdns_spectra_set_lines): G lines (mu, a, sigma), the ratio of
+// line t.ref fixed to 1, parameters (log_amp, z, log_width_scale, r_g for g != ref ascending).  Same geometry and
+// contract as k_muse3_model.  The table is a kernel argument passed by value: it is uniform, so it is read once per
+// wave into scalar registers; G is a template parameter so that the line loop unrolls as the literal one does (an exp
+// in fp64 is a few dozen VALU instructions: the loop body is the kernel).
+template <int G>
+__global__ void k_lines_model(const double *__restrict__ x, int nx, const double *__restrict__ params,
+                              double *__restrict__ model, int ldm, const LineTable t)
+{
+	const int b = blockIdx.y;
+	const int j0 = blockIdx.x * (int) blockDim.x * kMuseModelPer + threadIdx.x;
+	if (j0 >= ldm) return;
+	const double *p = params + (G + 2) * b;
+	const double amp = pow(10.0, p[0]), z = p[1], ws = pow(10.0, p[2]);
+	// per line: its weight, its centre -- the product rounded as the host statement rounds it (gen.muse_template), not
+	// fused into the subtraction: next to a line x - mu (1 + z) cancels, and the half ulp of a centre near 6 600 would
+	// be 4e-13 / sigma on the exponent's argument -- and its width
+	double wgt[G], cen[G], wid[G];
+#pragma unroll
+	for (int g = 0; g < G; g++) {
+		const double r = p[3 + g - (g >= t.ref ? 1 : 0)];                // (g == ref reads p[2 + g]: inside the row)
+		wgt[g] = amp * (g == t.ref ? 1.0 : r) * t.a[g];
+		cen[g] = __dmul_rn(t.mu[g], 1 + z);
+		wid[g] = t.sg[g] * ws;
+	}
+#pragma unroll
+	for (int i = 0; i < kMuseModelPer; i++) {
+		const int j = j0 + i * (int) blockDim.x;
+		if (j >= ldm) break;
+		double m = 0.0;
+		if (j < nx) {
+			const double xj = x[j];
+			m = 1.0;
+#pragma unroll
+			for (int g = 0; g < G; g++) {
+				const double u = (xj - cen[g]) / wid[g];
+				m = m + wgt[g] * exp(-0.5 * (u * u));
+			}
+		}
+		model[(size_t) b * ldm + j] = m;
+	}
+}
+
 // caller-supplied templates [B][nx] -> zero padded [B][ldm]
 __global__ void k_pad_model(const double *__restrict__ src, int nx, double *__restrict__ dst, int ldm)
 {
@@ -1321,12 +1364,21 @@ bool launch_joint_commit_trail(const int *d_thr_rows, int M, int B, const int *d
 	return launched("k_joint_commit_trail");
 }
 
-bool launch_muse3_model(const double *d_x, int nx, const double *d_params, int B, double *d_model, int ldm)
+bool launch_muse_model(const mdns_spectra *s, const double *d_params, int B, double *d_model, int ldm)
 {
 	Context *c = ctx();
 	dim3 grid((ldm + kBlock * kMuseModelPer - 1) / (kBlock * kMuseModelPer), B);
-	hipLaunchKernelGGL(k_muse3_model, grid, dim3(kBlock), 0, c->stream, d_x, nx, d_params, d_model, ldm);
-	return launched("k_muse3_model");
+	if (s->nlines == 0) {
+		hipLaunchKernelGGL(k_muse3_model, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x, s->nx, d_params, d_model, ldm);
+		return launched("k_muse3_model");
+	}
+#define LINES_LAUNCH(G) case G: hipLaunchKernelGGL(k_lines_model<G>, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x, s->nx, d_params, d_model, ldm, s->lines); break
+	switch (s->nlines) {
+	LINES_LAUNCH(1); LINES_LAUNCH(2); LINES_LAUNCH(3); LINES_LAUNCH(4); LINES_LAUNCH(5); LINES_LAUNCH(6);
+	default: set_error("k_lines_model: %d lines (1..%d)", s->nlines, kLinesMax); return false;
+	}
+#undef LINES_LAUNCH
+	return launched("k_lines_model");
 }
 
 bool launch_pad_model(const double *d_src, int nx, int B, double *d_dst, int ldm)

@@ -72,24 +72,51 @@ def nothing(n):
 MUSE_LINES = ((4861.3, 0.35, 4.0), (5006.8, 1.0, 4.0), (6562.8, 0.8, 5.0))
 
 
-def muse_template(x, params):
-    """Three-Gaussian emission template on a flat continuum.  ``params`` = (log_amp, z,
-    log_width_scale, ratio1, ratio3): ``ypred = 1 + 10**log_amp * sum_g r_g A_g
-    exp(-0.5 ((x - mu_g (1+z)) / (sigma_g 10**log_width_scale))**2)`` with ``r_2 = 1``.
-    Host statement of what the device template kernel evaluates
-    (``mdns_muse_template_batch``)."""
-    log_amp, z, log_ws, r1, r3 = params
-    ratios = (r1, 1.0, r3)
+#: lines a list may hold at most (include/mdns.h mdns_spectra_set_lines)
+MAX_LINES = 6
+
+
+def check_lines(lines, ref):
+    """``lines`` as a tuple of G ``(mu, a, sigma)`` float rows and ``ref`` as int; ValueError unless
+    1 <= G <= MAX_LINES, 0 <= ref < G, every value finite and every sigma > 0."""
+    try:
+        rows = tuple(tuple(float(v) for v in row) for row in lines)
+    except (TypeError, ValueError):
+        raise ValueError("lines must be rows of three numbers (mu, a, sigma)")
+    if not 1 <= len(rows) <= MAX_LINES:
+        raise ValueError("a line list has 1 to %d lines, not %d" % (MAX_LINES, len(rows)))
+    for g, row in enumerate(rows):
+        if len(row) != 3 or not all(np.isfinite(row)):
+            raise ValueError("line %d: three finite numbers (mu, a, sigma) are needed, got %r" % (g, row))
+        if not row[2] > 0:
+            raise ValueError("line %d: sigma = %g must be positive" % (g, row[2]))
+    if isinstance(ref, bool) or int(ref) != ref or not 0 <= int(ref) < len(rows):
+        raise ValueError("ref = %r must be the index of one of the %d lines" % (ref, len(rows)))
+    return rows, int(ref)
+
+
+def muse_template(x, params, lines=MUSE_LINES, ref=1):
+    """Gaussian emission lines on a flat continuum.  ``lines``: G rows ``(mu_g, A_g, sigma_g)``;
+    ``params`` = (log_amp, z, log_width_scale, r_g for g != ref in ascending g): ``ypred = 1 +
+    10**log_amp * sum_g r_g A_g exp(-0.5 ((x - mu_g (1+z)) / (sigma_g 10**log_width_scale))**2)``
+    with ``r_ref = 1``.  The defaults are the three lines of config C5: (log_amp, z,
+    log_width_scale, ratio1, ratio3).  Host statement of what the device template kernels
+    evaluate (``mdns_lines_template_batch``)."""
+    params = tuple(params)
+    if len(params) != len(lines) + 2:
+        raise ValueError("%d lines take %d parameters, not %d" % (len(lines), len(lines) + 2, len(params)))
+    log_amp, z, log_ws = params[:3]
+    ratios = params[3:3 + ref] + (1.0,) + params[3 + ref:]
     y = np.ones_like(x)
-    for (mu, a, sg), r in zip(MUSE_LINES, ratios):
+    for (mu, a, sg), r in zip(lines, ratios):
         y = y + (10 ** log_amp) * r * a * np.exp(-0.5 * ((x - mu * (1 + z)) / (sg * 10 ** log_ws)) ** 2)
     return y
 
 
-def muse_like(n, nx=4096):
+def muse_like(n, nx=4096, lines=MUSE_LINES, ref=1):
     """Synthetic IFU cube: ``n`` spaxels x ``nx`` channels.  Returns ``dict(x, y, v, z, scale)``
     with ``y`` and ``v`` (per-pixel variance) of shape ``[nx, n]``, the layout cmuselike.c:54
-    indexes (``i + j*ndata``)."""
+    indexes (``i + j*ndata``).  The truth holds ``lines`` (all ratios 1)."""
     n = int(n)
     x = np.linspace(4750, 9350, nx)
     rng = np.random.RandomState(n)
@@ -98,7 +125,7 @@ def muse_like(n, nx=4096):
     y = np.empty((nx, n))
     v = np.empty((nx, n))
     for i in range(n):
-        truth = scale[i] * muse_template(x, (0.0, z[i], 0.0, 1.0, 1.0))
+        truth = scale[i] * muse_template(x, (0.0, z[i], 0.0) + (1.0,) * (len(lines) - 1), lines, ref)
         v[:, i] = rng.uniform(0.5, 2.0, size=nx) * NOISE_LEVEL ** 2
         y[:, i] = truth + rng.normal(0, 1, size=nx) * np.sqrt(v[:, i])
     return dict(x=x, y=y, v=v, z=z, scale=scale)

@@ -467,19 +467,21 @@ class GaussJointState(object):
 
 class MuseJointState(GaussJointState):
     """The joint state of the MUSE-style problem on the GPU: spectra with per-pixel variances
-    (:class:`massivedatans_amd.like.MuseSpectra`), the three-line template evaluated on the device
-    from 5 parameters, the scale-marginalised likelihood of cmuselike.c:45-64.  Draw chunks go
-    through the entry points a native constrainer calls (``mdns_backend_draw_*``)."""
+    (:class:`massivedatans_amd.like.MuseSpectra`), the template evaluated on the device from the
+    parameters -- 5 of the built-in three lines, G + 2 of the spectra's line list --, the
+    scale-marginalised likelihood of cmuselike.c:45-64.  Draw chunks go through the entry points a
+    native constrainer calls (``mdns_backend_draw_*``)."""
 
     nparams = 5
 
     def __init__(self, spectra, nlive, shelf_cap=64):
         super(MuseJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
+        self.nparams = int(self._lib.mdns_spectra_nparams(spectra.handle))
 
     def init(self, xs, jitter=None):
         params = _lib.as_f64(xs)
-        if params.shape != (self.nlive, 5):
-            raise ValueError("initial points must be [nlive, 5]")
+        if params.shape != (self.nlive, self.nparams):
+            raise ValueError("initial points must be [nlive, %d]" % self.nparams)
         if jitter is not None:
             jitter = _lib.as_f64(jitter)
             if jitter.shape != (self.nlive, self.ndata):

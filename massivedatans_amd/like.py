@@ -117,10 +117,20 @@ class GaussLineSpectra(_Spectra):
 
 
 class MuseSpectra(_Spectra):
-    """Spectra with per-pixel variances scored against templates (cmuselike.c:45-64)."""
+    """Spectra with per-pixel variances scored against templates (cmuselike.c:45-64).  ``lines``:
+    G rows ``(mu, a, sigma)`` of the template the device evaluates from parameters, ``ref`` the line
+    whose ratio is 1 (:func:`massivedatans_amd.gen.muse_template`); None: the built-in three lines."""
 
-    def __init__(self, x, y, v, layout="channel_major"):
+    def __init__(self, x, y, v, layout="channel_major", lines=None, ref=1):
+        from . import gen
+        if lines is not None:
+            lines, ref = gen.check_lines(lines, ref)
         super(MuseSpectra, self).__init__(x, y, v, layout)
+        self.lines, self.ref = lines, (ref if lines is not None else 1)
+        if lines is not None:
+            table = _lib.as_f64(lines)
+            _lib.check(self._lib.mdns_spectra_set_lines(self._h, _lib.ptr(table), len(lines), ref), "mdns_spectra_set_lines")
+        self.nparams = int(self._lib.mdns_spectra_nparams(self._h))
 
     def loglike_batch(self, ypred, data_mask=None):
         """``ypred[B, nx]`` precomputed templates -> ``L[B, mask.sum()]`` (= -0.5 chi)."""
@@ -131,12 +141,26 @@ class MuseSpectra(_Spectra):
                            ypred, data_mask)
 
     def loglike_batch_lines(self, params, data_mask=None):
-        """``params[B, 5]`` of the config-C5 three-line template, evaluated on the device."""
+        """``params[B, 5]`` of the config-C5 three-line template -- ``[B, G + 2]`` of the line list
+        these spectra were made with -- evaluated on the device."""
         params = np.atleast_2d(_lib.as_f64(params))
-        if params.shape[1] != 5:
-            raise ValueError("params must be [B, 5]")
+        if params.shape[1] != self.nparams:
+            raise ValueError("params must be [B, %d]" % self.nparams)
+        if self.lines is not None:
+            return self._batch(self._lib.mdns_lines_loglike_batch, "mdns_lines_loglike_batch", params, data_mask)
         return self._batch(self._lib.mdns_muse3_loglike_batch, "mdns_muse3_loglike_batch",
                            params, data_mask)
+
+    def templates(self, params):
+        """``params[B, nparams]`` -> the templates ``[B, nx]`` as the device evaluates them."""
+        params = np.atleast_2d(_lib.as_f64(params))
+        if params.shape[1] != self.nparams:
+            raise ValueError("params must be [B, %d]" % self.nparams)
+        out = np.empty((len(params), self.nx))
+        if out.size:
+            _lib.check(self._lib.mdns_lines_template_batch(self._h, _lib.ptr(params), len(params), _lib.ptr(out)),
+                       "mdns_lines_template_batch")
+        return out
 
     def multi_loglikelihood(self, ypred, data_mask, jitter=None):
         """musefuse.py:534-535 given the template: masked likelihoods; ``jitter`` (e.g.

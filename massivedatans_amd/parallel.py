@@ -147,14 +147,21 @@ class ShardedGaussLine(object):
 class ShardedMuse(object):
     """The MUSE-style scorer (``loglike_batch(ypred[B, nx], mask)``, ``loglike_batch_lines(params[B, 5],
     mask)``: like.MuseSpectra) over all data sets, this rank scoring only its block of spectra and
-    variances.  ``backend_factory(x, y_block, v_block)`` builds the per-rank scorer."""
+    variances.  ``backend_factory(x, y_block, v_block)`` builds the per-rank scorer; with a line list
+    (``lines``, ``ref``: like.MuseSpectra) it is called with those two as keywords as well, so that every
+    rank sets the same list on its local handle."""
 
-    def __init__(self, x, y, v, backend_factory):
+    def __init__(self, x, y, v, backend_factory, lines=None, ref=1):
         torch, dist = _dist()
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.ndata = y.shape[1]
         self.lo, self.hi = shard_range(self.ndata, self.rank, self.world)
-        self.local = backend_factory(x, np.ascontiguousarray(y[:, self.lo:self.hi]), np.ascontiguousarray(v[:, self.lo:self.hi]))
+        if lines is not None:
+            from . import gen
+            lines, ref = gen.check_lines(lines, ref)
+        kw = dict(lines=lines, ref=ref) if lines is not None else {}
+        self.local = backend_factory(x, np.ascontiguousarray(y[:, self.lo:self.hi]), np.ascontiguousarray(v[:, self.lo:self.hi]), **kw)
+        self.lines, self.ref = lines, (ref if lines is not None else 1)
 
     def _sharded(self, call, rows_in, data_mask):
         if data_mask is None:
