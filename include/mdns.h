@@ -146,6 +146,15 @@ int mdns_lines_loglike_batch(mdns_spectra *s, const double *params, int B,
 /* The templates themselves, evaluated on the device: out f64[B, nx] on the host. */
 int mdns_lines_template_batch(mdns_spectra *s, const double *params, int B, double *out);
 
+/* Caller-defined models: the fixed-noise likelihood of sample.py:64-71 against B model curves the CALLER made,
+ * curves f64[B][nx] (one per candidate, any model): Lout f64[B][M], Lout[b][k] = -0.5 * sum_j ((curves[b][j] -
+ * y[row_k][j]) / noise_level)**2, row_ids as above.  Any spectra handle (variances are not used); nx >= 1, B >= 0,
+ * M >= 0.  The value of a pair (curve, spectrum) is the same bits whatever B, M, the position of either in its
+ * batch and the entry point that scored it -- one summation order over the channels (csrc/mdns_curves.hip).  Curve
+ * values are not validated: non-finite ones propagate as IEEE. */
+int mdns_curve_loglike_batch(mdns_spectra *s, const double *curves, int B, double noise_level,
+                             const int *row_ids, int M, double *Lout);
+
 /* Live-point pool resident on the device: the members of a RadFriends region
  * (clustering/radfriendsregion.py:59-70 keeps `members` and `maxdistance`; every are_inside /
  * count_nearby_members call of a region's life re-uses them, radfriendsregion.py:82-98). */
@@ -216,6 +225,10 @@ int mdns_joint_init_gauss(mdns_joint *j, const double *params, double noise_leve
  * adds to every likelihood evaluation).  A joint state over such spectra is driven through the
  * mdns_backend_* entry points (Part 5). */
 int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter);
+/* The same from model curves the caller made, curves f64[nlive][nx], for both kinds of spectra: without variances the
+ * fixed-noise likelihood (mdns_curve_loglike_batch) at noise_level, which the curve chunks of this state then use too;
+ * with variances the scale-marginalised one (mdns_muse_loglike_batch; noise_level is ignored).  jitter as above. */
+int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter);
 /* The same from a host matrix liveL f64[nlive, ndata] (row p = live slot p). */
 int mdns_joint_set_live(mdns_joint *j, const double *liveL);
 /* liveL f64[nlive, ndata] <- the device matrix (the integrator's remainder, :536-563). */
@@ -316,6 +329,10 @@ int mdns_muse3_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
                                  const int *d_row_ids, int M, double *d_Lout);
 /* d_params f64[B, mdns_spectra_nparams(s)]: the handle's line list, or the built-in model without one. */
 int mdns_lines_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
+                                 const int *d_row_ids, int M, double *d_Lout);
+
+/* d_curves f64[B] rows of ldc >= nx doubles, d_row_ids int32[M] or NULL, d_Lout f64[B][M]. */
+int mdns_curve_loglike_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, double noise_level,
                                  const int *d_row_ids, int M, double *d_Lout);
 
 /* The two halves of mdns_joint_draw_gauss on device pointers, nothing waits for the host:
@@ -592,6 +609,16 @@ int mdns_backend_draw_chunk(void *joint, const double *params, int B, const doub
 int mdns_backend_chunk_size(void *joint, int offered, int M, int hint);
 void *mdns_backend_region_begin(void *joint, const double *members, int K, int ndim, const unsigned *packed, int nbootstraps);
 int mdns_backend_region_radius(void *joint, void *region, double *radius);
+/* mdns_backend_draw_chunk for a model the CALLER evaluates: curves f64[B][nx], one model curve per candidate, in
+ * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M], both kinds of
+ * state).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
+ * variances) or as mdns_muse_loglike_batch (variances), decided and committed like a draw_chunk.  A draw may mix
+ * parameter chunks and curve chunks.  _dev: curves (rows of ldc >= nx doubles) and jitter already in device memory,
+ * read on the library stream. */
+int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
+                             unsigned long long *fillbits, int *nscored);
+int mdns_backend_draw_curves_dev(void *joint, const double *d_curves, int ldc, int B, const double *d_jitter, int *accepted,
+                                 unsigned long long *fillbits, int *nscored);
 /* mdns_backend_draw_chunk in two halves, for hosts that put something between them -- with the data sets
  * sharded over ranks a MAX all-reduce of the candidates' votes: `score` (after draw_begin)
  * stages and scores the chunk like draw_chunk and leaves one int32 0 / 1 vote per candidate in device

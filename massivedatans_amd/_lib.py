@@ -50,6 +50,9 @@ ABI_SYMBOLS = (
     # caller-chosen line list of the MUSE-style template (csrc/mdns_like.hip k_lines_model)
     "mdns_spectra_set_lines", "mdns_spectra_nparams", "mdns_lines_loglike_batch", "mdns_lines_loglike_batch_dev",
     "mdns_lines_template_batch",
+    # caller-made model curves (csrc/mdns_curves.hip)
+    "mdns_curve_loglike_batch", "mdns_curve_loglike_batch_dev", "mdns_joint_init_curves",
+    "mdns_backend_draw_curves", "mdns_backend_draw_curves_dev",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -200,6 +203,11 @@ def _declare(lib):
         "mdns_lines_loglike_batch": (i, [vp, vp, i, vp, i, vp]),
         "mdns_lines_loglike_batch_dev": (i, [vp, vp, i, vp, i, vp]),
         "mdns_lines_template_batch": (i, [vp, vp, i, vp]),
+        "mdns_curve_loglike_batch": (i, [vp, vp, i, d, vp, i, vp]),
+        "mdns_curve_loglike_batch_dev": (i, [vp, vp, i, i, d, vp, i, vp]),
+        "mdns_joint_init_curves": (i, [vp, vp, d, vp]),
+        "mdns_backend_draw_curves": (i, [vp, vp, i, vp, vp, vp, vp]),
+        "mdns_backend_draw_curves_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -628,6 +628,8 @@ static int fn_muse(mdns_spectra *s, const double *p, int B, const int *r, int M,
 { return mdns_muse_loglike_batch_dev(s, p, B, r, M, o); }
 static int fn_muse3(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_muse3_loglike_batch_dev(s, p, B, r, M, o); }
+static int fn_curve(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double noise)
+{ return mdns_curve_loglike_batch_dev(s, p, s->nx, B, noise, r, M, o); }
 static int fn_lines(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_lines_loglike_batch_dev(s, p, B, r, M, o); }
 
@@ -635,6 +637,11 @@ extern "C" int mdns_gauss_loglike_batch(mdns_spectra *s, const double *params, i
                                         double noise_level, const int *row_ids, int M, double *Lout)
 {
 	return host_batch(s, params, B, 3, row_ids, M, Lout, noise_level, fn_gauss, "mdns_gauss_loglike_batch");
+}
+extern "C" int mdns_curve_loglike_batch(mdns_spectra *s, const double *curves, int B, double noise_level,
+                                        const int *row_ids, int M, double *Lout)
+{
+	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, noise_level, fn_curve, "mdns_curve_loglike_batch");
 }
 extern "C" int mdns_muse_loglike_batch(mdns_spectra *s, const double *ypred, int B,
                                        const int *row_ids, int M, double *Lout)

@@ -1,0 +1,151 @@
+// Caller-defined models: the fixed-noise likelihood of sample.py:64-71 from model CURVES the caller made
+// (include/mdns.h, mdns_curve_loglike_batch[_dev]) -- what K1 computes from (A, mu, sig), for any model.
+//
+//   L[b][k] = -0.5 sum_j ((curves[b][j] - y[row_k][j]) / noise)^2
+//
+// k_curve_rows   one workgroup = 128 selected spectra x 32 candidates.  Channels go by in stages of 32: the
+//                stage's piece of the 128 spectrum rows (read from the [n_datasets x n_channels] rows, 256
+//                contiguous bytes per row: a sparse selection costs exactly its own bytes) and of the 32 curves
+//                are put into LDS, the next stage's loads already in flight in registers.  A lane owns TWO
+//                spectra, a wave EIGHT candidates: 16 sums per lane in registers, so a spectrum value is read
+//                from LDS once per eight candidates and a curve value -- the same address in all lanes, a
+//                broadcast -- once per two spectra.  Per pair of channels a wave issues 10 16-byte LDS reads
+//                (40 LDS cycles) against 64 fp64 instructions (256 cycles of its SIMD): with four SIMDs on one
+//                LDS the arithmetic is what bounds it.
+//
+// Per (curve, spectrum) pair the sum is ONE chain: channels in ascending order, d = c - y, acc = fma(d, d, acc),
+// from acc = 0; channels past the last one contribute fma(0, 0, acc), which changes nothing.  The value of a pair
+// therefore does not depend on B, M, where either sits in its batch, or which entry point asked.  Nothing is
+// validated: a non-finite curve value propagates as IEEE.
+#include "mdns_internal.h"
+
+namespace mdns {
+
+static constexpr int kCurveSpectra = 128;                 // spectra per workgroup (two per lane)
+static constexpr int kCurveNC = 8;                        // candidates per wave, all in registers
+static constexpr int kCurveCands = 4 * kCurveNC;          // candidates per workgroup
+static constexpr int kCurveCH = 32;                       // channels per stage
+// 16-byte slots per channel pair in LDS: one more than the spectra, so that the eight lanes of a store group --
+// eight channel pairs of one spectrum -- fall on eight different groups of four banks
+static constexpr int kCurveSlots = kCurveSpectra + 1;
+
+__global__ __launch_bounds__(256) void k_curve_rows(
+    const double *__restrict__ Y, int ld, int nx, const double *__restrict__ curves, int ldc, int B,
+    const int *__restrict__ rows, int M, double scale, double *__restrict__ out)
+{
+	__shared__ __attribute__((aligned(16))) double2 ys[kCurveCH / 2][kCurveSlots];       // [channel pair][spectrum]
+	__shared__ __attribute__((aligned(16))) double cs[kCurveCands][kCurveCH];            // [candidate][channel]
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int k0 = blockIdx.x * kCurveSpectra, b0 = blockIdx.y * kCurveCands;
+	// what this thread brings in per stage: channel pair cp of the spectra rsub, rsub + 16, ... (sixteen lanes
+	// read the 256 bytes of one row), and channel cch of the candidates crow, crow + 8, ...
+	const int cp = lane & 15, rsub = wave * 4 + (lane >> 4);
+	const int cch = threadIdx.x & 31, crow = threadIdx.x >> 5;
+	const double *yrow[kCurveSpectra / 16];
+#pragma unroll
+	for (int i = 0; i < kCurveSpectra / 16; i++) {
+		const int k = k0 + rsub + 16 * i;
+		const int kk = k < M ? k : M - 1;                                     // (past the selection: its last row again, never stored)
+		yrow[i] = Y + (size_t) (rows ? rows[kk] : kk) * ld + 2 * cp;
+	}
+	double2 yv[kCurveSpectra / 16];
+	double cv[kCurveCands / 8];
+	auto fetch = [&](int j0) {
+		const int j = j0 + 2 * cp;
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) {
+			// (rows are 16-byte aligned and an even number of doubles long: the pair of an even channel below nx is inside)
+			double2 v = make_double2(0.0, 0.0);
+			if (j < nx) v = *reinterpret_cast<const double2 *>(yrow[i] + j0);
+			if (j + 1 >= nx) v.y = 0.0;
+			yv[i] = v;
+		}
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 8; i++) {
+			const int b = b0 + crow + 8 * i;
+			cv[i] = b < B && j0 + cch < nx ? curves[(size_t) b * ldc + j0 + cch] : 0.0;
+		}
+	};
+	double acc[kCurveNC][2];
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) acc[c][0] = acc[c][1] = 0.0;
+	const bool working = b0 + wave * kCurveNC < B;                            // wave-uniform; an idle wave still stages
+	fetch(0);
+	for (int j0 = 0; j0 < nx; j0 += kCurveCH) {
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) ys[cp][rsub + 16 * i] = yv[i];
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 8; i++) cs[crow + 8 * i][cch] = cv[i];
+		__syncthreads();
+		if (j0 + kCurveCH < nx) fetch(j0 + kCurveCH);
+		if (working) {
+#pragma unroll 4
+			for (int jp = 0; jp < kCurveCH / 2; jp++) {
+				const double2 ya = ys[jp][lane], yb = ys[jp][lane + 64];
+#pragma unroll
+				for (int c = 0; c < kCurveNC; c++) {
+					const double2 m = *reinterpret_cast<const double2 *>(&cs[wave * kCurveNC + c][2 * jp]);
+					double d;
+					d = m.x - ya.x; acc[c][0] = fma(d, d, acc[c][0]);
+					d = m.y - ya.y; acc[c][0] = fma(d, d, acc[c][0]);
+					d = m.x - yb.x; acc[c][1] = fma(d, d, acc[c][1]);
+					d = m.y - yb.y; acc[c][1] = fma(d, d, acc[c][1]);
+				}
+			}
+		}
+		__syncthreads();
+	}
+	if (!working) return;
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) {
+		const int b = b0 + wave * kCurveNC + c;
+		if (b >= B) break;
+		const int k = k0 + lane;
+		if (k < M) out[(size_t) b * M + k] = acc[c][0] * scale;
+		if (k + 64 < M) out[(size_t) b * M + k + 64] = acc[c][1] * scale;
+	}
+}
+
+// curves [B][ldc] -> templates [B][ldm] as the K2 row kernels take them: zero behind channel nx
+__global__ __launch_bounds__(256) void k_curve_pad(const double *__restrict__ curves, int ldc, int nx, double *__restrict__ model, int ldm)
+{
+	const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+	if (j < ldm) model[(size_t) b * ldm + j] = j < nx ? curves[(size_t) b * ldc + j] : 0.0;
+}
+
+bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, int B, double scale,
+                       const int *d_rows, int M, double *d_out)
+{
+	Context *c = ctx();
+	if (B <= 0 || M <= 0) return true;
+	const dim3 grid((M + kCurveSpectra - 1) / kCurveSpectra, (B + kCurveCands - 1) / kCurveCands);
+	hipLaunchKernelGGL(k_curve_rows, grid, dim3(256), 0, c->stream, (const double *) s->d_y, s->ld, s->nx, d_curves, ldc, B,
+	                   d_rows, M, scale, d_out);
+	return launched("k_curve_rows");
+}
+
+bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm)
+{
+	Context *c = ctx();
+	if (B <= 0) return true;
+	hipLaunchKernelGGL(k_curve_pad, dim3((ldm + 255) / 256, B), dim3(256), 0, c->stream, d_curves, ldc, nx, d_model, ldm);
+	return launched("k_curve_pad");
+}
+
+}  // namespace mdns
+
+using namespace mdns;
+
+extern "C" int mdns_curve_loglike_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, double noise_level,
+                                            const int *d_row_ids, int M, double *d_Lout)
+{
+	if (!ctx()) return 1;
+	if (!s) { set_error("mdns_curve_loglike_batch_dev: null spectra handle"); return 1; }
+	if (B < 0 || M < 0 || M > s->ndata || s->nx < 1 || ldc < s->nx || (!d_row_ids && M != s->ndata && M != 0)) {
+		set_error("mdns_curve_loglike_batch_dev: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", B, M, s->ndata, ldc, s->nx);
+		return 1;
+	}
+	if (B == 0 || M == 0) return 0;
+	if (!d_curves || !d_Lout) { set_error("mdns_curve_loglike_batch_dev: null argument"); return 1; }
+	return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (noise_level * noise_level), d_row_ids, M, d_Lout) ? 0 : 1;
+}

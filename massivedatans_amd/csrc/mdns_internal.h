@@ -218,6 +218,12 @@ bool launch_tile_columns(const double *d_y, int ld, int ndata, int nx, const int
 bool launch_copy_rows(const double *d_src, int nx, int ndata, double *d_dst, int ld,
                       bool invert);
 bool launch_pad_model(const double *d_src, int nx, int B, double *d_dst, int ldm);
+// caller-made model curves (mdns_curves.hip): d_curves [B][ldc] against the selected rows of s->d_y at fixed noise,
+// d_out [B][M] = scale * sum_j (c_j - y_j)^2 (one chain per pair, channels ascending); and the curves as the K2 row
+// kernels take templates, [B][ldm] zero padded
+bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, int B, double scale,
+                       const int *d_rows, int M, double *d_out);
+bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm);
 
 // launchers implemented in mdns_neighbors.hip
 // What a radius computation leaves behind: written by the LAST workgroup of the bootstrap

@@ -423,6 +423,7 @@ struct mdns_joint {
 	int *d_filter_scratch = nullptr;                        // matrix-core filter: ambiguous marks
 	double *d_dense = nullptr;  size_t dense_cap = 0;       // L[B, M] of a chunk (kind 1)
 	double *d_jitter = nullptr;  size_t jitter_cap = 0;
+	double *d_curves = nullptr;  size_t curves_cap = 0;     // model curves of a chunk that came as a host array
 	// the draw in progress through the mdns_backend_* entry points: its selection, uploaded once
 	int *d_sel_rows = nullptr;  size_t sel_rows_cap = 0;
 	bool sel_rows = false;
@@ -474,7 +475,7 @@ extern "C" void mdns_joint_destroy(mdns_joint *j)
 	if (j->s && j->counted) j->s->njoint--;
 	void *bufs[] = {j->st.live, j->st.shelfL, j->st.shelfn, j->st.higher, j->d_running, j->d_Lmin, j->d_argmin_run,
 	                j->d_argmin, j->d_keep, j->d_status, j->d_flags, j->d_params, j->d_sel_rows, j->d_dense, j->d_msq,
-	                j->d_filter_scratch, j->d_jitter, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket,
+	                j->d_filter_scratch, j->d_jitter, j->d_curves, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket,
 	                j->d_commit_ticket, j->d_votes, j->d_band, j->d_bound, j->d_trail_stamp, j->d_trail_word, j->d_trail_L};
 	for (void *b : bufs) if (b) (void) hipFree(b);
 	void *pinned[] = {j->h_in, j->h_chain, j->h_band, j->h_box, j->h_pin};
@@ -618,6 +619,39 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 	if (mdns_lines_loglike_batch_dev(j->s, j->d_params, j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
 	if (jitter) {
 		// (musefuse.py:535 adds its noise to the initial points' likelihoods too)
+		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter, n);
+		if (!MDNS_HIP(hipGetLastError())) return 1;
+	}
+	if (joint_reset(j) != 0) return 1;
+	return joint_sync(c) ? 0 : 1;
+}
+
+// curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the fixed-noise likelihood from curves
+// (kind 0) or the scale-marginalised one on the curves staged as zero-padded templates (kind 1: exactly what
+// mdns_muse_loglike_batch_dev does with templates)
+static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
+{
+	mdns_spectra *s = j->s;
+	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
+	const int ldm = model_ld(s->nx);
+	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model, ldm) &&
+	       launch_muse_rows(s, s->d_model, ldm, B, d_rows, M, d_out);
+}
+
+extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter)
+{
+	Context *c = ctx();
+	if (!c || !j || !curves) return 1;
+	const int nx = j->s->nx;
+	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
+	const size_t n = (size_t) j->nlive * j->ndata;
+	if (j->kind == 0) j->noise_level = noise_level;
+	if (!joint_grow(&j->d_curves, &j->curves_cap, (size_t) j->nlive * nx)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves, curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!curves_score(j, j->d_curves, nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
+	if (jitter) {
 		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
 		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter, n);
@@ -1328,6 +1362,68 @@ extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B,
 	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_chunk") != 0) return 1;
 	if (backend_commit(j, c, sc, j->d_flags, sc.flag, "mdns_backend_draw_chunk") != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
+}
+
+// One chunk of a model the caller evaluates (mdns.h: mdns_backend_draw_curves): the candidates arrive as their model
+// curves.  Score into the dense block, then jitter, accept flags, commit and outcome as a chunk of the
+// scale-marginalised likelihood (path 1), for both kinds of state.
+static int draw_curves_dev(mdns_joint *j, Context *c, const double *d_curves, int ldc, int B, const double *d_jitter, int *accepted,
+                           unsigned long long *fillbits, const char *who)
+{
+	const int M = j->sel_M;
+	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
+	const int *d_rows;
+	if (!selection_to_device(j, c, &d_rows)) return 1;
+	if (!joint_grow(&j->d_dense, &j->dense_cap, (size_t) B * M)) return 1;
+	if (!curves_score(j, d_curves, ldc, B, d_rows, M, j->d_dense)) return 1;
+	const int flag = next_chunk_flag(j, c);
+	if (!flag) return 1;
+	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
+	                   j->d_dense, d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags, flag, (JointHeader *) j->d_result);
+	const ChunkScore sc = {1, B, flag};
+	if (backend_commit(j, c, sc, j->d_flags, flag, who) != 0) return 1;
+	return backend_fetch(j, accepted, fillbits);
+}
+
+// what both forms check first; 1: refused, 0: go on, -1: nothing to score (the outputs say so)
+static int draw_curves_check(mdns_joint *j, Context *c, const void *curves, int ldc, int B, int *accepted, int *nscored, const char *who)
+{
+	if (!c || !j || !accepted) return 1;
+	*accepted = -1;
+	if (!j->sel_open) { set_error("%s: no draw begun", who); return 1; }
+	if (!check_draw(j, B, j->sel_M, who)) return 1;
+	if (ldc < j->s->nx || j->s->nx < 1) { set_error("%s: rows of %d doubles for %d channels", who, ldc, j->s->nx); return 1; }
+	if (nscored) *nscored = B;
+	if (B == 0 || j->sel_M == 0) return -1;
+	if (!curves) { set_error("%s: null curves", who); return 1; }
+	return 0;
+}
+
+extern "C" int mdns_backend_draw_curves_dev(void *joint, const double *d_curves, int ldc, int B, const double *d_jitter, int *accepted,
+                                            unsigned long long *fillbits, int *nscored)
+{
+	Context *c = ctx();
+	mdns_joint *j = (mdns_joint *) joint;
+	const int rc = draw_curves_check(j, c, d_curves, ldc, B, accepted, nscored, "mdns_backend_draw_curves_dev");
+	if (rc != 0) return rc > 0;
+	return draw_curves_dev(j, c, d_curves, ldc, B, d_jitter, accepted, fillbits, "mdns_backend_draw_curves_dev");
+}
+
+extern "C" int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
+                                        unsigned long long *fillbits, int *nscored)
+{
+	Context *c = ctx();
+	mdns_joint *j = (mdns_joint *) joint;
+	const int nx = j ? j->s->nx : 0;
+	const int rc = draw_curves_check(j, c, curves, nx, B, accepted, nscored, "mdns_backend_draw_curves");
+	if (rc != 0) return rc > 0;
+	const size_t nc = (size_t) B * nx, n = (size_t) B * j->sel_M;
+	// (pageable sources: the runtime stages them and returns when the caller's buffers are free)
+	if (!joint_grow(&j->d_curves, &j->curves_cap, nc) ||
+	    !MDNS_HIP(hipMemcpyAsync(j->d_curves, curves, nc * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (jitter && (!joint_grow(&j->d_jitter, &j->jitter_cap, n) ||
+	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
+	return draw_curves_dev(j, c, j->d_curves, nx, B, jitter ? j->d_jitter : nullptr, accepted, fillbits, "mdns_backend_draw_curves");
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,

@@ -10,6 +10,9 @@ integer side (point ids, queues of ids, the data-set graph):
 * :class:`GaussJointState` -- the state lives in HBM (``mdns_joint_*`` of include/mdns.h); a
   draw chunk is scored, decided and committed on the GPU and only the accepted candidate's
   index, likelihood row and fill bits come back.
+* :class:`CurveJointState` -- the same state for a model the CALLER evaluates: a Python function makes
+  one model curve per candidate (numpy, or a torch tensor on the device), the device does everything
+  after the curves.
 * :class:`HostJointState` -- the same interface in numpy over any ``loglike_batch`` scorer.  It
   is the statement the device implementation is tested against (tests/), and what the CPU
   tests run the orchestration with.
@@ -496,6 +499,151 @@ class MuseJointState(GaussJointState):
         return int(self._lib.mdns_backend_chunk_size(self._h, int(offered), int(M), int(hint or 1)))
 
 
+class CurveJointState(GaussJointState):
+    """The joint state of a caller-defined model on the GPU.  ``model(xs f64[B, ndim]) -> curves [B, nx]``
+    makes one model curve per candidate -- a C-contiguous float64 numpy array, or a float64 torch tensor
+    on the device the library runs on, which is then read where it lies (by pointer and row stride; nothing
+    is copied through the host) -- and the device scores, decides and commits from the curves
+    (``mdns_backend_draw_curves[_dev]``, include/mdns.h).  Over a
+    :class:`massivedatans_amd.like.GaussLineSpectra` the likelihood is the fixed-noise one of sample.py:64-71
+    at the spectra's ``noise_level``, over a :class:`massivedatans_amd.like.MuseSpectra` the
+    scale-marginalised one of cmuselike.c:45-64.  ``nparams`` is the model's ``ndim``: what the first
+    ``init`` is given, or ``ndim=``.
+
+    A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in
+    :meth:`draw_params`.  Whoever drives the draws -- the sampler, the native core, a test -- may or may not
+    count accepted points into ``shelf_n`` itself, so :meth:`prepare` reads the shelf sizes back from the
+    device instead of trusting the mirror."""
+
+    def __init__(self, spectra, nlive, model, shelf_cap=64, ndim=None):
+        super(CurveJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
+        self.model = model
+        self.nx = int(spectra.nx)
+        self.nparams = int(ndim) if ndim is not None else None
+        self._d_jitter, self._d_jitter_bytes = None, 0
+        self._n32 = numpy.zeros(self.ndata, dtype=numpy.int32)
+
+    def close(self):
+        if getattr(self, "_d_jitter", None):
+            self._lib.mdns_dev_free(self._d_jitter)
+            self._d_jitter = None
+        super(CurveJointState, self).close()
+
+    def _curves(self, xs):
+        """``model(xs)`` as ``(address, row stride in doubles, on the device?, what keeps it alive)``."""
+        n = len(xs)
+        curves = self.model(xs)
+        if hasattr(curves, "data_ptr") and getattr(curves, "is_cuda", False):
+            import torch
+            if curves.dtype != torch.float64 or curves.dim() != 2 or tuple(curves.shape) != (n, self.nx):
+                raise ValueError("the model must return float64 curves [%d, %d], got %s %s"
+                                 % (n, self.nx, curves.dtype, tuple(curves.shape)))
+            if curves.stride(1) != 1 or (n > 1 and curves.stride(0) < self.nx):
+                curves = curves.contiguous()
+            # the library reads on its own stream: what torch has queued for the tensor must be done
+            torch.cuda.current_stream(curves.device).synchronize()
+            return curves.data_ptr(), max(int(curves.stride(0)), self.nx), True, curves
+        if hasattr(curves, "detach"):                     # a host tensor
+            curves = curves.detach().numpy()
+        curves = _lib.as_f64(curves)
+        if curves.shape != (n, self.nx):
+            raise ValueError("the model must return curves [%d, %d], got %s" % (n, self.nx, curves.shape))
+        return _lib.ptr(curves), self.nx, False, curves
+
+    def init(self, xs, jitter=None):
+        xs = numpy.asarray(xs, dtype=float)
+        if xs.ndim != 2 or len(xs) != self.nlive or (self.nparams is not None and xs.shape[1] != self.nparams):
+            raise ValueError("initial points must be [nlive, ndim]")
+        self.nparams = int(xs.shape[1])
+        address, ld, on_device, keep = self._curves(xs)
+        if on_device:                                     # (once per run: through the host)
+            keep = _lib.as_f64(keep.cpu().numpy())
+            address = _lib.ptr(keep)
+        if jitter is not None:
+            jitter = _lib.as_f64(jitter)
+            if jitter.shape != (self.nlive, self.ndata):
+                raise ValueError("jitter must be [nlive, ndata]")
+        self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.ptr(jitter) if jitter is not None else None),
+                    "mdns_joint_init_curves")
+        self.shelf_n[:] = 0
+        self.nevals_scored += self.nlive * self.ndata
+        self.ncalls += 1
+
+    def prepare(self):
+        self._check(self._lib.mdns_joint_get_thresholds(self._h, None, _lib.ptr(self._n32)), "mdns_joint_get_thresholds")
+        self.shelf_n[:] = self._n32
+        return super(CurveJointState, self).prepare()
+
+    def chunk_size(self, offered, M, hint=None):
+        return int(self._lib.mdns_backend_chunk_size(self._h, int(offered), int(M), int(hint or 1)))
+
+    def took(self, rows, beats):
+        """(``prepare`` reads the shelf sizes from the device: nothing to keep here)"""
+
+    def draw(self, xs, rows):
+        return self.draw_params(xs, rows)
+
+    def draw_params(self, params, rows, jitter=None):
+        """One chunk: ``params[B, ndim]`` as the model takes them (at most ``MDNS_JOINT_MAX_BATCH`` are
+        looked at); ``jitter`` [B, M] is added to the likelihoods before anything is compared or kept."""
+        M = self.ndata if rows is None else len(rows)
+        B = min(len(params), _lib.JOINT_MAX_BATCH)
+        if B == 0 or M == 0:
+            return -1, None, None, B
+        params = numpy.asarray(params, dtype=float)[:B]
+        address, ld, on_device, keep = self._curves(params)
+        if rows is not None:
+            rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
+        if jitter is not None:
+            jitter = _lib.as_f64(jitter)[:B]
+            if jitter.shape != (B, M):
+                raise ValueError("jitter must be [B, M]")
+        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.ptr(rows) if rows is not None else None, M),
+                    "mdns_backend_draw_begin")
+        out = (C.addressof(self._accepted), _lib.ptr(self._bits), C.addressof(self._nscored))
+        if on_device:
+            self._check(self._lib.mdns_backend_draw_curves_dev(self._h, address, ld, B, self._jitter_to_device(jitter), *out),
+                        "mdns_backend_draw_curves_dev")
+        else:
+            self._check(self._lib.mdns_backend_draw_curves(self._h, address, B, _lib.ptr(jitter) if jitter is not None else None, *out),
+                        "mdns_backend_draw_curves")
+        del keep
+        self.ncalls += 1
+        self.nevals_scored += B * M
+        idx = self._accepted.value
+        if idx < 0:
+            return -1, None, None, B
+        beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+        return idx, None, beats, B
+
+    def _jitter_to_device(self, jitter):
+        """The noise block of a chunk whose curves are on the device already (a synchronous copy)."""
+        if jitter is None:
+            return None
+        if jitter.nbytes > self._d_jitter_bytes:
+            if self._d_jitter:
+                self._check(self._lib.mdns_sync(), "mdns_sync")
+                self._lib.mdns_dev_free(self._d_jitter)
+            self._d_jitter_bytes = 2 * jitter.nbytes
+            self._d_jitter = self._lib.mdns_dev_alloc(self._d_jitter_bytes)
+            if not self._d_jitter:
+                self._d_jitter_bytes = 0
+                raise _lib.MdnsError("mdns_dev_alloc failed: " + _lib.last_error())
+        self._check(self._lib.mdns_h2d(self._d_jitter, _lib.ptr(jitter), jitter.nbytes), "mdns_h2d")
+        return self._d_jitter
+
+    def draw_gauss_params(self, params, rows):
+        """A chunk of the built-in Gaussian line, ``params[B, 3]`` = (A, mu, sig), on this state (fixed-noise
+        spectra only): parameter chunks and curve chunks may alternate."""
+        return GaussJointState.draw_params(self, params, rows)
+
+    # the halves of a chunk exist for sharded runs, which take parameters
+    def score_params(self, params, rows):
+        raise NotImplementedError("a curve state is driven through draw / draw_params")
+
+    score = score_backend = score_params
+
+
 _POP8 = numpy.array([bin(i).count("1") for i in range(256)], dtype=numpy.int64)
 
 
@@ -506,4 +654,4 @@ def _popcount(words):
     return _POP8[numpy.ascontiguousarray(words).view(numpy.uint8).reshape(len(words), 8)].sum(axis=1)
 
 
-__all__ = ['HostJointState', 'GaussJointState', 'MuseJointState']
+__all__ = ['HostJointState', 'GaussJointState', 'MuseJointState', 'CurveJointState']

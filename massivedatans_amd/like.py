@@ -108,6 +108,15 @@ class GaussLineSpectra(_Spectra):
         return self._batch(self._lib.mdns_gauss_loglike_batch, "mdns_gauss_loglike_batch",
                            params, data_mask, self.noise_level)
 
+    def loglike_batch_curves(self, curves, data_mask=None):
+        """``curves[B, nx]`` model curves the caller made, one per candidate (any model) ->
+        ``L[B, mask.sum()]``, ``L = -0.5 sum_j ((curve_j - y_j) / noise_level)^2`` (sample.py:64-71)."""
+        curves = np.atleast_2d(_lib.as_f64(curves))
+        if curves.shape[1] != self.nx:
+            raise ValueError("curves must be [B, %d]" % self.nx)
+        return self._batch(self._lib.mdns_curve_loglike_batch, "mdns_curve_loglike_batch",
+                           curves, data_mask, self.noise_level)
+
     def multi_loglikelihood(self, params, data_mask):
         """Same call as sample.py:101-108: ``params = (A, mu, log10 sig)`` after
         priortransform; returns the likelihood vector of the masked data sets."""

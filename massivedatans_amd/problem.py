@@ -1,0 +1,128 @@
+"""A problem definition the caller writes: any model that makes one curve per candidate.
+
+The reference's first instruction to its user is "Set your problem definition (parameters, model,
+likelihood) in sample.py": a host-side function predicts one model curve per candidate and the data
+comparison runs that curve over all spectra (sample.py:60-71; musefuse.py:222-284,520-535 is the same
+pattern with a stellar-population grid).  :class:`CurveProblem` is that pattern with the whole
+constrained draw on the device: the caller's ``model`` makes the curves of a chunk of candidates --
+in numpy, or in torch on the GPU --, and scoring, thresholds, accept test and commit happen in
+:class:`massivedatans_amd.jointstate.CurveJointState`.
+
+    import numpy
+    from massivedatans_amd import problem, sample
+
+    def model(xs):                       # xs[B, 4] -> curves[B, nx]: a broad and a narrow line
+        A, mu, broad, narrow = (xs[:, k, None] for k in range(4))
+        return A * (numpy.exp(-0.5 * ((mu - x) / broad) ** 2) + numpy.exp(-0.5 * ((mu - x) / narrow) ** 2))
+
+    def priortransform_batch(us):        # us[B, 4] in the unit cube -> xs[B, 4]
+        return numpy.column_stack((10 ** (2 * us[:, 0] - 2), 400 + 400 * us[:, 1], 10 + 90 * us[:, 2], 1 + 9 * us[:, 3]))
+
+    p = problem.CurveProblem(x, y, model, priortransform_batch, ndim=4, noise_level=0.01)
+    results, sampler, p, seconds = sample.run_model(p, nlive_points=400)
+"""
+import numpy
+
+MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
+
+
+def default_backend(x, y, noise_level, v=None):
+    """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood."""
+    from .like import GaussLineSpectra, MuseSpectra
+    if v is None:
+        return GaussLineSpectra(x, y, noise_level=noise_level)
+    return MuseSpectra(x, y, v)
+
+
+def host_curves(curves):
+    """What a model returned as a float64 numpy array (a device tensor comes over)."""
+    if hasattr(curves, "detach"):
+        curves = curves.detach().cpu().numpy()
+    return numpy.ascontiguousarray(curves, dtype=float)
+
+
+class _ModelScorer(object):
+    """``loglike_batch(xs[B, ndim], mask)`` = the backend's score of the model's curves."""
+
+    def __init__(self, score, model):
+        self.score, self.model = score, model
+
+    def loglike_batch(self, xs, data_mask=None):
+        return self.score(host_curves(self.model(numpy.asarray(xs, dtype=float))), data_mask)
+
+
+class CurveProblem(object):
+    """``x`` f64[nx], ``y`` (and ``v``) f64[nx, ndata] in the reference's layout.  ``model(xs[B, ndim]) ->
+    curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Without ``v``
+    the likelihood is ``-0.5 sum_j ((curve_j - y_j) / noise_level)**2`` (sample.py:64-71); with per-pixel
+    variances ``v`` the scale-marginalised one of cmuselike.c:45-64 (``noise_level`` is not used).
+    ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
+    stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
+    L[B, M]`` (tests put a numpy scorer there; the state is then the numpy one); by default the spectra go
+    to the GPU.
+
+    Gives ``sample.build_sampler`` what it reads of a problem."""
+
+    def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None):
+        self.x = numpy.ascontiguousarray(x, dtype=float)
+        self.y = numpy.ascontiguousarray(y, dtype=float)
+        self.v = None if v is None else numpy.ascontiguousarray(v, dtype=float)
+        self.nx, self.ndata = self.y.shape
+        if not 1 <= int(ndim) <= MAX_DIM:
+            raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
+        self.nparams = int(ndim)
+        self.model = model
+        self.priortransform_batch = priortransform_batch
+        self.noise_level = float(noise_level)
+        self.jitter_sigma = float(jitter_sigma)
+        self.backend = default_backend(self.x, self.y, self.noise_level, self.v) if backend is None else backend
+        if jitter_sigma > 0:
+            self.multi_loglikelihood_batch = None         # (every evaluation draws its noise: one candidate at a time)
+        self.ncalls = 0
+        self.nevals = 0
+
+    def priortransform(self, cube):
+        return numpy.asarray(self.priortransform_batch(numpy.asarray(cube, dtype=float)[None, :]), dtype=float)[0]
+
+    def _on_device(self):
+        from .like import _Spectra
+        return isinstance(self.backend, _Spectra)
+
+    def _score(self, curves, data_mask):
+        if hasattr(self.backend, "loglike_batch_curves"):
+            return self.backend.loglike_batch_curves(curves, data_mask)
+        return self.backend.loglike_batch(curves, data_mask)
+
+    def multi_loglikelihood(self, params, data_mask):
+        L = self._score(host_curves(self.model(numpy.asarray(params, dtype=float)[None, :])), data_mask)[0]
+        self.ncalls += 1
+        self.nevals += len(L)
+        if self.jitter_sigma > 0:
+            L = L + numpy.random.normal(0, self.jitter_sigma, size=len(L))
+        return L
+
+    def multi_loglikelihood_batch(self, params, data_mask):
+        L = self._score(host_curves(self.model(numpy.asarray(params, dtype=float))), data_mask)
+        self.ncalls += 1
+        self.nevals += L.size
+        return L
+
+    def native_prior(self):
+        """The prior transform stays in Python, the kernel parameters are the physical ones (the model takes them)."""
+        from . import constrainer
+        p = constrainer.custom_prior(self.nparams, self.nparams, self.priortransform_batch, lambda xs: xs)
+        p.jitter_sigma = self.jitter_sigma
+        return p
+
+    def joint_state(self, nlive_points):
+        from . import jointstate
+        if self._on_device():
+            js = jointstate.CurveJointState(self.backend, nlive_points, self.model, ndim=self.nparams)
+        else:
+            js = jointstate.HostJointState(_ModelScorer(self._score, self.model), nlive_points, self.ndata,
+                                           lambda xs: xs, nparams=self.nparams)
+        js.jitter_sigma = self.jitter_sigma
+        return js
+
+
+__all__ = ['CurveProblem', 'default_backend']

@@ -129,10 +129,13 @@ def native_context(joint, prior, ndata):
     ranks every rank runs the same constrainer on the same random stream; its chunks go through
     ``ShardedJointState.draw_params``, where the ranks exchange their accept flags."""
     from . import constrainer, parallel
-    from .jointstate import GaussJointState, HostJointState
+    from .jointstate import CurveJointState, GaussJointState, HostJointState
     if not constrainer.available():
         return None
-    if isinstance(joint, GaussJointState):
+    if isinstance(joint, CurveJointState):
+        # the model is a Python function: the chunks of a draw come back through it
+        backend = constrainer.python_backend(joint)
+    elif isinstance(joint, GaussJointState):
         backend = constrainer.hip_backend(joint)
     elif isinstance(joint, (HostJointState, parallel.ShardedJointState)):
         backend = constrainer.python_backend(joint)
@@ -223,6 +226,42 @@ def run(x, y, nlive_points=400, nsuperset_draws=10, use_graph=False, max_samples
         # constrainers stepped: Python code that draws after the run sees the reference's numbers
         sampler.native.sync_gauss_to_numpy()
     return results, sampler, problem, time.time() - start
+
+
+def run_model(problem, nlive_points=400, nsuperset_draws=10, use_graph=False, max_samples=0, min_samples=0,
+              tolerance=0.5, seed=1, batched=True, fused=None):
+    """``run`` for a problem object of the caller's (``massivedatans_amd.problem.CurveProblem``): the same
+    wiring, the same return value."""
+    if fused is None:
+        fused = os.environ.get('MDNS_FUSED', '1') != '0'
+    start = time.time()
+    sampler = build_sampler(problem, nlive_points, nsuperset_draws, use_graph, seed, batched, fused)
+    results = integrate(sampler, tolerance, min_samples, max_samples)
+    if sampler.native is not None:
+        sampler.native.sync_gauss_to_numpy()
+    return results, sampler, problem, time.time() - start
+
+
+def load_model(path):
+    """A ``MDNS_MODEL`` file: Python that defines ``model(xs[B, ndim]) -> curves[B, nx]``,
+    ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` and ``ndim``, optionally ``noise_level``.  Returns
+    them as a dict; ValueError says what is wrong with the file."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mdns_model", path)
+    if spec is None or spec.loader is None:
+        raise ValueError("cannot load a model from %s" % path)
+    module = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(module)
+    except Exception as e:       # noqa: BLE001 -- whatever the file raises is the user's to read
+        raise ValueError("%s: %s: %s" % (path, type(e).__name__, e))
+    out = {}
+    for name in ("model", "priortransform_batch", "ndim"):
+        if not hasattr(module, name):
+            raise ValueError("%s does not define `%s`" % (path, name))
+        out[name] = getattr(module, name)
+    out["noise_level"] = float(getattr(module, "noise_level", noise_level))
+    return out
 
 
 class _TimedSampler(object):
@@ -355,6 +394,14 @@ def main(argv=None):
     if len(argv) < 3:
         sys.exit("usage: python -m massivedatans_amd.sample <data.npz> <ndata>")
     logging.basicConfig(level=os.environ.get('MDNS_LOG', 'WARNING'))
+    definition = None
+    if os.environ.get('MDNS_MODEL'):
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            sys.exit("MDNS_MODEL: a caller-defined model runs in one process")
+        try:
+            definition = load_model(os.environ['MDNS_MODEL'])
+        except ValueError as e:
+            sys.exit("MDNS_MODEL: %s" % e)
     from . import gen
     ndata = int(argv[2])
     data = gen.load(argv[1], ndata)
@@ -363,12 +410,19 @@ def main(argv=None):
         sys.exit("CONSTRAINER=%s is not available: only MLFRIENDS runs on the accelerated path" % constrainer_type)
     nlive_points = int(os.environ.get('NLIVE_POINTS', '400'))
     use_graph = os.environ.get('USE_GRAPH', '1') == '1'               # the reference's default (sample.py:189)
-    backend = distributed_backend(data['x'], data['y'])
-    results, sampler, problem, duration = run(
-        data['x'], data['y'], nlive_points=nlive_points, backend=backend,
-        nsuperset_draws=int(os.environ.get('SUPERSET_DRAWS', '10')),
-        use_graph=use_graph,
-        max_samples=int(os.environ.get('MAXSAMPLES', 0)), min_samples=int(os.environ.get('MINSAMPLES', 0)))
+    settings = dict(nlive_points=nlive_points, nsuperset_draws=int(os.environ.get('SUPERSET_DRAWS', '10')), use_graph=use_graph,
+                    max_samples=int(os.environ.get('MAXSAMPLES', 0)), min_samples=int(os.environ.get('MINSAMPLES', 0)))
+    backend = None
+    if definition is not None:
+        # the caller's own model (massivedatans_amd.problem): variances `v` in the data file select the
+        # scale-marginalised likelihood
+        from . import problem as problem_module
+        results, sampler, problem, duration = run_model(problem_module.CurveProblem(
+            data['x'], data['y'], definition['model'], definition['priortransform_batch'], definition['ndim'],
+            noise_level=definition['noise_level'], v=data.get('v')), **settings)
+    else:
+        backend = distributed_backend(data['x'], data['y'])
+        results, sampler, problem, duration = run(data['x'], data['y'], backend=backend, **settings)
     if backend is not None:
         import torch.distributed as dist
         dist.barrier()
