@@ -1260,12 +1260,15 @@ int gauss_filter_pays(const mdns_spectra *s, int M, int B)
 	if (s->d_ysq == nullptr || gauss_cols_tile(M, B) < 8) return 0;
 	if (forced && forced[0] == '1') return 1;
 	if (forced && forced[0] == '0') return 0;
-	if (forced && forced[0] == 'm') return 2;
+	// the exact re-score behind the matrix-core forms (k_exact_list) holds a spectrum in at most 32 stages of 8 channels,
+	// like the quad-lane chunk (chunk_fits): longer spectra stay on the chain kernel, also when the form is forced
+	const bool listed = cols_nx(s->nx) <= 8 * 32;
+	if (forced && forced[0] == 'm') return listed ? 2 : 0;
 	// (round 4: with both operands straight from memory in tiles of 16 rows -- k_gauss_gemm_filter -- the filter kernel takes
 	// 29 us against the chain's 43 at 10 000 x 256 and a chunk alone 74.6 / 72.1 us against 86.9 / 81.3 (tools/filter_bench.py);
 	// but inside a whole sampler step the route still loses there: bench.py 96.8 us per step against 92.0 on the same box.  So
 	// the threshold stays where the passes around the product are small beside it.)
-	return B >= 128 && (long long) M * B >= 8000000LL ? 2 : 0;
+	return listed && B >= 128 && (long long) M * B >= 8000000LL ? 2 : 0;
 }
 
 // candidates per wave of the filter: with ONE vector instruction per (candidate, channel, spectrum)

@@ -12,64 +12,9 @@ import pytest
 from massivedatans_amd import gen, jointstate, sample
 from massivedatans_amd.like import GaussLineSpectra
 from chain_support import LaneScorer
+from filter_support import _drive
 
 pytestmark = pytest.mark.gpu
-
-
-def _drive(dev, host, ndata, rng, iterations, exact):
-    """The same sequence of iterations on both states: prepare, a few draw chunks on random
-    selections until every running data set has something waiting, advance."""
-    nlive = dev.nlive
-    running = np.arange(ndata)
-    ndraws = 0
-    for it in range(iterations):
-        if it == iterations // 2 and ndata > 8:
-            running = np.sort(rng.choice(ndata, size=max(3, ndata * 2 // 3), replace=False))   # cut_down
-            dev.set_running(running)
-            host.set_running(running)
-        a, b = dev.prepare(), host.prepare()
-        assert np.array_equal(a[1], b[1])
-        assert np.array_equal(a[0], b[0]) if exact else np.allclose(a[0], b[0], rtol=1e-12)
-        assert (a[2] is None) == (b[2] is None)
-        if a[2] is not None:
-            w = min(a[2].shape[1], b[2].shape[1])
-            assert np.array_equal(a[2][:, :w], b[2][:, :w]) and not a[2][:, w:].any() and not b[2][:, w:].any()
-        waiting = np.zeros(ndata, dtype=int)
-        waiting[running] = host.thresholds()[1][running]
-        passes = 0
-        while (waiting[running] == 0).any():
-            passes += 1
-            assert passes < 400, "the candidates never filled every shelf"
-            if passes <= 2:
-                rows = running                                      # superset draw
-            else:
-                empty = running[waiting[running] == 0]
-                rows = np.sort(rng.choice(empty, size=rng.randint(1, len(empty) + 1), replace=False))
-            B = int(rng.choice([1, 3, 17, 64, 200]))
-            cube = rng.uniform(size=(B, 3))
-            if passes > 6:
-                cube[:, 0] *= 0.05                                  # faint lines beat more thresholds
-            xs = sample.priortransform_batch(cube)
-            ha, hn = dev.thresholds()
-            hb, hm = host.thresholds()
-            assert np.array_equal(hn[running], hm[running])
-            assert np.array_equal(ha[running], hb[running]) if exact else np.allclose(ha[running], hb[running], rtol=1e-12)
-            sel = None if len(rows) == ndata else rows
-            xs = xs[:dev.chunk_size(len(xs), len(rows), hint=int(rng.randint(1, 80)))]
-            ia, La, ba, na = dev.draw(xs, sel)
-            ib, Lb, bb, nb_ = host.draw(xs[:na], sel)
-            assert ia == ib, (it, passes, ia, ib)
-            if ia >= 0:
-                ndraws += 1
-                assert np.array_equal(ba, bb)
-                if La is not None:                                  # (None: the state keeps the row to itself)
-                    assert np.array_equal(La, Lb) if exact else np.allclose(La, Lb, rtol=1e-12)
-                waiting[rows[ba]] += 1
-        dev.advance()
-        host.advance()
-        la, lb = dev.live_matrix(), host.live_matrix()
-        assert np.array_equal(la, lb) if exact else np.allclose(la, lb, rtol=1e-12)
-    return ndraws
 
 
 @pytest.mark.parametrize("fetch_rows", [True, False, "backend"])
