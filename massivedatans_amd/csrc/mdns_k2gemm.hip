@@ -287,7 +287,7 @@ __global__ __launch_bounds__(512) void k_muse_gemm_band_sk(
 			// for is their completion -- a device-scope fence would write back and invalidate this XCD's whole L2,
 			// templates included, once per piece: 365 us a launch against 221 without split tiles)
 			for (int e = threadIdx.x; e < NE; e += 64 * KW) __hip_atomic_store(&slot[e], red[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+			handover_release();                                           // (every wave's slot stores acknowledged before the ticket)
 			__syncthreads();
 			if (threadIdx.x == 0) {
 				const unsigned before = atomicAdd(&delivered[tile], (unsigned) (g1 - g0));
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(512) void k_muse_gemm_band_sk(
 			__syncthreads();
 			finish = last_piece != 0;
 			if (finish) {
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+				handover_acquire();
 				const long long t0 = (long long) tile * ng, t1 = t0 + ng;
 				// workgroups w with [U w / P, U (w + 1) / P) meeting [t0, t1)
 				long long wlo = t0 * gridDim.x / U, whi = (t1 * gridDim.x + U - 1) / U;

@@ -67,13 +67,14 @@ def child_environment(mode, cache=None):
 _child_died = []
 
 
-def run_child(mode, path, cache=None, timeout=600):
+def run_child(mode, path, cache=None, timeout=600, environment=child_environment):
     """One child pytest over ``path`` under filter ``mode``; once, never again.  Returns its output; raises
-    AssertionError if it failed, died, or if an earlier child of this session died."""
+    AssertionError if it failed, died, or if an earlier child of this session died.  ``environment(mode, cache)``
+    makes the child's environment (k2_filter_support.py passes its own)."""
     assert not _child_died, "not started: the child of mode %s died (%s)" % tuple(_child_died[0])
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-m", "gpu", path]
     try:
-        out = subprocess.run(cmd, env=child_environment(mode, cache), capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+        out = subprocess.run(cmd, env=environment(mode, cache), capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     except subprocess.TimeoutExpired as e:
         _child_died.append((mode, "no end within %d s" % timeout))
         raise AssertionError("the child of mode %s did not end within %d s\n%s" % (mode, timeout, (e.stdout or b"")[-3000:]))
