@@ -34,6 +34,7 @@
 #include "mdns_internal.h"
 
 #include <cmath>
+#include <cstdlib>
 
 namespace mdns {
 
@@ -462,10 +463,21 @@ bool post_var(mdns_posterior *h, hipStream_t st)
 	return post_launch_ok("mdns_posterior (std)");
 }
 
-// data sets per batch whose scratch (per data set: `per` bytes) fits in kScratchBytes
+// the scratch budget of a call: kScratchBytes, or MDNS_POST_SCRATCH_BYTES where that holds a positive integer
+// (tests only: it brings the batch loop within reach of small shapes).  Read at every call, not once per process.
+size_t post_scratch_bytes()
+{
+	const char *s = getenv("MDNS_POST_SCRATCH_BYTES");
+	if (!s || !*s) return kScratchBytes;
+	char *end = nullptr;
+	const long long v = strtoll(s, &end, 10);
+	return (end && !*end && v > 0) ? (size_t) v : kScratchBytes;
+}
+
+// data sets per batch whose scratch (per data set: `per` bytes) fits in the budget
 int post_batch(const mdns_posterior *h, size_t per)
 {
-	size_t b = kScratchBytes / (per ? per : 1);
+	size_t b = post_scratch_bytes() / (per ? per : 1);
 	if (b < 1) b = 1;
 	return b >= (size_t) h->ndata ? h->ndata : (int) b;
 }

@@ -233,3 +233,152 @@ def test_real_run_and_cli(tmp_path):
             assert a[k].tobytes() == b[k].tobytes(), k
         assert np.array_equal(a['logZ'], results['logZ'])
         assert np.array_equal(a['quant'], got['quant'][:, :, :3])          # the CLI's default quantiles: Q[:3]
+
+
+# ---- batches, edges and exact quantile ties: against the longdouble statement of posterior_support.py ------------
+# (its derived bounds, its quantile classes -- the inputs have no slivers, so every quantile must be equal -- and
+# numpy's draws, none of which lies within the clearance of a cdf boundary; test_posterior_host.py checks both
+# conditions, the statement and the bounds without a device)
+
+import posterior_support as ps
+
+
+def _ids(cases):
+    return [c[0] for c in cases]
+
+
+@pytest.fixture(autouse=True)
+def _default_scratch(monkeypatch):
+    monkeypatch.delenv(ps.SCRATCH_VARIABLE, raising=False)
+
+
+@pytest.mark.parametrize("case", ps.sweep_cases(), ids=_ids(ps.sweep_cases()))
+def test_sweep_matches_statement(case):
+    """Every nsamp around 64, 128, 256, kQLds and the longer slices, every ndata around the 64-lane groups and the
+    256-thread combines, every ndim: within the derived bounds, and within the fixed ones of the first tests."""
+    w, L, x, q, st = ps.stated(case)
+    got = run_summary(w, L, x, q)
+    ps.check_against_statement(got, st)
+    check_summary(got, ref_summary(w, L, x, q), x, w, L, q)
+
+
+@pytest.mark.parametrize("case", ps.quantile_cases(), ids=_ids(ps.quantile_cases()))
+def test_quantile_cases_match_statement(case):
+    """Dyadic ties (no allowance), key columns that exercise every level of the radix select, silent rows, rows
+    placed at the ends, nq = 1 and 64: staged in LDS and read from the scratch."""
+    w, L, x, q, st = ps.stated(case)
+    ps.check_against_statement(run_summary(w, L, x, q), st)
+
+
+def test_refusals():
+    from massivedatans_amd._lib import MdnsError
+    from massivedatans_amd.posterior import Posterior
+    w = np.zeros((4, 2))
+    with pytest.raises(MdnsError, match=r"ndim=9; 1 <= ndim <= 8"):
+        Posterior(w, w, np.zeros((4, 2, ps.K_POST_DIM + 1)))
+    with pytest.raises(MdnsError, match=r"ndim=0; 1 <= ndim <= 8"):
+        Posterior(w, w, np.zeros((4, 2, 0)))
+    x = np.arange(24.0).reshape(4, 2, 3)
+    with Posterior(w, w, x) as post:
+        for bad in ([0.0], [-0.25], [1.0 + 2.0 ** -52], [np.nan], [0.5, 1e-300, -0.0]):
+            with pytest.raises(MdnsError, match=r"q\[%d\]=.* outside \(0, 1\]" % (len(bad) - 1)):
+                post.summary(bad)
+        with pytest.raises(MdnsError, match=r"nq=65 \(1\.\.64 quantiles\)"):
+            post.summary(np.linspace(0.01, 0.99, ps.K_MAXQ + 1))
+        with pytest.raises(MdnsError, match=r"n=0"):
+            post.resample(0)
+        got = post.summary(np.linspace(0.01, 0.99, ps.K_MAXQ))           # and the handle still answers
+    ps.check_against_statement(got, ps.statement(w, w, x, got['q']))
+
+
+def _batched(monkeypatch, per, b, call):
+    monkeypatch.setenv(ps.SCRATCH_VARIABLE, str(b * per))
+    try:
+        return call()
+    finally:
+        monkeypatch.delenv(ps.SCRATCH_VARIABLE)
+
+
+@pytest.mark.parametrize("case", ps.batch_cases(), ids=_ids(ps.batch_cases()))
+def test_batches_equal_the_whole(case, monkeypatch):
+    """Batches of 1, 64, 65, all but one and all data sets -- for the summary and for the resampling, whose bytes
+    per data set differ -- give the bytes of the unbatched call, which is within the statement."""
+    from massivedatans_amd.posterior import Posterior
+    w, L, x, q, st = ps.stated(case)
+    nsamp, ndata, ndim = x.shape
+    n, seed, col = ps.BATCH_DRAWS
+    with Posterior(w, L, x) as post:
+        s0 = post.summary(q)
+        r0, x0 = post.resample(n, seed=seed, gather=True, first_column=col)
+    ps.check_against_statement(s0, st)
+    ps.check_draws(r0, x0, w, L, x, seed, col)
+    for b in ps.batch_sizes(ndata):
+        with Posterior(w, L, x) as post:                                 # a fresh handle: its moments run again too
+            s = _batched(monkeypatch, ps.summary_bytes(nsamp, ndim), b, lambda: post.summary(q))
+            r, xd = _batched(monkeypatch, ps.resample_bytes(nsamp), b,
+                             lambda: post.resample(n, seed=seed, gather=True, first_column=col))
+        for k in ('nfinite', 'log_norm', 'ess', 'mean', 'std', 'quant', 'imaxL'):
+            assert s[k].tobytes() == s0[k].tobytes(), (b, k)
+        assert r.tobytes() == r0.tobytes() and xd.tobytes() == x0.tobytes(), b
+
+
+def test_part_equals_whole_across_a_batch_boundary(monkeypatch):
+    """test_part_equals_whole with batches of 64 in the whole and of 25 in the part [40, 100): a boundary of either
+    falls inside the part."""
+    from massivedatans_amd.posterior import Posterior
+    w, L, x, q, _ = ps.stated(ps.batch_cases()[0])
+    nsamp, ndata, ndim = x.shape
+    lo, hi = 40, 100
+    with Posterior(w, L, x) as whole:
+        s = _batched(monkeypatch, ps.summary_bytes(nsamp, ndim), 64, lambda: whole.summary(Q))
+        r = _batched(monkeypatch, ps.resample_bytes(nsamp), 64, lambda: whole.resample(100, seed=2))
+    with Posterior(w[:, lo:hi], L[:, lo:hi], x[:, lo:hi]) as part:
+        sp = _batched(monkeypatch, ps.summary_bytes(nsamp, ndim), 25, lambda: part.summary(Q))
+        rp = _batched(monkeypatch, ps.resample_bytes(nsamp), 25, lambda: part.resample(100, seed=2, first_column=lo))
+    for k in ('nfinite', 'log_norm', 'ess', 'mean', 'std', 'quant', 'imaxL'):
+        assert s[k][lo:hi].tobytes() == sp[k].tobytes(), k
+    assert r[lo:hi].tobytes() == rp.tobytes()
+
+
+def test_deterministic_bytes_under_batches(monkeypatch):
+    from massivedatans_amd.posterior import Posterior
+    w, L, x, q, _ = ps.stated(ps.batch_cases()[0])
+    nsamp, ndata, ndim = x.shape
+    with Posterior(w, L, x) as a, Posterior(w, L, x) as b:
+        s1, s2 = (_batched(monkeypatch, ps.summary_bytes(nsamp, ndim), 7, lambda: h.summary(Q)) for h in (a, b))
+        r1, r2 = (_batched(monkeypatch, ps.resample_bytes(nsamp), 7, lambda: h.resample(500, seed=7)) for h in (a, b))
+        s3 = _batched(monkeypatch, ps.summary_bytes(nsamp, ndim), 7, lambda: a.summary(Q))
+    for k in s1:
+        assert s1[k].tobytes() == s2[k].tobytes() == s3[k].tobytes(), k
+    assert r1.tobytes() == r2.tobytes()
+
+
+def _check_resample(w, L, x, calls):
+    from massivedatans_amd.posterior import Posterior
+    with Posterior(w, L, x) as post:
+        for n, seed, col in calls:
+            index, xd = post.resample(n, seed=seed, gather=True, first_column=col)
+            ps.check_draws(index, xd, w, L, x, seed, col)
+            plain = post.resample(n, seed=seed, first_column=col)
+            assert plain.tobytes() == index.tobytes(), (n, seed, col)
+
+
+@pytest.mark.parametrize("nsamp", ps.RESAMPLE_NSAMP)
+def test_resample_sweep(nsamp):
+    """n = 1, 2, 3, 5, 255, 257, 4001 (the tail of the last Philox block cut at every length) at nsamp below, at
+    and above the 256 per-thread runs: every draw a finite row, gathered rows equal x[index], equal to numpy."""
+    w, L, x = ps.resample_input(nsamp)
+    _check_resample(w, L, x, ps.resample_calls(nsamp))
+
+
+def test_resample_keys():
+    """Every seed (0, 2^32, 2^63 + 5, 2^64 - 1) with every first column (0, 100, 2^40)."""
+    w, L, x = ps.resample_input(257)
+    _check_resample(w, L, x, ps.key_calls())
+
+
+@pytest.mark.parametrize("nsamp", ps.PLACEMENT_NSAMP)
+def test_resample_placements(nsamp):
+    """Finite rows only in the last slice, only row 0, only the last row, none in the first and last 300 rows."""
+    w, L, x = ps.placement_input(nsamp)
+    _check_resample(w, L, x, [(257, 2 ** 63 + 5, 100), (4001, 0, 2 ** 40)])
