@@ -675,16 +675,14 @@ bool launch_gauss_mfma_filter(const mdns_spectra *s, const double *d_yT, const d
 #undef GG_LAUNCH
 			if (!launched("k_gauss_gemm_filter")) return false;
 		} else if (pr == 0 && gauss_mfma_form() == 1) {
-			static double *d_zeros = nullptr;
-			if (!d_zeros && (!MDNS_HIP(hipMalloc((void **) &d_zeros, 16 * sizeof(double))) ||
-			                 !MDNS_HIP(hipMemsetAsync(d_zeros, 0, 16 * sizeof(double), c->stream)))) return false;
+			if (!c->mfma_zeros.fit_zeroed(16)) return false;                  // (made once: it never grows again)
 			const int nc = nbt >= 16 ? 4 : (nbt >= 8 ? 2 : 1);                // candidate tiles per wave
 			const int gy = (nbt + 4 * nc - 1) / (4 * nc);
 			ProfileScope prof(0);
 			note_kernel(0, "k_gauss_mfma_direct<%d>", nc);
 #define GD_LAUNCH(NC) hipLaunchKernelGGL((k_gauss_mfma_direct<NC>), dim3((M + 15) / 16, gy), dim3(256), 0, c->stream, \
 			d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest, \
-			(const double *) d_zeros)
+			(const double *) c->mfma_zeros.get())
 			if (nc == 4) GD_LAUNCH(4); else if (nc == 2) GD_LAUNCH(2); else GD_LAUNCH(1);
 #undef GD_LAUNCH
 			if (!launched("k_gauss_mfma_direct")) return false;

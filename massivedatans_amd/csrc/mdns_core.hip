@@ -46,7 +46,8 @@ bool launched(const char *name)
 // ---------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------
-static Context g_ctx;
+// never destroyed: its buffers must not be freed through a runtime that is torn down at exit
+static Context &g_ctx = *new Context;
 static bool g_ctx_ready = false;
 static std::mutex g_ctx_mutex;
 
@@ -96,52 +97,39 @@ Context *ctx()
 	return &g_ctx;
 }
 
-void *device_scratch(size_t bytes)
+void *device_scratch(size_t bytes) { Context *c = ctx(); return c && c->d_ws.fit(bytes) ? c->d_ws.get() : nullptr; }
+void *mask_scratch(size_t bytes) { Context *c = ctx(); return c && c->d_mask.fit(bytes) ? c->d_mask.get() : nullptr; }
+void *pinned_scratch(size_t bytes) { Context *c = ctx(); return c && c->h_pin.fit(bytes) ? c->h_pin.get() : nullptr; }
+
+void scratch_free(void *p, bool host) { (void) (host ? hipHostFree(p) : hipFree(p)); }
+
+// a block that exists may still be in use by a kernel on the stream: wait, then free it.  nullptr: no context
+static Context *drop_old(void *old, bool host)
 {
 	Context *c = ctx();
-	if (!c) return nullptr;
-	if (bytes <= c->d_ws_bytes) return c->d_ws;
-	if (c->d_ws) {
-		(void) hipStreamSynchronize(c->stream);
-		(void) hipFree(c->d_ws);
-		c->d_ws = nullptr; c->d_ws_bytes = 0;
-	}
-	size_t cap = bytes + bytes / 2 + 4096;
-	if (!MDNS_HIP(hipMalloc(&c->d_ws, cap))) return nullptr;
-	c->d_ws_bytes = cap;
-	return c->d_ws;
+	if (old) { if (c) (void) hipStreamSynchronize(c->stream); scratch_free(old, host); }
+	return c;
 }
 
-void *mask_scratch(size_t bytes)
+void *device_regrow(void *old, size_t bytes, bool zero)
 {
-	Context *c = ctx();
-	if (!c) return nullptr;
-	if (bytes <= c->d_mask_bytes) return c->d_mask;
-	if (c->d_mask) {
-		(void) hipStreamSynchronize(c->stream);
-		(void) hipFree(c->d_mask);
-		c->d_mask = nullptr; c->d_mask_bytes = 0;
-	}
-	size_t cap = bytes + bytes / 2 + 4096;
-	if (!MDNS_HIP(hipMalloc(&c->d_mask, cap))) return nullptr;
-	c->d_mask_bytes = cap;
-	return c->d_mask;
+	Context *c = drop_old(old, false);
+	void *p = nullptr;
+	if (!c || !MDNS_HIP(hipMalloc(&p, bytes))) return nullptr;
+	if (zero && !MDNS_HIP(hipMemsetAsync(p, 0, bytes, c->stream))) { (void) hipFree(p); return nullptr; }
+	return p;
 }
 
-void *pinned_scratch(size_t bytes)
+void *pinned_regrow(void *old, size_t bytes, unsigned flags)
 {
-	Context *c = ctx();
-	if (!c) return nullptr;
-	if (bytes <= c->h_pin_bytes) return c->h_pin;
-	if (c->h_pin) {
-		(void) hipStreamSynchronize(c->stream);
-		(void) hipHostFree(c->h_pin);
-		c->h_pin = nullptr; c->h_pin_bytes = 0;
-	}
-	size_t cap = bytes + bytes / 2 + 4096;
-	if (!MDNS_HIP(hipHostMalloc(&c->h_pin, cap, hipHostMallocDefault))) return nullptr;
-	c->h_pin_bytes = cap;
-	return c->h_pin;
+	void *p = nullptr;
+	return drop_old(old, true) && MDNS_HIP(hipHostMalloc(&p, bytes, flags)) ? p : nullptr;
+}
+
+void *scratch_dev_pointer(void *host_block)
+{
+	void *d = nullptr;
+	return MDNS_HIP(hipHostGetDevicePointer(&d, host_block, 0)) ? d : nullptr;
 }
 
 // smallest non-negative double T with sqrt(T) >= r.  sqrt on doubles is correctly rounded
@@ -216,19 +204,6 @@ ProfileScope::~ProfileScope()
 	if (slot < 0) return;
 	(void) hipEventRecord(g_pending[slot].stop, g_ctx.stream);
 	if (g_pending.size() >= 4096) drain_pending();      // bound the number of live events
-}
-
-template <typename T>
-static bool grow(T **p, size_t *cap, size_t need)
-{
-	if (need <= *cap) return true;
-	Context *c = ctx();
-	if (!c) return false;
-	if (*p) { (void) hipStreamSynchronize(c->stream); (void) hipFree(*p); *p = nullptr; *cap = 0; }
-	size_t n = need + need / 2 + 64;
-	if (!MDNS_HIP(hipMalloc((void **) p, n * sizeof(T)))) return false;
-	*cap = n;
-	return true;
 }
 
 }  // namespace mdns
@@ -429,11 +404,10 @@ extern "C" void mdns_spectra_destroy(mdns_spectra *s)
 	if (!s) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
-	void *bufs[] = {s->d_y, s->d_yT, s->d_w, s->d_x, s->d_model, s->d_params, s->d_rows, s->d_out, s->d_sel, s->d_ysq};
+	// (the grow-only buffers free themselves)
+	void *bufs[] = {s->d_y, s->d_yT, s->d_w, s->d_x, s->d_ysq};
 	for (void *b : bufs) if (b) (void) hipFree(b);
 	if (s->d_yG) (void) hipFree(s->d_yG);
-	if (s->d_selG) (void) hipFree(s->d_selG);
-	if (s->d_model_g) (void) hipFree(s->d_model_g);
 	if (s->d_fyw) (void) hipFree(s->d_fyw);
 	if (s->d_fyw_t) (void) hipFree(s->d_fyw_t);
 	if (s->d_fw_t) (void) hipFree(s->d_fw_t);
@@ -484,8 +458,8 @@ static bool check_batch(const mdns_spectra *s, int B, int M, const char *who)
 }
 
 namespace mdns {
-bool ensure_model(mdns_spectra *s, size_t doubles) { return grow(&s->d_model, &s->model_cap, doubles); }
-bool ensure_selection(mdns_spectra *s, size_t doubles) { return grow(&s->d_sel, &s->sel_cap, doubles); }
+bool ensure_model(mdns_spectra *s, size_t doubles) { return s->d_model.fit(doubles); }
+bool ensure_selection(mdns_spectra *s, size_t doubles) { return s->d_sel.fit(doubles); }
 
 // K1 with the lane kernel whatever the shape (one lane per spectrum, channels summed in
 // ascending order): L[B, M] to d_Lout.  The likelihood of a (candidate, spectrum) pair computed
@@ -497,7 +471,7 @@ int gauss_loglike_cols_dev(mdns_spectra *s, const double *d_params, int B, doubl
 	const double scale = -0.5 / (noise_level * noise_level);
 	const int bt = gauss_cols_tile(M, B);
 	if (!ensure_model(s, (size_t) cols_nx(s->nx) * (B + bt))) return 1;
-	if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model)) return 1;
+	if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model.get())) return 1;
 	// A selection is first copied into a compact replica (coalesced row reads, one pass)
 	// when the lane kernel would otherwise gather its columns once per candidate tile:
 	// many tiles, or a sparse selection (measured: 1 000 of 10 000 spectra, B = 256: 59 us
@@ -505,10 +479,10 @@ int gauss_loglike_cols_dev(mdns_spectra *s, const double *d_params, int B, doubl
 	const bool sparse = (size_t) M * 8 < (size_t) s->ndata;
 	if (d_row_ids && (B >= 128 || sparse)) {
 		if (!ensure_selection(s, (size_t) ((M + 63) / 64) * 64 * cols_nx(s->nx))) return 1;
-		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel)) return 1;
-		return launch_gauss_cols(s, s->d_sel, s->d_model, bt, B, scale, nullptr, M, d_Lout) ? 0 : 1;
+		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
+		return launch_gauss_cols(s, s->d_sel.get(), s->d_model.get(), bt, B, scale, nullptr, M, d_Lout) ? 0 : 1;
 	}
-	return launch_gauss_cols(s, s->d_yT, s->d_model, bt, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
+	return launch_gauss_cols(s, s->d_yT, s->d_model.get(), bt, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 }  // namespace mdns
 
@@ -538,9 +512,9 @@ extern "C" int mdns_gauss_loglike_batch_dev(mdns_spectra *s, const double *d_par
 	if (forced && !strcmp(forced, "cols") && s->d_yT) use_cols = true;
 	if (use_cols) return gauss_loglike_cols_dev(s, d_params, B, noise_level, d_row_ids, M, d_Lout);
 	const int ldm = model_ld(s->nx);
-	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
-	if (!launch_gauss_model(s->d_x, s->nx, d_params, B, s->d_model, ldm)) return 1;
-	return launch_gauss_rows(s, s->d_model, ldm, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
+	if (!s->d_model.fit((size_t) B * ldm)) return 1;
+	if (!launch_gauss_model(s->d_x, s->nx, d_params, B, s->d_model.get(), ldm)) return 1;
+	return launch_gauss_rows(s, s->d_model.get(), ldm, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
 extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypred, int B,
@@ -550,9 +524,9 @@ extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypre
 	if (!s->d_w) { set_error("spectra were created without variances"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const int ldm = model_ld(s->nx);
-	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
-	if (!launch_pad_model(d_ypred, s->nx, B, s->d_model, ldm)) return 1;
-	return launch_muse_rows(s, s->d_model, ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
+	if (!s->d_model.fit((size_t) B * ldm)) return 1;
+	if (!launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;
+	return launch_muse_rows(s, s->d_model.get(), ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
 // templates of the handle's model (the built-in three lines or its line list), then K2
@@ -562,9 +536,9 @@ static int lines_loglike_dev(mdns_spectra *s, const double *d_params, int B, con
 	if (!s->d_w || !s->d_x) { set_error("spectra need variances and a wavelength grid"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const int ldm = model_ld(s->nx);
-	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
-	if (!launch_muse_model(s, d_params, B, s->d_model, ldm)) return 1;
-	return launch_muse_rows(s, s->d_model, ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
+	if (!s->d_model.fit((size_t) B * ldm)) return 1;
+	if (!launch_muse_model(s, d_params, B, s->d_model.get(), ldm)) return 1;
+	return launch_muse_rows(s, s->d_model.get(), ldm, B, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
 extern "C" int mdns_muse3_loglike_batch_dev(mdns_spectra *s, const double *d_params, int B,
@@ -600,23 +574,23 @@ static int host_batch(mdns_spectra *s, const double *params, int B, int nparam,
 			}
 	}
 	const size_t np = (size_t) B * nparam, no = (size_t) B * M;
-	if (!grow(&s->d_params, &s->params_cap, np)) return 1;
-	if (!grow(&s->d_out, &s->out_cap, no)) return 1;
-	if (row_ids && !grow(&s->d_rows, &s->rows_cap, (size_t) M)) return 1;
+	if (!s->d_params.fit(np)) return 1;
+	if (!s->d_out.fit(no)) return 1;
+	if (row_ids && !s->d_rows.fit((size_t) M)) return 1;
 	// stage through pinned memory so both copies are truly asynchronous
 	const size_t stage_bytes = np * 8 + (row_ids ? (size_t) M * 4 : 0);
 	const size_t out_off = (stage_bytes + 15) & ~(size_t) 15;
 	char *pin = (char *) pinned_scratch(out_off + no * 8);
 	if (!pin) return 1;
 	memcpy(pin, params, np * 8);
-	bool ok = MDNS_HIP(hipMemcpyAsync(s->d_params, pin, np * 8, hipMemcpyHostToDevice, c->stream));
+	bool ok = MDNS_HIP(hipMemcpyAsync(s->d_params.get(), pin, np * 8, hipMemcpyHostToDevice, c->stream));
 	if (ok && row_ids) {
 		memcpy(pin + np * 8, row_ids, (size_t) M * 4);
-		ok = MDNS_HIP(hipMemcpyAsync(s->d_rows, pin + np * 8, (size_t) M * 4, hipMemcpyHostToDevice, c->stream));
+		ok = MDNS_HIP(hipMemcpyAsync(s->d_rows.get(), pin + np * 8, (size_t) M * 4, hipMemcpyHostToDevice, c->stream));
 	}
 	if (!ok) return 1;
-	if (fn(s, s->d_params, B, row_ids ? s->d_rows : nullptr, M, s->d_out, extra) != 0) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(pin + out_off, s->d_out, no * 8, hipMemcpyDeviceToHost, c->stream))) return 1;
+	if (fn(s, s->d_params.get(), B, row_ids ? s->d_rows.get() : nullptr, M, s->d_out.get(), extra) != 0) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(pin + out_off, s->d_out.get(), no * 8, hipMemcpyDeviceToHost, c->stream))) return 1;
 	if (!MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
 	memcpy(Lout, pin + out_off, no * 8);
 	return 0;
@@ -669,11 +643,11 @@ extern "C" int mdns_lines_template_batch(mdns_spectra *s, const double *params, 
 	if (B == 0 || s->nx == 0) return 0;
 	const int ldm = model_ld(s->nx);
 	const size_t pbytes = (size_t) B * muse_nparams(s) * sizeof(double);
-	if (!grow(&s->d_params, &s->params_cap, (size_t) B * muse_nparams(s))) return 1;
-	if (!grow(&s->d_model, &s->model_cap, (size_t) B * ldm)) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(s->d_params, params, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	if (!launch_muse_model(s, s->d_params, B, s->d_model, ldm)) return 1;
-	if (!MDNS_HIP(hipMemcpy2DAsync(out, (size_t) s->nx * sizeof(double), s->d_model, (size_t) ldm * sizeof(double),
+	if (!s->d_params.fit((size_t) B * muse_nparams(s))) return 1;
+	if (!s->d_model.fit((size_t) B * ldm)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(s->d_params.get(), params, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!launch_muse_model(s, s->d_params.get(), B, s->d_model.get(), ldm)) return 1;
+	if (!MDNS_HIP(hipMemcpy2DAsync(out, (size_t) s->nx * sizeof(double), s->d_model.get(), (size_t) ldm * sizeof(double),
 	                               (size_t) s->nx * sizeof(double), (size_t) B, hipMemcpyDeviceToHost, c->stream))) return 1;
 	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }
@@ -1280,11 +1254,9 @@ extern "C" int mdns_region_count_dev(mdns_region *r, const double *d_points, int
 }
 
 // one staging block for the membership round trips of the native constrainer: pinned + mapped,
-// layout { seq | counts int32[cap] | points f64[cap * ndim] }
-static char *g_stage = nullptr, *g_stage_dev = nullptr;
-static size_t g_stage_points = 0, g_stage_doubles = 0;
+// layout { seq | counts int32[M] | points f64[M * ndim] } (Context::count_stage; count_ticket: workgroups of the
+// current launch that are through)
 static unsigned long long g_stage_seq = 0;
-static int *g_stage_ticket = nullptr;                 // device: workgroups of the current launch that are through
 
 // K3 for host points with the least round trip: ONE kernel.  The points sit in a pinned block mapped
 // into the device, the kernel reads them there, stores the counts there and its last workgroup
@@ -1300,39 +1272,34 @@ extern "C" int mdns_region_count_polled(mdns_region *r, const double *points, in
 	if (M <= 0) return M < 0;
 	if (!r->on_device && r->radius != r->radius) { set_error("mdns_region_count: the region has no radius yet"); return 1; }
 	const size_t n = (size_t) M * r->ndim;
-	if ((size_t) M > g_stage_points || n > g_stage_doubles) {
-		if (g_stage) { (void) hipStreamSynchronize(c->stream); (void) hipHostFree(g_stage); g_stage = nullptr; }
-		const size_t np = (size_t) M + M / 2 + 1024, nd = n + n / 2 + 4096;
-		if (!MDNS_HIP(hipHostMalloc((void **) &g_stage, 64 + np * sizeof(int) + 64 + nd * sizeof(double), hipHostMallocMapped)) ||
-		    !MDNS_HIP(hipHostGetDevicePointer((void **) &g_stage_dev, g_stage, 0))) { g_stage = nullptr; g_stage_points = g_stage_doubles = 0; return 1; }
-		g_stage_points = np; g_stage_doubles = nd;
-		*(volatile unsigned long long *) g_stage = g_stage_seq;
-	}
-	if (!g_stage_ticket) {
-		if (!MDNS_HIP(hipMalloc((void **) &g_stage_ticket, sizeof(int))) ||
-		    !MDNS_HIP(hipMemsetAsync(g_stage_ticket, 0, sizeof(int), c->stream))) { g_stage_ticket = nullptr; return 1; }
-	}
-	const size_t off_counts = 64, off_points = (64 + g_stage_points * sizeof(int) + 63) & ~(size_t) 63;
-	memcpy(g_stage + off_points, points, n * sizeof(double));
+	// (the layout follows M, not the capacity: nothing in the block outlives a call but its first word)
+	const size_t off_counts = 64, off_points = (64 + (size_t) M * sizeof(int) + 63) & ~(size_t) 63;
+	if (!c->count_ticket.fit_zeroed(1)) return 1;
+	const size_t had = c->count_stage.cap();
+	if (!c->count_stage.fit(off_points + n * sizeof(double))) return 1;
+	char *const stage = c->count_stage.get(), *const stage_dev = c->count_stage.dev();
+	int *const ticket = c->count_ticket.get();
+	if (c->count_stage.cap() != had) *(volatile unsigned long long *) stage = g_stage_seq;      // a new block: its number so far
+	memcpy(stage + off_points, points, n * sizeof(double));
 	const unsigned long long seq = ++g_stage_seq;
-	const CountMail mail = {g_stage_ticket, (unsigned long long *) g_stage_dev, seq};
+	const CountMail mail = {ticket, (unsigned long long *) stage_dev, seq};
 	// right after a radius computation the kernel takes the threshold the bootstrap kernel left in
 	// device memory (stream order)
 	if (!launch_count_within(r->d_members, r->K, r->ndim, r->thresh_sq, r->on_device ? r->d_res : nullptr,
-	                         (const double *) (g_stage_dev + off_points), M, (int *) (g_stage_dev + off_counts), &mail)) return 1;
+	                         (const double *) (stage_dev + off_points), M, (int *) (stage_dev + off_counts), &mail)) return 1;
 	hipError_t e = hipSuccess;
-	switch (wait_seq((const volatile unsigned long long *) g_stage, seq, &e)) {
+	switch (wait_seq((const volatile unsigned long long *) stage, seq, &e)) {
 	case Wait::ok: break;
 	case Wait::timeout: set_error("membership count: no result within MDNS_POLL_TIMEOUT_S"); return 1;
 	case Wait::failed: set_error("membership count failed: %s", hipGetErrorString(e)); return 1;
 	case Wait::empty:
 		// (the stream drained and the number is not there: the launch failed; the ticket counter
 		// may be anywhere)
-		(void) hipMemsetAsync(g_stage_ticket, 0, sizeof(int), c->stream);
+		(void) hipMemsetAsync(ticket, 0, sizeof(int), c->stream);
 		set_error("membership count finished without a result");
 		return 1;
 	}
-	memcpy(counts, g_stage + off_counts, (size_t) M * sizeof(int));
+	memcpy(counts, stage + off_counts, (size_t) M * sizeof(int));
 	return 0;
 }
 

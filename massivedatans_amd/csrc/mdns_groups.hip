@@ -286,7 +286,7 @@ struct mdns_groups {
 	// per id; grown with the pile of accepted points.  One block:
 	//   header | touched bit map | plabel | point labels (out)
 	char *d_points = nullptr;  long long cap_points = 0;
-	char *h_pin = nullptr;  size_t pin_bytes = 0;
+	PinnedBuffer h_pin;
 	GroupsBox *h_box = nullptr, *h_box_dev = nullptr;  long long box_cap = 0;   // room for box_cap ids
 	unsigned long long box_seq = 0;
 	bool have_ids = false;
@@ -294,7 +294,7 @@ struct mdns_groups {
 	int rounds_hint = 4;                               // rounds the next call launches before it looks
 	int call = 0;                                      // number of the current components call (stamps)
 	int label_call = 0;                                // the stamp the point labels of the last call carry
-	char *h_rows = nullptr, *h_rows_dev = nullptr;  size_t rows_bytes = 0;    // pinned + mapped block of a call's selection (its own:
+	PinnedBuffer h_rows{hipHostMallocMapped};          // pinned + mapped block of a call's selection (its own:
 	                                                   // every call ends by polling, so it is free at the next one)
 	long long rounds_total = 0, calls_total = 0;
 };
@@ -306,17 +306,6 @@ static GroupsHeader *hdr_of(mdns_groups *g) { return (GroupsHeader *) g->d_point
 static unsigned long long *touched_of(mdns_groups *g) { return (unsigned long long *) (g->d_points + kHeaderBytes); }
 static PLabel *plabel_of(mdns_groups *g) { return (PLabel *) (touched_of(g) + words_of(g->cap_points)); }
 static int *pout_of(mdns_groups *g) { return (int *) (plabel_of(g) + g->cap_points); }
-
-static char *groups_pin(mdns_groups *g, size_t bytes)
-{
-	if (bytes <= g->pin_bytes) return g->h_pin;
-	Context *c = ctx();
-	if (g->h_pin) { (void) hipStreamSynchronize(c->stream); (void) hipHostFree(g->h_pin); g->h_pin = nullptr; g->pin_bytes = 0; }
-	const size_t want = bytes + bytes / 2 + 4096;
-	if (!MDNS_HIP(hipHostMalloc((void **) &g->h_pin, want, hipHostMallocDefault))) return nullptr;
-	g->pin_bytes = want;
-	return g->h_pin;
-}
 
 static bool groups_fit_points(mdns_groups *g, long long npoints)
 {
@@ -356,10 +345,8 @@ extern "C" void mdns_groups_destroy(mdns_groups *g)
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
 	if (g->h_box) (void) hipHostFree(g->h_box);
-	if (g->h_rows) (void) hipHostFree(g->h_rows);
 	void *bufs[] = {g->d_idsT, g->d_tmp, g->d_label, g->d_rows, g->d_labels, g->d_points};
 	for (void *b : bufs) if (b) (void) hipFree(b);
-	if (g->h_pin) (void) hipHostFree(g->h_pin);
 	delete g;
 }
 
@@ -417,8 +404,8 @@ extern "C" int mdns_groups_replace(mdns_groups *g, const int32_t *rows, const in
 	if (n == 0) return 0;
 	// rows | slots | new ids: one pinned block, one copy.  Nothing waits: a bad index raises a
 	// bit in the header that the next mdns_groups_components reports.
-	char *pin = groups_pin(g, (size_t) 3 * n * sizeof(int));
-	if (!pin) return 1;
+	if (!g->h_pin.fit((size_t) 3 * n * sizeof(int))) return 1;
+	char *pin = g->h_pin.get();
 	// (the staging block may still feed the previous copy)
 	if (!MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
 	memcpy(pin, rows, (size_t) n * 4);
@@ -463,14 +450,10 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 	if (!groups_fit_box(g, most)) return 1;
 	if (rows) {
 		// (the selection's own pinned block: the previous call ended by polling for its outcome, so
-		// nothing reads the block any more -- no stream synchronisation)
-		if ((size_t) M * 4 > g->rows_bytes) {
-			if (g->h_rows) { (void) hipStreamSynchronize(c->stream); (void) hipHostFree(g->h_rows); g->h_rows = nullptr; g->rows_bytes = 0; }
-			if (!MDNS_HIP(hipHostMalloc((void **) &g->h_rows, (size_t) g->ndata * 4, hipHostMallocMapped)) ||
-			    !MDNS_HIP(hipHostGetDevicePointer((void **) &g->h_rows_dev, g->h_rows, 0))) return 1;
-			g->rows_bytes = (size_t) g->ndata * 4;
-		}
-		memcpy(g->h_rows, rows, (size_t) M * 4);
+		// nothing reads the block any more; it is made once, for every data set, so the fit never finds a block
+		// to replace and never synchronises the stream)
+		if (!g->h_rows.fit((size_t) g->ndata * 4)) return 1;              // (room for every data set: made once)
+		memcpy(g->h_rows.get(), rows, (size_t) M * 4);
 	}
 	int *d_rows = rows ? g->d_rows : nullptr;
 	// Nothing is cleared: point labels and the rounds' "moved" flags carry the number of the batch
@@ -489,7 +472,7 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 		if (total > 0) flag = ++g->call;                              // (labels keep the stamp `call`; only the flags move on)
 		for (int r = 0; r < batch; r++)
 			hipLaunchKernelGGL(k_groups_round, dim3((M + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-			                   g->d_idsT, g->nlive, d_rows, rows && total == 0 && r == 0 ? (const int *) g->h_rows_dev : nullptr, M, npoints,
+			                   g->d_idsT, g->nlive, d_rows, rows && total == 0 && r == 0 ? (const int *) g->h_rows.dev() : nullptr, M, npoints,
 			                   plabel_of(g), g->d_label, total == 0 && r == 0 ? 1 : 0, call,
 			                   flag, &hdr_of(g)->changed[r], &hdr_of(g)->status, kSweeps);
 		total += batch;

@@ -24,16 +24,104 @@ bool launched(const char *name);
 enum class Wait { ok, timeout, failed, empty };
 Wait wait_seq(const volatile unsigned long long *at, unsigned long long want, hipError_t *err = nullptr);
 
+// ---- grow-only scratch ---------------------------------------------------------------------
+// How large a block that has to hold `need` elements of `elem` bytes is made: half as much again, in whole pages of
+// 4 KiB.  The ONE growth policy of every DeviceBuffer and PinnedBuffer.
+constexpr size_t grown_bytes(size_t need, size_t elem) { return ((need + need / 2) * elem + 4095) / 4096 * 4096; }
+static_assert(grown_bytes(0, 8) == 0, "nothing asked, nothing made");
+static_assert(grown_bytes(1, 8) == 4096, "one element: one page");
+static_assert(grown_bytes(341, 8) == 4096, "341 + 170 doubles = 4088 bytes: still one page");
+static_assert(grown_bytes(342, 8) == 8192, "342 + 171 doubles = 4104 bytes: two pages");
+// The growing path (mdns_core.hip): a block that exists is freed once the context's current stream has drained -- a
+// kernel may still be using it --, a first allocation waits for nothing.  zero: the new block is cleared over all its
+// `bytes`, in stream order; flags: as hipHostMalloc takes them.  nullptr (and the error set) on any failure; the old
+// block is gone either way.
+void *device_regrow(void *old, size_t bytes, bool zero);
+void *pinned_regrow(void *old, size_t bytes, unsigned flags);
+void scratch_free(void *p, bool host);
+void *scratch_dev_pointer(void *host_block);       // of a mapped block; nullptr (and the error set) on failure
+
+// An owning, grow-only block of device memory for `cap()` elements.  Everything else (kernel arguments, JointTrail,
+// last_yT ...) is a view: a raw pointer taken with get() AFTER the fit() of the call that uses it.
+template <typename T> class DeviceBuffer {
+public:
+	DeviceBuffer() = default;
+	DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+	DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+	{
+		if (this != &o) { release(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+		return *this;
+	}
+	~DeviceBuffer() { release(); }
+	T *get() const { return p_; }
+	size_t cap() const { return cap_; }
+	// holds >= n elements afterwards; contents are NOT kept across a growth.  false (error set): the buffer is empty
+	bool fit(size_t n) { return n <= cap_ || regrow(n, false); }
+	// the same; a newly allocated block is zero over its whole capacity, in stream order
+	bool fit_zeroed(size_t n) { return n <= cap_ || regrow(n, true); }
+	// (whoever calls has made sure that nothing on the device uses the block any more)
+	void release() { if (p_) scratch_free(p_, false); p_ = nullptr; cap_ = 0; }
+private:
+	bool regrow(size_t n, bool zero)
+	{
+		const size_t bytes = grown_bytes(n, sizeof(T));
+		p_ = (T *) device_regrow(p_, bytes, zero);
+		cap_ = p_ ? bytes / sizeof(T) : 0;
+		return p_ != nullptr;
+	}
+	T *p_ = nullptr;
+	size_t cap_ = 0;
+};
+
+// The same for pinned host memory, counted in bytes; `flags` as hipHostMalloc takes them.  dev(): a mapped block as
+// the device sees it.
+class PinnedBuffer {
+public:
+	explicit PinnedBuffer(unsigned flags = hipHostMallocDefault) : flags_(flags) {}
+	PinnedBuffer(const PinnedBuffer &) = delete;       // (nothing copies or moves one)
+	PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+	~PinnedBuffer() { release(); }
+	char *get() const { return p_; }
+	char *dev() const { return dev_; }
+	size_t cap() const { return cap_; }
+	bool fit(size_t bytes) { return bytes <= cap_ || regrow(bytes); }
+	void release() { if (p_) scratch_free(p_, true); p_ = dev_ = nullptr; cap_ = 0; }
+private:
+	bool regrow(size_t bytes)
+	{
+		const size_t want = grown_bytes(bytes, 1);
+		p_ = (char *) pinned_regrow(p_, want, flags_);
+		dev_ = nullptr; cap_ = 0;
+		if (p_ && (flags_ & hipHostMallocMapped) && !(dev_ = (char *) scratch_dev_pointer(p_))) release();
+		if (p_) cap_ = want;
+		return p_ != nullptr;
+	}
+	char *p_ = nullptr, *dev_ = nullptr;
+	size_t cap_ = 0;
+	unsigned flags_;
+};
+
 // ---- per-process context (one process drives one GPU) -----------------------------------
 struct Context {
 	int device = -1;
 	hipStream_t own_stream = nullptr;
 	hipStream_t stream = nullptr;     // stream every launch goes to (own_stream unless overridden)
 	int num_cus = 256;
-	// grow-only scratch: device workspace and pinned host staging
-	void *d_ws = nullptr;   size_t d_ws_bytes = 0;
-	void *h_pin = nullptr;  size_t h_pin_bytes = 0;
-	void *d_mask = nullptr; size_t d_mask_bytes = 0;
+	// grow-only scratch of the process: device workspace, packed bootstrap masks, pinned host staging
+	DeviceBuffer<char> d_ws, d_mask;
+	PinnedBuffer h_pin;
+	// staging of mdns_region_count_polled: pinned + mapped; its ticket (one int, zero between launches)
+	PinnedBuffer count_stage{hipHostMallocMapped};
+	DeviceBuffer<int> count_ticket;
+	// partial sums of squares and tickets of launch_gauss_model_tsq's shared tiles (the tickets zero between launches)
+	DeviceBuffer<double> tsq_part;
+	DeviceBuffer<int> tsq_tickets;
+	DeviceBuffer<unsigned> fold_tickets;       // of the folded K6 merge (mdns_neighbors.hip), zero between launches
+	DeviceBuffer<double> mfma_zeros;           // 16 zeros for k_gauss_mfma_direct (mdns_chunk.hip)
+	// stream-K form of the K2 matrix-core filter (mdns_k2gemm.hip): scratch tiles and delivery counts, zero whenever
+	// no launch is in flight; tiled templates; 64 zeros
+	DeviceBuffer<double> sk_scratch, sk_templ, sk_zeros;
+	DeviceBuffer<unsigned> sk_delivered;
 };
 // nullptr (and mdns_last_error set) when no device can be initialised
 Context *ctx();
@@ -65,14 +153,14 @@ struct mdns_spectra {
 	double *d_ysq = nullptr; // [ndata] sum of squares of every spectrum (K1 accept filter), or nullptr
 	double *d_yG = nullptr;  // K1 on the matrix cores with operands straight from memory (k_gauss_gemm_filter): the spectra in
 	                         // tiles of 16 rows, channel pair by channel pair (tiled16_at), channels padded to 16; or nullptr
-	double *d_selG = nullptr; size_t selG_cap = 0;     // the same of the current selection
-	double *d_model_g = nullptr; size_t model_g_cap = 0;   // templates in the same tiling
+	mdns::DeviceBuffer<double> d_selG;                 // the same of the current selection
+	mdns::DeviceBuffer<double> d_model_g;              // templates in the same tiling
 	// per-handle grow-only device buffers for the host-pointer batch API
-	double *d_model = nullptr; size_t model_cap = 0;   // [B, ldm]
-	double *d_params = nullptr; size_t params_cap = 0;
-	int *d_rows = nullptr; size_t rows_cap = 0;
-	double *d_out = nullptr; size_t out_cap = 0;
-	double *d_sel = nullptr; size_t sel_cap = 0;       // compact replica of the current selection (K1 lane kernel)
+	mdns::DeviceBuffer<double> d_model;                // [B, ldm]
+	mdns::DeviceBuffer<double> d_params;
+	mdns::DeviceBuffer<int> d_rows;
+	mdns::DeviceBuffer<double> d_out;
+	mdns::DeviceBuffer<double> d_sel;                  // compact replica of the current selection (K1 lane kernel)
 	// K2 on the matrix cores (mdns_k2gemm.hip), made on first use: y w and w [ndata, ldf] with ldf = nx rounded
 	// up to 16 (zero padded; d_fw is d_w itself when the strides agree), A = sum y^2 w [ndata]
 	double *d_fyw = nullptr, *d_fw = nullptr, *d_fa = nullptr;

@@ -381,7 +381,7 @@ struct mdns_joint {
 	double *d_Lmin = nullptr;          // [ndata] by position in the running list
 	int *d_argmin_run = nullptr;       // [ndata] by position in the running list
 	int *d_argmin = nullptr;           // [ndata] by data set
-	unsigned long long *d_keep = nullptr;  size_t keep_cap = 0;
+	DeviceBuffer<unsigned long long> d_keep;
 	int *d_status = nullptr;           // sticky failure bits of advance
 	// one allocation: accept flags | header | fill bits | likelihood row  (the model kernel of a
 	// chunk clears flags + header; header onward is what the host reads)
@@ -393,14 +393,13 @@ struct mdns_joint {
 	unsigned long long box_seq = 0;
 	bool box_pending = false;          // a commit was launched whose mailbox has not been read
 	// the trail of the accept pass (JointTrail): grown to candidates x tiles of the largest chunk
-	int *d_trail_stamp = nullptr;  unsigned long long *d_trail_word = nullptr;  double *d_trail_L = nullptr;
-	size_t trail_cap = 0;              // entries (candidate, tile)
+	DeviceBuffer<int> d_trail_stamp;  DeviceBuffer<unsigned long long> d_trail_word;  DeviceBuffer<double> d_trail_L;
 	int trail_stamp = 0;
 	bool trail_valid = false;          // the last score left a trail for its chunk
 	// staging of the host-pointer draw
 	double *d_params = nullptr;
 	int *d_rows = nullptr;             // inside d_params' block, behind the candidates
-	char *h_pin = nullptr;  size_t pin_bytes = 0;
+	PinnedBuffer h_pin;
 	// what the last score launched with (commit uses the same spectra replica and templates)
 	const double *last_yT = nullptr;
 	const int *last_gather = nullptr;
@@ -421,11 +420,11 @@ struct mdns_joint {
 	bool counted = false;              // this state is in the spectra's njoint (the model is fixed while it lives)
 	double *d_msq = nullptr;                                // templates' sums of squares (guarded accept filter, kind 0)
 	int *d_filter_scratch = nullptr;                        // matrix-core filter: ambiguous marks
-	double *d_dense = nullptr;  size_t dense_cap = 0;       // L[B, M] of a chunk (kind 1)
-	double *d_jitter = nullptr;  size_t jitter_cap = 0;
-	double *d_curves = nullptr;  size_t curves_cap = 0;     // model curves of a chunk that came as a host array
+	DeviceBuffer<double> d_dense;                           // L[B, M] of a chunk (kind 1)
+	DeviceBuffer<double> d_jitter;
+	DeviceBuffer<double> d_curves;                          // model curves of a chunk that came as a host array
 	// the draw in progress through the mdns_backend_* entry points: its selection, uploaded once
-	int *d_sel_rows = nullptr;  size_t sel_rows_cap = 0;
+	DeviceBuffer<int> d_sel_rows;
 	bool sel_rows = false;
 	int sel_M = 0;
 	bool sel_open = false;
@@ -474,11 +473,10 @@ extern "C" void mdns_joint_destroy(mdns_joint *j)
 	if (c) (void) hipStreamSynchronize(c->stream);
 	if (j->s && j->counted) j->s->njoint--;
 	void *bufs[] = {j->st.live, j->st.shelfL, j->st.shelfn, j->st.higher, j->d_running, j->d_Lmin, j->d_argmin_run,
-	                j->d_argmin, j->d_keep, j->d_status, j->d_flags, j->d_params, j->d_sel_rows, j->d_dense, j->d_msq,
-	                j->d_filter_scratch, j->d_jitter, j->d_curves, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket,
-	                j->d_commit_ticket, j->d_votes, j->d_band, j->d_bound, j->d_trail_stamp, j->d_trail_word, j->d_trail_L};
+	                j->d_argmin, j->d_status, j->d_flags, j->d_params, j->d_msq, j->d_filter_scratch, j->d_chain_props,
+	                j->d_chain_counts, j->d_chain_ticket, j->d_commit_ticket, j->d_votes, j->d_band, j->d_bound};
 	for (void *b : bufs) if (b) (void) hipFree(b);
-	void *pinned[] = {j->h_in, j->h_chain, j->h_band, j->h_box, j->h_pin};
+	void *pinned[] = {j->h_in, j->h_chain, j->h_band, j->h_box};
 	for (void *b : pinned) if (b) (void) hipHostFree(b);
 	delete j;
 }
@@ -535,17 +533,6 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	return j;
 }
 
-static char *joint_pin(mdns_joint *j, size_t bytes)
-{
-	if (bytes <= j->pin_bytes) return j->h_pin;
-	Context *c = ctx();
-	if (j->h_pin) { (void) hipStreamSynchronize(c->stream); (void) hipHostFree(j->h_pin); j->h_pin = nullptr; j->pin_bytes = 0; }
-	const size_t want = bytes + bytes / 2 + 4096;
-	if (!MDNS_HIP(hipHostMalloc((void **) &j->h_pin, want, hipHostMallocDefault))) return nullptr;
-	j->pin_bytes = want;
-	return j->h_pin;
-}
-
 extern "C" int mdns_joint_shelf_cap(const mdns_joint *j) { return j ? j->cap : -1; }
 extern "C" int mdns_joint_keep_words(const mdns_joint *j) { return j ? keep_words_of(j->cap) : -1; }
 
@@ -583,8 +570,8 @@ extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double
 	if (!c || !j || !params) return 1;
 	if (j->kind != 0) { set_error("mdns_joint_init_gauss: these spectra carry variances (mdns_joint_init_muse3)"); return 1; }
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_gauss: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
-	char *pin = joint_pin(j, (size_t) j->nlive * 24);
-	if (!pin) return 1;
+	if (!j->h_pin.fit((size_t) j->nlive * 24)) return 1;
+	char *pin = j->h_pin.get();
 	j->noise_level = noise_level;
 	memcpy(pin, params, (size_t) j->nlive * 24);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, (size_t) j->nlive * 24, hipMemcpyHostToDevice, c->stream))) return 1;
@@ -594,17 +581,6 @@ extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double
 	return joint_sync(c) ? 0 : 1;
 }
 
-static bool joint_grow(double **p, size_t *cap, size_t need)
-{
-	if (need <= *cap) return true;
-	Context *c = ctx();
-	if (*p) { (void) hipStreamSynchronize(c->stream); (void) hipFree(*p); *p = nullptr; *cap = 0; }
-	const size_t n = need + need / 2 + 1024;
-	if (!MDNS_HIP(hipMalloc((void **) p, n * sizeof(double)))) return false;
-	*cap = n;
-	return true;
-}
-
 extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter)
 {
 	Context *c = ctx();
@@ -612,16 +588,16 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 	if (j->kind != 1) { set_error("mdns_joint_init_muse3: the spectra carry no variances"); return 1; }
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_muse3: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
 	const size_t pbytes = (size_t) j->nlive * j->nparams * sizeof(double), n = (size_t) j->nlive * j->ndata;
-	char *pin = joint_pin(j, pbytes);
-	if (!pin) return 1;
+	if (!j->h_pin.fit(pbytes)) return 1;
+	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	if (mdns_lines_loglike_batch_dev(j->s, j->d_params, j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
 	if (jitter) {
 		// (musefuse.py:535 adds its noise to the initial points' likelihoods too)
-		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter, n);
+		if (!j->d_jitter.fit(n)) return 1;
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter.get(), n);
 		if (!MDNS_HIP(hipGetLastError())) return 1;
 	}
 	if (joint_reset(j) != 0) return 1;
@@ -636,8 +612,8 @@ static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, 
 	mdns_spectra *s = j->s;
 	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
-	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model, ldm) &&
-	       launch_muse_rows(s, s->d_model, ldm, B, d_rows, M, d_out);
+	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
+	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);
 }
 
 extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter)
@@ -648,13 +624,13 @@ extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, doubl
 	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
 	const size_t n = (size_t) j->nlive * j->ndata;
 	if (j->kind == 0) j->noise_level = noise_level;
-	if (!joint_grow(&j->d_curves, &j->curves_cap, (size_t) j->nlive * nx)) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves, curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (!curves_score(j, j->d_curves, nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
+	if (!j->d_curves.fit((size_t) j->nlive * nx)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!curves_score(j, j->d_curves.get(), nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
 	if (jitter) {
-		if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter, n);
+		if (!j->d_jitter.fit(n)) return 1;
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter.get(), n);
 		if (!MDNS_HIP(hipGetLastError())) return 1;
 	}
 	if (joint_reset(j) != 0) return 1;
@@ -729,17 +705,11 @@ extern "C" int mdns_joint_prepare_dev(mdns_joint *j)
 	Context *c = ctx();
 	if (!c || !j) return 1;
 	const int kw = keep_words_of(j->cap);
-	const size_t need = (size_t) (j->nrun > 0 ? j->nrun : 1) * kw;
-	if (need > j->keep_cap) {
-		if (j->d_keep) { (void) hipStreamSynchronize(c->stream); (void) hipFree(j->d_keep); j->d_keep = nullptr; j->keep_cap = 0; }
-		const size_t want = (size_t) j->ndata * kw;
-		if (!MDNS_HIP(hipMalloc((void **) &j->d_keep, want * sizeof(unsigned long long)))) return 1;
-		j->keep_cap = want;
-	}
+	if (!j->d_keep.fit((size_t) j->ndata * kw)) return 1;              // (room for every data set: no growth as the running list changes)
 	j->prepared = true;
 	if (j->nrun == 0) return 0;
 	hipLaunchKernelGGL(k_joint_prepare, dim3((j->nrun + 15) / 16), dim3(kBlock), 0, c->stream,
-	                   j->st, j->d_running, j->nrun, j->d_Lmin, j->d_argmin_run, j->d_argmin, j->d_keep, kw);
+	                   j->st, j->d_running, j->nrun, j->d_Lmin, j->d_argmin_run, j->d_argmin, j->d_keep.get(), kw);
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -752,11 +722,11 @@ extern "C" int mdns_joint_prepare(mdns_joint *j, double *Lmin, int *argmin, unsi
 	if (n == 0) return 0;
 	// one pinned block, three copies, one wait
 	const size_t o1 = n * 8, o2 = o1 + ((n * 4 + 7) & ~(size_t) 7);
-	char *pin = joint_pin(j, o2 + n * kw * 8);
-	if (!pin) return 1;
+	if (!j->h_pin.fit(o2 + n * kw * 8)) return 1;
+	char *pin = j->h_pin.get();
 	if (!MDNS_HIP(hipMemcpyAsync(pin, j->d_Lmin, n * 8, hipMemcpyDeviceToHost, c->stream)) ||
 	    !MDNS_HIP(hipMemcpyAsync(pin + o1, j->d_argmin_run, n * 4, hipMemcpyDeviceToHost, c->stream)) ||
-	    !MDNS_HIP(hipMemcpyAsync(pin + o2, j->d_keep, n * kw * 8, hipMemcpyDeviceToHost, c->stream)) ||
+	    !MDNS_HIP(hipMemcpyAsync(pin + o2, j->d_keep.get(), n * kw * 8, hipMemcpyDeviceToHost, c->stream)) ||
 	    !joint_sync(c)) return 1;
 	if (Lmin) memcpy(Lmin, pin, n * 8);
 	if (argmin) memcpy(argmin, pin + o1, n * 4);
@@ -803,24 +773,17 @@ static bool joint_trail(mdns_joint *j, int B, int M, JointTrail *out)
 {
 	Context *c = ctx();
 	const size_t need = (size_t) B * ((M + 63) / 64);
-	if (need > j->trail_cap) {
-		(void) hipStreamSynchronize(c->stream);
-		void *old[] = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L};
-		for (void *b : old) if (b) (void) hipFree(b);
-		j->d_trail_stamp = nullptr; j->d_trail_word = nullptr; j->d_trail_L = nullptr; j->trail_cap = 0;
-		const size_t cap = need + need / 2 + 1024;
-		if (!MDNS_HIP(hipMalloc((void **) &j->d_trail_stamp, cap * sizeof(int))) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_trail_word, cap * sizeof(unsigned long long))) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_trail_L, cap * 64 * sizeof(double))) ||
-		    !MDNS_HIP(hipMemsetAsync(j->d_trail_stamp, 0, cap * sizeof(int), c->stream))) return false;
-		j->trail_cap = cap;
-		j->trail_stamp = 0;
-	}
+	const size_t had = j->d_trail_stamp.cap();
+	if (!j->d_trail_stamp.fit_zeroed(need)) { j->trail_valid = false; return false; }
+	if (j->d_trail_stamp.cap() != had) j->trail_stamp = 0;             // fresh stamps are zero: so is the count
+	// (words and likelihoods may grow when the stamps do not: an entry is read only under the stamp issued below, by the
+	// commit of THIS score, and a growth drains the stream first -- no stamp of an earlier block is ever matched)
+	if (!j->d_trail_word.fit(need) || !j->d_trail_L.fit(need * 64)) { j->trail_valid = false; return false; }
 	if (j->trail_stamp == 0x7fffffff) {                                 // stamps start over
-		if (!MDNS_HIP(hipMemsetAsync(j->d_trail_stamp, 0, j->trail_cap * sizeof(int), c->stream))) return false;
+		if (!MDNS_HIP(hipMemsetAsync(j->d_trail_stamp.get(), 0, j->d_trail_stamp.cap() * sizeof(int), c->stream))) return false;
 		j->trail_stamp = 0;
 	}
-	out->stamp_of = j->d_trail_stamp; out->word = j->d_trail_word; out->L = j->d_trail_L;
+	out->stamp_of = j->d_trail_stamp.get(); out->word = j->d_trail_word.get(); out->L = j->d_trail_L.get();
 	out->stamp = ++j->trail_stamp;
 	return true;
 }
@@ -875,17 +838,12 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 			    !launch_tile_rows16(s->d_y, s->ld, s->ndata, s->nx, nullptr, s->d_yG)) return 1;
 		}
 		if (filter == 2 && gauss_mfma_form() == 2 && (d_row_ids || s->d_yG)) {
-			const size_t need = (size_t) ((B + 15) / 16) * 16 * tiled16_nx(s->nx);
-			if (need > s->model_g_cap) {
-				if (s->d_model_g) { if (!joint_sync(c)) return 1; (void) hipFree(s->d_model_g); s->d_model_g = nullptr; s->model_g_cap = 0; }
-				if (!MDNS_HIP(hipMalloc((void **) &s->d_model_g, (need + need / 2) * sizeof(double)))) return 1;
-				s->model_g_cap = need + need / 2;
-			}
-			model_g = s->d_model_g;
+			if (!s->d_model_g.fit((size_t) ((B + 15) / 16) * 16 * tiled16_nx(s->nx))) return 1;
+			model_g = s->d_model_g.get();
 		}
-		if (!launch_gauss_model_tsq(s->d_x, s->nx, d_params, B, bt, s->d_model, j->d_msq, j->d_flags, kZeroInts, model_g)) return 1;
+		if (!launch_gauss_model_tsq(s->d_x, s->nx, d_params, B, bt, s->d_model.get(), j->d_msq, j->d_flags, kZeroInts, model_g)) return 1;
 		gemm_form = model_g != nullptr;
-	} else if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model, j->d_flags, kZeroInts)) return 1;
+	} else if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model.get(), j->d_flags, kZeroInts)) return 1;
 	const double *yT = s->d_yT;
 	const int *gather = d_row_ids;
 	// a sparse selection, or many candidate tiles over a selection: first a compact replica of
@@ -894,32 +852,27 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 	const double *yG = s->d_yG;
 	if (d_row_ids && gemm_form) {
 		// (its own compact replica of the selection, in its tiling)
-		const size_t need = (size_t) ((M + 15) / 16) * 16 * tiled16_nx(s->nx);
-		if (need > s->selG_cap) {
-			if (s->d_selG) { if (!joint_sync(c)) return 1; (void) hipFree(s->d_selG); s->d_selG = nullptr; s->selG_cap = 0; }
-			if (!MDNS_HIP(hipMalloc((void **) &s->d_selG, (need + need / 2) * sizeof(double)))) return 1;
-			s->selG_cap = need + need / 2;
-		}
-		if (!launch_tile_rows16(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_selG)) return 1;
-		yG = s->d_selG;
+		if (!s->d_selG.fit((size_t) ((M + 15) / 16) * 16 * tiled16_nx(s->nx))) return 1;
+		if (!launch_tile_rows16(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_selG.get())) return 1;
+		yG = s->d_selG.get();
 	} else if (d_row_ids && (B >= 128 || sparse || filter == 2)) {
 		if (!ensure_selection(s, (size_t) ((M + 63) / 64) * 64 * cols_nx(s->nx))) return 1;
-		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel)) return 1;
-		yT = s->d_sel;
+		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
+		yT = s->d_sel.get();
 		gather = nullptr;
 	}
 	JointTrail trail;
 	if (!joint_trail(j, B, M, &trail)) return 1;
 	if (filter == 2) {
 		int *lowest = (int *) &((JointHeader *) j->d_result)->pad;
-		if (!launch_gauss_mfma_filter(s, yT, s->d_model, B, scale, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest,
-		                              j->d_filter_scratch, j->d_result, gemm_form ? yG : nullptr, gemm_form ? s->d_model_g : nullptr)) return 1;
+		if (!launch_gauss_mfma_filter(s, yT, s->d_model.get(), B, scale, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest,
+		                              j->d_filter_scratch, j->d_result, gemm_form ? yG : nullptr, gemm_form ? s->d_model_g.get() : nullptr)) return 1;
 	} else if (filter) {
 		// issue-bound launch: the guarded filter decides -- same flags and trail, bit for bit.  Its
 		// "lowest flagged candidate so far" lives in the header's spare word (cleared with the flags).
 		int *lowest = (int *) &((JointHeader *) j->d_result)->pad;
-		if (!launch_gauss_cols_filter(s, yT, s->d_model, bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest)) return 1;
-	} else if (!launch_gauss_cols_accept(s, yT, s->d_model, bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, trail)) return 1;
+		if (!launch_gauss_cols_filter(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest)) return 1;
+	} else if (!launch_gauss_cols_accept(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, trail)) return 1;
 	j->trail_valid = true;
 	j->last_yT = yT; j->last_gather = gather; j->last_bt = bt; j->last_B = B; j->last_scale = scale;
 	j->scored_M = M;
@@ -951,7 +904,7 @@ static void launch_publish(mdns_joint *j, Context *c, int M)
 // one_group: the pass was the two-launch chunk's, whose single-workgroup commit takes a selection of a tile or two
 static bool commit_from_trail(mdns_joint *j, const int *thr_rows, int M, int B, const int *decides, int value, bool one_group)
 {
-	const JointTrail trail = {j->d_trail_stamp, j->d_trail_word, j->d_trail_L, j->trail_stamp};
+	const JointTrail trail = {j->d_trail_stamp.get(), j->d_trail_word.get(), j->d_trail_L.get(), j->trail_stamp};
 	if (one_group && M <= 128) {
 		// a tile or two: shelf appends, thresholds and the mailbox in ONE workgroup
 		return launch_chunk_commit(thr_rows, M, B, decides, value, trail, j->st, j->d_result, result_bits(j), j->h_box_dev, ++j->box_seq);
@@ -987,7 +940,7 @@ static int joint_commit_dev(mdns_joint *j, const int *d_row_ids, int M, bool wan
 		if (!commit_from_trail(j, d_row_ids, M, j->last_B, j->d_flags, 1, false)) return 1;
 	} else {
 		double *Lrow = (double *) (j->d_result + sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8);
-		if (!launch_gauss_cols_commit(j->s, j->last_yT, j->s->d_model, j->last_bt, j->last_B, j->last_scale, j->last_gather,
+		if (!launch_gauss_cols_commit(j->s, j->last_yT, j->s->d_model.get(), j->last_bt, j->last_B, j->last_scale, j->last_gather,
 		                              d_row_ids, M, j->d_flags, j->st, j->d_result, result_bits(j), Lrow)) return 1;
 		launch_publish(j, c, M);
 	}
@@ -1060,8 +1013,8 @@ static int joint_stage_and_score(mdns_joint *j, const double *params, int B, dou
 	// candidates and selection travel together: one pinned block, one copy
 	const size_t pbytes = (size_t) B * 24, rbytes = row_ids ? (size_t) M * 4 : 0;
 	const size_t in_bytes = (pbytes + rbytes + 15) & ~(size_t) 15;
-	char *pin = joint_pin(j, in_bytes + result_bytes(j->ndata));
-	if (!pin) return 1;
+	if (!j->h_pin.fit(in_bytes + result_bytes(j->ndata))) return 1;
+	char *pin = j->h_pin.get();
 	if (pbytes) memcpy(pin, params, pbytes);
 	if (rbytes) memcpy(pin + pbytes, row_ids, rbytes);
 	if (pbytes + rbytes &&
@@ -1089,7 +1042,7 @@ static int joint_commit_and_fetch(mdns_joint *j, int *accepted, double *Lrow, un
 	// the header says whether the rest matters, but one copy of at most 80 KB costs less than a
 	// second round trip; a caller that does not ask for the likelihood row gets header + bits
 	const size_t out_bytes = Lrow ? result_bytes(M) : sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8;
-	char *out = j->h_pin + j->staged_in_bytes;
+	char *out = j->h_pin.get() + j->staged_in_bytes;
 	if (!MDNS_HIP(hipMemcpyAsync(out, j->d_result, out_bytes, hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c)) return 1;
 	const JointHeader *h = (const JointHeader *) out;
 	if (h->status) { status_error(who, h->status, j->cap); return 1; }
@@ -1181,10 +1134,7 @@ extern "C" int mdns_backend_draw_begin(void *joint, const int *rows, int M)
 		if (!MDNS_HIP(hipHostMalloc((void **) &j->h_in, kInParams + (size_t) j->ndata * sizeof(int), hipHostMallocMapped)) ||
 		    !MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_in_dev, j->h_in, 0))) return 1;
 	}
-	if (!j->d_sel_rows) {
-		if (!MDNS_HIP(hipMalloc((void **) &j->d_sel_rows, (size_t) j->ndata * sizeof(int)))) return 1;
-		j->sel_rows_cap = (size_t) j->ndata;
-	}
+	if (!j->d_sel_rows.fit((size_t) j->ndata)) return 1;
 	if (rows) {
 		int *dst = (int *) (j->h_in + kInParams);
 		int prev = -1;
@@ -1211,14 +1161,14 @@ extern "C" int mdns_backend_draw_begin(void *joint, const int *rows, int M)
 // the pieces of a backend chunk: selection, chunk flag, score, commit, fetch
 // ---------------------------------------------------------------------------------------
 // the selection of the draw in progress as the kernels take it: its row ids in device memory, or nullptr for every data set
-static const int *selection_rows(const mdns_joint *j) { return j->sel_rows ? j->d_sel_rows : nullptr; }
+static const int *selection_rows(const mdns_joint *j) { return j->sel_rows ? j->d_sel_rows.get() : nullptr; }
 
 // the same, uploaded if no chunk of this draw has put it there yet
 static bool selection_to_device(mdns_joint *j, Context *c, const int **d_rows)
 {
 	if (j->sel_rows && !j->sel_on_device) {
 		// (the mapped block is pinned: a plain asynchronous copy)
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows, j->h_in + kInParams, (size_t) j->sel_M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return false;
+		if (!MDNS_HIP(hipMemcpyAsync(j->d_sel_rows.get(), j->h_in + kInParams, (size_t) j->sel_M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return false;
 		j->sel_on_device = true;
 	}
 	*d_rows = selection_rows(j);
@@ -1232,8 +1182,8 @@ static SelectionIO selection_for_accept(const mdns_joint *j)
 {
 	SelectionIO rows = {nullptr, nullptr};
 	if (j->sel_rows) {
-		if (j->sel_on_device) rows.in = j->d_sel_rows;
-		else { rows.in = (const int *) (j->h_in_dev + kInParams); rows.out = j->d_sel_rows; }
+		if (j->sel_on_device) rows.in = j->d_sel_rows.get();
+		else { rows.in = (const int *) (j->h_in_dev + kInParams); rows.out = j->d_sel_rows.get(); }
 	}
 	return rows;
 }
@@ -1259,23 +1209,23 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 	if (j->kind == 1) {
 		// templates + K2 into the dense block, jitter, accept flags
 		const size_t pbytes = (size_t) B * j->nparams * sizeof(double), n = (size_t) B * M;
-		char *pin = joint_pin(j, pbytes);
-		if (!pin) return 1;
+		if (!j->h_pin.fit(pbytes)) return 1;
+		char *pin = j->h_pin.get();
 		memcpy(pin, params, pbytes);
 		if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 		const int *d_rows;
 		if (!selection_to_device(j, c, &d_rows)) return 1;
-		if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
+		if (!j->d_dense.fit(n)) return 1;
 		if (jitter) {
-			if (!joint_grow(&j->d_jitter, &j->jitter_cap, n)) return 1;
+			if (!j->d_jitter.fit(n)) return 1;
 			// (pageable source: the runtime stages it and returns when the caller's buffer is free)
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 		}
-		if (mdns_lines_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense) != 0) return 1;
+		if (mdns_lines_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense.get()) != 0) return 1;
 		const int flag = next_chunk_flag(j, c);
 		if (!flag) return 1;
 		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-		                   j->d_dense, jitter ? (const double *) j->d_jitter : nullptr, B, M, d_rows, (const double *) j->st.higher,
+		                   j->d_dense.get(), jitter ? (const double *) j->d_jitter.get() : nullptr, B, M, d_rows, (const double *) j->st.higher,
 		                   j->d_flags, flag, (JointHeader *) j->d_result);
 		out->path = 1; out->flag = flag;
 		return 0;
@@ -1299,8 +1249,8 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 		out->path = 2; out->flag = flag;
 		return 0;
 	}
-	char *pin = joint_pin(j, pbytes);
-	if (!pin) return 1;
+	if (!j->h_pin.fit(pbytes)) return 1;
+	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	const int *d_rows;
@@ -1320,7 +1270,7 @@ static int backend_commit(mdns_joint *j, Context *c, const ChunkScore &sc, const
 	if (sc.path == 1) {
 		const int ntiles = (M + 63) / 64;
 		hipLaunchKernelGGL(k_joint_commit_dense, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-		                   (const double *) j->d_dense, thr_rows, M, sc.B, ntiles, decides, value, j->st, (JointHeader *) j->d_result, result_bits(j));
+		                   (const double *) j->d_dense.get(), thr_rows, M, sc.B, ntiles, decides, value, j->st, (JointHeader *) j->d_result, result_bits(j));
 		launch_publish(j, c, M);
 		if (!MDNS_HIP(hipGetLastError())) return 1;
 	} else if (sc.path == 2) {
@@ -1374,12 +1324,12 @@ static int draw_curves_dev(mdns_joint *j, Context *c, const double *d_curves, in
 	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;
-	if (!joint_grow(&j->d_dense, &j->dense_cap, (size_t) B * M)) return 1;
-	if (!curves_score(j, d_curves, ldc, B, d_rows, M, j->d_dense)) return 1;
+	if (!j->d_dense.fit((size_t) B * M)) return 1;
+	if (!curves_score(j, d_curves, ldc, B, d_rows, M, j->d_dense.get())) return 1;
 	const int flag = next_chunk_flag(j, c);
 	if (!flag) return 1;
 	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-	                   j->d_dense, d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags, flag, (JointHeader *) j->d_result);
+	                   j->d_dense.get(), d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags, flag, (JointHeader *) j->d_result);
 	const ChunkScore sc = {1, B, flag};
 	if (backend_commit(j, c, sc, j->d_flags, flag, who) != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
@@ -1419,11 +1369,11 @@ extern "C" int mdns_backend_draw_curves(void *joint, const double *curves, int B
 	if (rc != 0) return rc > 0;
 	const size_t nc = (size_t) B * nx, n = (size_t) B * j->sel_M;
 	// (pageable sources: the runtime stages them and returns when the caller's buffers are free)
-	if (!joint_grow(&j->d_curves, &j->curves_cap, nc) ||
-	    !MDNS_HIP(hipMemcpyAsync(j->d_curves, curves, nc * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (jitter && (!joint_grow(&j->d_jitter, &j->jitter_cap, n) ||
-	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter, jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
-	return draw_curves_dev(j, c, j->d_curves, nx, B, jitter ? j->d_jitter : nullptr, accepted, fillbits, "mdns_backend_draw_curves");
+	if (!j->d_curves.fit(nc) ||
+	    !MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, nc * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (jitter && (!j->d_jitter.fit(n) ||
+	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
+	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, jitter ? j->d_jitter.get() : nullptr, accepted, fillbits, "mdns_backend_draw_curves");
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,
@@ -1633,19 +1583,19 @@ static int band_launch(mdns_joint *j, bool filtered)
 	const double *d_p = j->d_bound, *d_b = j->d_bound + (size_t) B * j->nparams;
 	if (filtered) {
 		const int ldm = model_ld(j->s->nx) + 16;            // (not a power of two: mdns_k2gemm.hip, muse_filter_ld)
-		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model, ldm)) return 1;
+		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;
 		const MuseBandOut out = {&j->d_band->counter, j->d_band->clear, j->d_band->maybe, j->d_band->pair_b, j->d_band->pair_k,
 		                         j->d_band->pair_L, j->d_band->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
-		if (!launch_muse_filter(j->s, j->s->d_model, ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
+		if (!launch_muse_filter(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
 	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w && j->s->d_x) {
 		// small chunks (pairs of candidates per workgroup): templates, then ONE kernel that scores, votes and publishes
 		const int ldm = model_ld(j->s->nx);
-		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model, ldm)) return 1;
+		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;
 		const MuseBandFused fused = {j->d_band, j->h_band_dev, ++j->band_seq, j->st.higher, d_b, &((JointHeader *) j->d_result)->status};
-		if (!launch_muse_rows(j->s, j->s->d_model, ldm, B, d_rows, M, j->d_dense, 0, &fused)) return 1;
+		if (!launch_muse_rows(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->d_dense.get(), 0, &fused)) return 1;
 	} else {
-		if (mdns_lines_loglike_batch_dev(j->s, d_p, B, d_rows, M, j->d_dense) != 0) return 1;
-		hipLaunchKernelGGL(k_joint_band, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream, (const double *) j->d_dense,
+		if (mdns_lines_loglike_batch_dev(j->s, d_p, B, d_rows, M, j->d_dense.get()) != 0) return 1;
+		hipLaunchKernelGGL(k_joint_band, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream, (const double *) j->d_dense.get(),
 		                   d_b, B, M, d_rows, (const double *) j->st.higher, j->d_band, (JointHeader *) j->d_result, j->h_band_dev, ++j->band_seq);
 	}
 	if (filtered) hipLaunchKernelGGL(k_joint_band_publish, dim3(1), dim3(kBlock), 0, c->stream, j->d_band, B, j->h_band_dev, ++j->band_seq);
@@ -1676,14 +1626,14 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 	}
 	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
 	const size_t pbytes = (size_t) B * j->nparams * sizeof(double), bbytes = (size_t) B * sizeof(double), n = (size_t) B * M;
-	char *pin = joint_pin(j, pbytes + bbytes);
-	if (!pin) return 1;
+	if (!j->h_pin.fit(pbytes + bbytes)) return 1;
+	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
 	memcpy(pin + pbytes, bound, bbytes);
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_bound, pin, pbytes + bbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;              // (band_launch takes it from the handle)
-	if (!joint_grow(&j->d_dense, &j->dense_cap, n)) return 1;
+	if (!j->d_dense.fit(n)) return 1;
 	j->band_B = B;
 	j->trail_valid = false;
 	j->last_B = 0;
@@ -1755,18 +1705,18 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 		const int ldm = model_ld(j->s->nx) + 16, Bc = j->band_B;
 		const int lo = muse_rows_variant(Bc, M) == 1 ? (b & ~1) : b;
 		const int nb = lo == b && muse_rows_variant(Bc, M) != 1 ? 1 : (Bc - lo < 2 ? Bc - lo : 2);
-		if (!launch_muse_rows(j->s, j->s->d_model + (size_t) lo * ldm, ldm, nb, d_rows, M,
-		                      j->d_dense + (size_t) lo * M, Bc)) return 1;
+		if (!launch_muse_rows(j->s, j->s->d_model.get() + (size_t) lo * ldm, ldm, nb, d_rows, M,
+		                      j->d_dense.get() + (size_t) lo * M, Bc)) return 1;
 		muse_filter_note(2);
 	}
 	j->band_B = 0;
 	double *d_row = j->d_bound + kBandRowAt;
-	char *pin = joint_pin(j, (size_t) M * sizeof(double));
-	if (!pin) return 1;
+	if (!j->h_pin.fit((size_t) M * sizeof(double))) return 1;
+	char *pin = j->h_pin.get();
 	memcpy(pin, jitter_row, (size_t) M * sizeof(double));
 	if (!MDNS_HIP(hipMemcpyAsync(d_row, pin, (size_t) M * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 	hipLaunchKernelGGL(k_joint_commit_band, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-	                   (const double *) j->d_dense, (const double *) d_row, d_rows, M, b, ntiles, j->st, (JointHeader *) j->d_result, result_bits(j));
+	                   (const double *) j->d_dense.get(), (const double *) d_row, d_rows, M, b, ntiles, j->st, (JointHeader *) j->d_result, result_bits(j));
 	launch_publish(j, c, M);
 	if (!MDNS_HIP(hipGetLastError())) return 1;
 	j->box_pending = true;

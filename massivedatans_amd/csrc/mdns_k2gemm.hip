@@ -338,32 +338,10 @@ __global__ __launch_bounds__(512) void k_muse_gemm_band_sk(
 	}
 }
 
-// scratch tiles and delivery counts of the stream-K form: grow-only, zero whenever no launch is in flight
-static double *g_sk_scratch = nullptr, *g_sk_zeros = nullptr, *g_sk_templ = nullptr;
-static size_t g_sk_templ_cap = 0;
-static unsigned *g_sk_delivered = nullptr;
-static size_t g_sk_tiles = 0, g_sk_doubles = 0;
-
-static bool sk_reserve(size_t tiles, size_t doubles)
+// scratch tiles and delivery counts of the stream-K form (Context): zero whenever no launch is in flight; the zeros never grow
+static bool sk_reserve(Context *c, size_t tiles, size_t doubles)
 {
-	Context *c = ctx();
-	if (!g_sk_zeros && (!MDNS_HIP(hipMalloc((void **) &g_sk_zeros, 64 * sizeof(double))) ||
-	                    !MDNS_HIP(hipMemsetAsync(g_sk_zeros, 0, 64 * sizeof(double), c->stream)))) return false;
-	if (tiles > g_sk_tiles) {
-		if (g_sk_delivered) { (void) hipStreamSynchronize(c->stream); (void) hipFree(g_sk_delivered); g_sk_delivered = nullptr; g_sk_tiles = 0; }
-		const size_t want = tiles + tiles / 2 + 64;
-		if (!MDNS_HIP(hipMalloc((void **) &g_sk_delivered, want * sizeof(unsigned))) ||
-		    !MDNS_HIP(hipMemsetAsync(g_sk_delivered, 0, want * sizeof(unsigned), c->stream))) return false;
-		g_sk_tiles = want;
-	}
-	if (doubles > g_sk_doubles) {
-		if (g_sk_scratch) { (void) hipStreamSynchronize(c->stream); (void) hipFree(g_sk_scratch); g_sk_scratch = nullptr; g_sk_doubles = 0; }
-		const size_t want = doubles + doubles / 2;
-		if (!MDNS_HIP(hipMalloc((void **) &g_sk_scratch, want * sizeof(double))) ||
-		    !MDNS_HIP(hipMemsetAsync(g_sk_scratch, 0, want * sizeof(double), c->stream))) return false;
-		g_sk_doubles = want;
-	}
-	return true;
+	return c->sk_zeros.fit_zeroed(64) && c->sk_delivered.fit_zeroed(tiles) && c->sk_scratch.fit_zeroed(doubles);
 }
 
 static long long g_filter_stats[4];        // chunks filtered | scored again exactly | exact rows for a commit | prepared handles
@@ -438,27 +416,22 @@ bool launch_muse_filter(mdns_spectra *s, const double *d_model, int ldm, int B, 
 		if (P < 1) P = 1;
 		static const char *p_forced = getenv("MDNS_K2_FILTER_P");        // experiments only; 0: one per tile
 		if (p_forced) { const long long f = atoll(p_forced); P = f > 0 ? f : tiles; }
-		if (!sk_reserve((size_t) tiles, (size_t) P * 2 * nc * 512)) return false;
+		if (!sk_reserve(c, (size_t) tiles, (size_t) P * 2 * nc * 512)) return false;
 		// the whole set of spectra in its stored order: tiled operands (every load of a quarter wave contiguous);
 		// the templates are tiled on the way (2 MB: one more small launch)
 		static const char *tiled_forced = getenv("MDNS_K2_FILTER_TILED");    // "0": row-major operands always (experiments)
 		const bool tiled = !d_rows && M == s->ndata && !(tiled_forced && tiled_forced[0] == '0');
 		const double *d_templ = d_model;
 		if (tiled) {
-			const size_t need = (size_t) bt * nc * 16 * s->ldf;
-			if (need > g_sk_templ_cap) {
-				if (g_sk_templ) { (void) hipStreamSynchronize(c->stream); (void) hipFree(g_sk_templ); g_sk_templ = nullptr; g_sk_templ_cap = 0; }
-				if (!MDNS_HIP(hipMalloc((void **) &g_sk_templ, (need + need / 2) * sizeof(double)))) return false;
-				if (!MDNS_HIP(hipMemsetAsync(g_sk_templ, 0, (need + need / 2) * sizeof(double), c->stream))) return false;
-				g_sk_templ_cap = need + need / 2;
-			}
-			hipLaunchKernelGGL(k_muse_tile_templates, dim3((s->ldf + 255) / 256, B), dim3(256), 0, c->stream, d_model, ldm, B, s->ldf, g_sk_templ);
-			d_templ = g_sk_templ;
+			// (zeroed as before: the tiling kernel writes the B templates, the rows up to the tile's 16 multiply as zeros)
+			if (!c->sk_templ.fit_zeroed((size_t) bt * nc * 16 * s->ldf)) return false;
+			hipLaunchKernelGGL(k_muse_tile_templates, dim3((s->ldf + 255) / 256, B), dim3(256), 0, c->stream, d_model, ldm, B, s->ldf, c->sk_templ.get());
+			d_templ = c->sk_templ.get();
 		}
 		note_kernel(1, tiled ? "k_muse_gemm_band_sk<%d, tiled>" : "k_muse_gemm_band_sk<%d>", nc);
 #define K2_SK(NC, T) hipLaunchKernelGGL((k_muse_gemm_band_sk<NC, T>), dim3((unsigned) P), dim3(512), 0, c->stream, \
 		(const double *) (T ? s->d_fyw_t : s->d_fyw), (const double *) (T ? s->d_fw_t : s->d_fw), s->ldf, (const double *) s->d_fa, d_templ, ldm, B, d_rows, M, bt, \
-		d_higher, d_bound, gamma, out, g_sk_scratch, g_sk_delivered, (const double *) g_sk_zeros)
+		d_higher, d_bound, gamma, out, c->sk_scratch.get(), c->sk_delivered.get(), (const double *) c->sk_zeros.get())
 		{
 			ProfileScope prof(1);
 			if (tiled) { if (nc == 4) K2_SK(4, true); else if (nc == 2) K2_SK(2, true); else K2_SK(1, true); }
@@ -498,9 +471,9 @@ extern "C" int mdns_muse_filter_dev(mdns_spectra *s, const double *d_ypred, int 
 	if (!ctx() || !s || !d_ypred || !d_thr || !d_bound || !d_out || B < 1 || M < 1 || M > s->ndata) { set_error("mdns_muse_filter_dev: bad arguments"); return 1; }
 	if (!s->d_w) { set_error("spectra were created without variances"); return 1; }
 	const int ldm = model_ld(s->nx) + 16;
-	if (!ensure_model(s, (size_t) B * ldm) || !launch_pad_model(d_ypred, s->nx, B, s->d_model, ldm)) return 1;
+	if (!ensure_model(s, (size_t) B * ldm) || !launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;
 	const MuseBandOut out = {d_out + 2 * B, d_out, d_out + B, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-	return launch_muse_filter(s, s->d_model, ldm, B, d_row_ids, M, d_thr, d_bound, out) ? 0 : 1;
+	return launch_muse_filter(s, s->d_model.get(), ldm, B, d_row_ids, M, d_thr, d_bound, out) ? 0 : 1;
 }
 
 extern "C" void mdns_muse_filter_mode(int mode) { mdns::g_filter_mode = mode == 0 || mode == 1 ? mode : -1; }

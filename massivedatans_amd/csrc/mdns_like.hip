@@ -1291,23 +1291,13 @@ bool launch_gauss_model_tsq(const double *d_x, int nx, const double *d_params, i
 	Context *c = ctx();
 	const int ntile = (B + bt - 1) / bt;
 	if (d_model_g && bt != 16) { set_error("launch_gauss_model_tsq: tiled templates come 16 candidates wide"); return false; }
-	// partial sums of squares and tickets of the shared tiles: grow-only, the tickets zero between launches
-	static double *d_part = nullptr;
-	static int *d_tickets = nullptr;
-	static int cap_tiles = 0;
 	constexpr int kShares = 4;
 	static const char *one = getenv("MDNS_TSQ_SHARES");                  // "1": one workgroup per tile (experiments)
 	const int ny = one && one[0] == '1' ? 1 : kShares;
-	if (ny > 1 && ntile > cap_tiles) {
-		if (d_part) { (void) hipStreamSynchronize(c->stream); (void) hipFree(d_part); (void) hipFree(d_tickets); d_part = nullptr; d_tickets = nullptr; cap_tiles = 0; }
-		const int cap = ntile + 64;
-		if (!MDNS_HIP(hipMalloc((void **) &d_part, (size_t) cap * kShares * 64 * sizeof(double))) ||
-		    !MDNS_HIP(hipMalloc((void **) &d_tickets, (size_t) cap * sizeof(int))) ||
-		    !MDNS_HIP(hipMemsetAsync(d_tickets, 0, (size_t) cap * sizeof(int), c->stream))) return false;
-		cap_tiles = cap;
-	}
+	// partial sums of squares and tickets of the shared tiles (the kernel indexes both by tile < ntile)
+	if (ny > 1 && (!c->tsq_part.fit((size_t) ntile * kShares * 64) || !c->tsq_tickets.fit_zeroed((size_t) ntile))) return false;
 	hipLaunchKernelGGL(k_gauss_model_tsq, dim3(ntile, ny), dim3(256), 0, c->stream, d_x, nx, cols_nx(nx), d_params, B, bt, d_model_t, d_msq,
-	                   d_zero, d_zero ? nzero : 0, d_model_g, tiled16_nx(nx), d_part, d_tickets);
+	                   d_zero, d_zero ? nzero : 0, d_model_g, tiled16_nx(nx), c->tsq_part.get(), c->tsq_tickets.get());
 	return launched("k_gauss_model_tsq");
 }
 

@@ -521,16 +521,8 @@ bool launch_bootstrap_packed(const double *d_members, int K, int ndim, const uns
 		// 26.2 / 48.1 / 107.1 against 19.1 / 22.3 / 47.6 / 106.3 -- level, so the pair stays the default.
 		static const char *merge = getenv("MDNS_K6_MERGE");
 		const bool fold = merge && !strcmp(merge, "fold");
-		static unsigned *d_tickets = nullptr;
-		static int tickets_cap = 0;
-		if (fold && (int) grid.x > tickets_cap) {
-			if (d_tickets) { (void) hipStreamSynchronize(c->stream); (void) hipFree(d_tickets); d_tickets = nullptr; }
-			const int cap = (int) grid.x + 1024;
-			if (!MDNS_HIP(hipMalloc((void **) &d_tickets, (size_t) cap * sizeof(unsigned))) ||
-			    !MDNS_HIP(hipMemsetAsync(d_tickets, 0, (size_t) cap * sizeof(unsigned), c->stream))) { d_tickets = nullptr; tickets_cap = 0; return false; }
-			tickets_cap = cap;
-		}
-		unsigned *tickets = fold ? d_tickets : nullptr;
+		if (fold && !c->fold_tickets.fit_zeroed(grid.x)) return false;
+		unsigned *tickets = fold ? c->fold_tickets.get() : nullptr;
 #define UNI_LAUNCH(D) do { if (rt == 10) hipLaunchKernelGGL((k_nearest_uniform<D, 10>), grid, dim3(kBlock), lds, c->stream, d_members, K, d_packed, kchunk, tile_n, d_part, tickets, nbootstraps, d_round_sq, *finish, nbootstraps); \
 		else hipLaunchKernelGGL((k_nearest_uniform<D, kRounds>), grid, dim3(kBlock), lds, c->stream, d_members, K, d_packed, kchunk, tile_n, d_part, tickets, nbootstraps, d_round_sq, *finish, nbootstraps); } while (0)
 		MDNS_DIM5_SWITCH(ndim, UNI_LAUNCH)
