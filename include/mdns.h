@@ -769,6 +769,38 @@ int mdns_posterior_resample(mdns_posterior *h, unsigned long long seed, long lon
  * [2] quantiles, [3] resampling (ms double[4]) */
 int mdns_posterior_timings(const mdns_posterior *h, double *ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 8 -- a polynomial continuum per spectrum in the scale-marginalised likelihood
+ * (csrc/mdns_continuum.hip).
+ *
+ * With w = 1/v, basis b_k(x_j) = Legendre P_k(t_j), k < P, t_j = (2 x_j - x_0 - x_last) / (x_last - x_0):
+ *   once per spectrum:        G = sum_j w b b^T, beta = G^-1 sum_j w b y, yt = y - sum_k beta_k b_k;
+ *   per (template m, spectrum): alpha = G^-1 sum_j w b m, mt = m - sum_k alpha_k b_k,
+ *                             s = sum w yt mt / (1e-10 + sum w mt^2), L = -0.5 sum w (yt - s mt)^2;
+ * the least-squares minimum over (s, c_0..c_{P-1}) of sum w (y - s m - sum c_k b_k)^2, fitted continuum
+ * c = beta - s alpha.  The bits of L for a (template, spectrum) pair do not depend on B, M, the pair's place in
+ * its batch or the entry point.
+ *
+ * mdns_spectra_set_continuum: P = 0 switches the continuum off, 1..4 on; the spectra need variances and a
+ * wavelength grid.  While P > 0 EVERY scale-marginalised scoring on the handle -- mdns_muse_loglike_batch[_dev],
+ * mdns_muse3_/mdns_lines_loglike_batch[_dev], the joint state and its draw chunks in both forms -- is this
+ * likelihood; chunks take the dense route (no matrix-core filter: mdns_muse_filter_dev fails).  Refused once a
+ * joint state exists on the handle.  A spectrum with fewer than P channels that carry weight (or nx < P) fails
+ * the call with a message naming the first such spectrum; the former setting stays in force.
+ * mdns_spectra_continuum: the current P (-1: null handle).
+ *
+ * mdns_muse_continuum_fit_batch[_dev]: templates ypred [B][nx] against the selected spectra as
+ * mdns_muse_loglike_batch[_dev] scores them (the same kernel, the same bytes in Lout [B][M]), and the fit:
+ * scale_out [B][M] = s, coef_out [B][M][P] = c.  The host form's three output pointers may each be NULL, of the
+ * device form scale and coef.  0 on success, message in mdns_last_error().
+ * ------------------------------------------------------------------------------------------ */
+int mdns_spectra_set_continuum(mdns_spectra *s, int P);
+int mdns_spectra_continuum(const mdns_spectra *s);
+int mdns_muse_continuum_fit_batch(mdns_spectra *s, const double *ypred, int B, const int *row_ids, int M,
+                                  double *Lout, double *scale_out, double *coef_out);
+int mdns_muse_continuum_fit_batch_dev(mdns_spectra *s, const double *d_ypred, int B, const int *d_row_ids, int M,
+                                      double *d_Lout, double *d_scale_out, double *d_coef_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ ABI_SYMBOLS = (
     # caller-made model curves (csrc/mdns_curves.hip)
     "mdns_curve_loglike_batch", "mdns_curve_loglike_batch_dev", "mdns_joint_init_curves",
     "mdns_backend_draw_curves", "mdns_backend_draw_curves_dev",
+    # Part 8: a polynomial continuum per spectrum (csrc/mdns_continuum.hip)
+    "mdns_spectra_set_continuum", "mdns_spectra_continuum", "mdns_muse_continuum_fit_batch", "mdns_muse_continuum_fit_batch_dev",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -208,6 +210,10 @@ def _declare(lib):
         "mdns_joint_init_curves": (i, [vp, vp, d, vp]),
         "mdns_backend_draw_curves": (i, [vp, vp, i, vp, vp, vp, vp]),
         "mdns_backend_draw_curves_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "mdns_spectra_set_continuum": (i, [vp, i]),
+        "mdns_spectra_continuum": (i, [vp]),
+        "mdns_muse_continuum_fit_batch": (i, [vp, vp, i, vp, i, vp, vp, vp]),
+        "mdns_muse_continuum_fit_batch_dev": (i, [vp, vp, i, vp, i, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -405,7 +405,7 @@ extern "C" void mdns_spectra_destroy(mdns_spectra *s)
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
 	// (the grow-only buffers free themselves)
-	void *bufs[] = {s->d_y, s->d_yT, s->d_w, s->d_x, s->d_ysq};
+	void *bufs[] = {s->d_y, s->d_yT, s->d_w, s->d_x, s->d_ysq, s->d_ct, s->d_cfac};
 	for (void *b : bufs) if (b) (void) hipFree(b);
 	if (s->d_yG) (void) hipFree(s->d_yG);
 	if (s->d_fyw) (void) hipFree(s->d_fyw);

@@ -172,6 +172,12 @@ struct mdns_spectra {
 	int nlines = 0;
 	mdns::LineTable lines = {};
 	int njoint = 0;
+	// per-spectrum polynomial continuum profiled out of the scale-marginalised likelihood (mdns_continuum.hip,
+	// mdns_spectra_set_continuum): P = 0 off, else 1..4 Legendre terms in t; d_ct [model_ld(nx)] the channels mapped to
+	// [-1, 1] (zero padded), d_cfac [ndata][kContRec] per spectrum the Cholesky factor of G = sum w b b^T (off-diagonal
+	// entries, then the RECIPROCALS of the diagonal) and beta = G^-1 sum w b y.  Fixed like the line list (njoint)
+	int continuum = 0;
+	double *d_ct = nullptr, *d_cfac = nullptr;
 };
 
 namespace mdns {
@@ -290,6 +296,13 @@ struct MuseBandFused;
 bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int B,
                       const int *d_rows, int M, double *d_out, int B_shape = 0, const MuseBandFused *band = nullptr);
 int muse_rows_variant(int B, int M);
+// the same likelihood with the handle's polynomial continuum profiled out per spectrum (mdns_continuum.hip; what
+// launch_muse_rows launches when s->continuum > 0).  d_scale [B][M] and d_coef [B][M][P] (either may be nullptr): the
+// fitted scale and continuum coefficients of every pair
+static constexpr int kContMax = 4;             // terms at most
+static constexpr int kContRec = 16;            // doubles per spectrum in d_cfac: 6 off-diagonal, 4 reciprocal diagonal, 4 beta, 2 unused
+bool launch_continuum_rows(const mdns_spectra *s, const double *d_model, int ldm, int B, const int *d_rows, int M,
+                           double *d_out, double *d_scale, double *d_coef);
 // the band test of a chunk (mdns_joint.hip, k_joint_band) on K2 as two matrix products (mdns_k2gemm.hip):
 // where its outcome goes (device memory; clear / maybe per candidate, listed pairs behind a counter)
 struct MuseBandOut { int *counter, *clear, *maybe, *pair_b, *pair_k; double *pair_L, *pair_thr; int cap; int *zero_at; };
@@ -419,6 +432,33 @@ __device__ __forceinline__ void handover_acquire() { __builtin_amdgcn_fence(__AT
 // a few microseconds that nobody needs: what the host reads is all in the mailbox.
 template <class T, class V> __device__ __forceinline__ void mail_store(T *at, V v) { __hip_atomic_store(at, (T) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ void mail_raise(unsigned long long *seq_at, unsigned long long seq) { handover_release(); mail_store(seq_at, seq); }
+
+// Sum over the 64 lanes of a wavefront, returned in every lane (wave-uniform).
+// Data-parallel primitives (DPP) move the partial sums inside the VALU -- no LDS crossbar
+// round trips as with ds_bpermute shuffles, which made reductions the longest part of the row
+// kernels.  Steps: the two quad permutations, row_shr:4, row_shr:8 (each 16-lane row now has its
+// sum in lanes 12-15), row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3; lane 63
+// holds the total.  Lanes without a source receive 0 (bound_ctrl), the identity of the sum.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_move(double v)
+{
+	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
+	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
+	return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+	v += dpp_move<0xb1, 0xf>(v);      // quad_perm:[1,0,3,2]
+	v += dpp_move<0x4e, 0xf>(v);      // quad_perm:[2,3,0,1]
+	v += dpp_move<0x114, 0xf>(v);     // row_shr:4
+	v += dpp_move<0x118, 0xf>(v);     // row_shr:8
+	v += dpp_move<0x142, 0xa>(v);     // row_bcast:15 -> rows 1, 3
+	v += dpp_move<0x143, 0xc>(v);     // row_bcast:31 -> rows 2, 3
+	const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
+	const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+	return __hiloint2double(hi, lo);
+}
 
 // ---- what the commit kernels share (mdns_like.hip, mdns_chunk.hip, mdns_joint.hip) ----
 // Likelihood L, which beats the threshold `thr` of data set d, goes onto d's shelf, and d gets its next threshold

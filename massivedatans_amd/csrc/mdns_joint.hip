@@ -1587,7 +1587,7 @@ static int band_launch(mdns_joint *j, bool filtered)
 		const MuseBandOut out = {&j->d_band->counter, j->d_band->clear, j->d_band->maybe, j->d_band->pair_b, j->d_band->pair_k,
 		                         j->d_band->pair_L, j->d_band->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_filter(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
-	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w && j->s->d_x) {
+	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w && j->s->d_x && j->s->continuum == 0) {
 		// small chunks (pairs of candidates per workgroup): templates, then ONE kernel that scores, votes and publishes
 		const int ldm = model_ld(j->s->nx);
 		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;

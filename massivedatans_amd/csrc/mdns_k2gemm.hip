@@ -358,6 +358,7 @@ bool muse_filter_applies(const mdns_spectra *s, int B, int M)
 		g_filter_mode = forced && forced[0] == '0' ? 0 : (forced && forced[0] == '1' ? 1 : -1);
 	}
 	if (!s || !s->d_w || !s->d_x || s->nx < 1 || B < 1 || M < 1) return false;
+	if (s->continuum > 0) return false;          // (its rounding bound is that of K2's formula, not of the continuum's)
 	if (g_filter_mode == 0) return false;
 	if (g_filter_mode == 1) return true;
 	// where the two-row kernel is what the exact path takes (mdns_like.hip, launch_muse_rows) and a pass
@@ -470,6 +471,7 @@ extern "C" int mdns_muse_filter_dev(mdns_spectra *s, const double *d_ypred, int 
 	using namespace mdns;
 	if (!ctx() || !s || !d_ypred || !d_thr || !d_bound || !d_out || B < 1 || M < 1 || M > s->ndata) { set_error("mdns_muse_filter_dev: bad arguments"); return 1; }
 	if (!s->d_w) { set_error("spectra were created without variances"); return 1; }
+	if (s->continuum > 0) { set_error("mdns_muse_filter_dev: a continuum is set on these spectra (the filter bounds K2 without one)"); return 1; }
 	const int ldm = model_ld(s->nx) + 16;
 	if (!ensure_model(s, (size_t) B * ldm) || !launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;
 	const MuseBandOut out = {d_out + 2 * B, d_out, d_out + B, nullptr, nullptr, nullptr, nullptr, 0, nullptr};

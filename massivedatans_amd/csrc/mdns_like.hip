@@ -22,32 +22,7 @@ namespace mdns {
 
 static constexpr int kBlock = 256;
 
-// Sum over the 64 lanes of a wavefront, returned in every lane (wave-uniform).
-// Data-parallel primitives (DPP) move the partial sums inside the VALU -- no LDS crossbar
-// round trips as with ds_bpermute shuffles, which made reductions the longest part of the row
-// kernels.  Steps: the two quad permutations, row_shr:4, row_shr:8 (each 16-lane row now has its
-// sum in lanes 12-15), row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3; lane 63
-// holds the total.  Lanes without a source receive 0 (bound_ctrl), the identity of the sum.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double v)
-{
-	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
-	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-	return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-	v += dpp_move<0xb1, 0xf>(v);      // quad_perm:[1,0,3,2]
-	v += dpp_move<0x4e, 0xf>(v);      // quad_perm:[2,3,0,1]
-	v += dpp_move<0x114, 0xf>(v);     // row_shr:4
-	v += dpp_move<0x118, 0xf>(v);     // row_shr:8
-	v += dpp_move<0x142, 0xa>(v);     // row_bcast:15 -> rows 1, 3
-	v += dpp_move<0x143, 0xc>(v);     // row_bcast:31 -> rows 2, 3
-	const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-	const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-	return __hiloint2double(hi, lo);
-}
+// (dpp_move and wave_sum, the sum over the 64 lanes of a wavefront: mdns_internal.h)
 
 // Several sums at once (gfx950): v_permlane32_swap / v_permlane16_swap exchange half-waves and
 // 16-lane rows between TWO registers, so one swap + one add halves two sums together instead of
@@ -1470,6 +1445,11 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
                       int M, double *d_out, int B_shape, const MuseBandFused *band)
 {
 	const MuseBandFused none = {nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+	if (s->continuum > 0) {
+		// a continuum is profiled out per spectrum: its own kernel, dense scores only (mdns_continuum.hip)
+		if (band) { set_error("launch_muse_rows: no fused band test with a continuum (the chunk takes the dense route)"); return false; }
+		return launch_continuum_rows(s, d_model, ldm, B, d_rows, M, d_out, nullptr, nullptr);
+	}
 	if (band && muse_rows_variant(B_shape > 0 ? B_shape : B, M) != 1) { set_error("launch_muse_rows: the band test rides along with pairs of candidates only"); return false; }
 	const MuseBandFused fused = band ? *band : none;
 	Context *c = ctx();

@@ -113,10 +113,15 @@ def muse_template(x, params, lines=MUSE_LINES, ref=1):
     return y
 
 
-def muse_like(n, nx=4096, lines=MUSE_LINES, ref=1):
+def muse_like(n, nx=4096, lines=MUSE_LINES, ref=1, continuum=0):
     """Synthetic IFU cube: ``n`` spaxels x ``nx`` channels.  Returns ``dict(x, y, v, z, scale)``
     with ``y`` and ``v`` (per-pixel variance) of shape ``[nx, n]``, the layout cmuselike.c:54
-    indexes (``i + j*ndata``).  The truth holds ``lines`` (all ratios 1)."""
+    indexes (``i + j*ndata``).  The truth holds ``lines`` (all ratios 1).
+
+    ``continuum=P`` (1..4) adds to spaxel ``i`` the polynomial ``sum_k scale_i a_k g[i, k] P_k(t)`` in the
+    Legendre basis of :func:`massivedatans_amd.continuum.legendre_basis`, ``a = (1, 1, 0.5, 0.25)[:P]``,
+    ``g = RandomState([n, P]).normal(size=(n, P))`` -- a stream of its own, so that ``continuum=0`` returns the
+    same bytes as ever; the result gains ``continuum_coef`` ``[n, P]``."""
     n = int(n)
     x = np.linspace(4750, 9350, nx)
     rng = np.random.RandomState(n)
@@ -128,7 +133,15 @@ def muse_like(n, nx=4096, lines=MUSE_LINES, ref=1):
         truth = scale[i] * muse_template(x, (0.0, z[i], 0.0) + (1.0,) * (len(lines) - 1), lines, ref)
         v[:, i] = rng.uniform(0.5, 2.0, size=nx) * NOISE_LEVEL ** 2
         y[:, i] = truth + rng.normal(0, 1, size=nx) * np.sqrt(v[:, i])
-    return dict(x=x, y=y, v=v, z=z, scale=scale)
+    out = dict(x=x, y=y, v=v, z=z, scale=scale)
+    if continuum:
+        from . import continuum as _continuum
+        P = _continuum.check_terms(continuum)
+        g = np.random.RandomState([n, P]).normal(size=(n, P))
+        coef = scale[:, None] * np.array((1.0, 1.0, 0.5, 0.25)[:P]) * g
+        y += (coef @ _continuum.legendre_basis(x, P)).T
+        out["continuum_coef"] = coef
+    return out
 
 
 def _is_hdf5(path):

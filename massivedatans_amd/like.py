@@ -128,10 +128,14 @@ class GaussLineSpectra(_Spectra):
 class MuseSpectra(_Spectra):
     """Spectra with per-pixel variances scored against templates (cmuselike.c:45-64).  ``lines``:
     G rows ``(mu, a, sigma)`` of the template the device evaluates from parameters, ``ref`` the line
-    whose ratio is 1 (:func:`massivedatans_amd.gen.muse_template`); None: the built-in three lines."""
+    whose ratio is 1 (:func:`massivedatans_amd.gen.muse_template`); None: the built-in three lines.
+    ``continuum=P`` (1..4): every scoring on these spectra profiles a polynomial of P Legendre terms out per
+    spectrum, together with the scale (:mod:`massivedatans_amd.continuum`; include/mdns.h Part 8)."""
 
-    def __init__(self, x, y, v, layout="channel_major", lines=None, ref=1):
+    def __init__(self, x, y, v, layout="channel_major", lines=None, ref=1, continuum=0):
         from . import gen
+        from .continuum import check_terms
+        continuum = check_terms(continuum)
         if lines is not None:
             lines, ref = gen.check_lines(lines, ref)
         super(MuseSpectra, self).__init__(x, y, v, layout)
@@ -140,6 +144,27 @@ class MuseSpectra(_Spectra):
             table = _lib.as_f64(lines)
             _lib.check(self._lib.mdns_spectra_set_lines(self._h, _lib.ptr(table), len(lines), ref), "mdns_spectra_set_lines")
         self.nparams = int(self._lib.mdns_spectra_nparams(self._h))
+        self.continuum = 0
+        if continuum:
+            _lib.check(self._lib.mdns_spectra_set_continuum(self._h, continuum), "mdns_spectra_set_continuum")
+            self.continuum = continuum
+
+    def continuum_fit(self, ypred, data_mask=None):
+        """``ypred[B, nx]`` -> ``(L[B, M], s[B, M], coef[B, M, P])``: the likelihood as ``loglike_batch`` gives it
+        (the same kernel, the same bytes) with the fitted scale and continuum coefficients of every pair."""
+        if not self.continuum:
+            raise ValueError("these spectra were made without a continuum")
+        ypred = np.atleast_2d(_lib.as_f64(ypred))
+        if ypred.shape[1] != self.nx:
+            raise ValueError("templates must be [B, %d]" % self.nx)
+        rows, M = _rows_from_mask(data_mask, self.ndata)
+        B = len(ypred)
+        L, s, coef = np.empty((B, M)), np.empty((B, M)), np.empty((B, M, self.continuum))
+        if B and M:
+            _lib.check(self._lib.mdns_muse_continuum_fit_batch(self._h, _lib.ptr(ypred), B, _lib.ptr(rows) if rows is not None else None,
+                                                               M, _lib.ptr(L), _lib.ptr(s), _lib.ptr(coef)),
+                       "mdns_muse_continuum_fit_batch")
+        return L, s, coef
 
     def loglike_batch(self, ypred, data_mask=None):
         """``ypred[B, nx]`` precomputed templates -> ``L[B, mask.sum()]`` (= -0.5 chi)."""

@@ -20,6 +20,8 @@ with this problem); ``jitter=False`` drops the noise (kernel benchm
 
 ``MUSE_LINES=<file.json>`` fits another line list: ``{"lines": [[mu, a, sigma], ...], "ref": k}``,
 optionally with ``"prior": [[a, b], ...]`` (one pair per parameter, ``x = a * u + b``).
+``MUSE_CONTINUUM=P`` (1..4) profiles a polynomial continuum of P Legendre terms out of every spectrum,
+together with its scale (:mod:`massivedatans_amd.continuum`); unset or 0: none.
 """
 import json
 import os
@@ -149,7 +151,11 @@ class MuseProblem(object):
     (one ``(a, b)`` pair or None per parameter) overrides the default prior; parameter names, count
     and prior transforms follow.  A GPU backend evaluates the list on the device (it must have been
     made with the same list); of any other backend only ``loglike_batch`` is used, over
-    :func:`massivedatans_amd.gen.muse_template` in numpy."""
+    :func:`massivedatans_amd.gen.muse_template` in numpy.
+
+    ``continuum=P`` (1..4): a polynomial of P Legendre terms per spectrum is profiled out with the scale
+    (:mod:`massivedatans_amd.continuum`).  A backend must have been made with the same ``continuum``
+    (:class:`massivedatans_amd.continuum.ContinuumScorer` is the CPU one); sharded backends have none."""
 
     paramnames = paramnames
     nparams = nparams
@@ -157,7 +163,9 @@ class MuseProblem(object):
     priortransform = staticmethod(priortransform)
     priortransform_batch = staticmethod(priortransform_batch)
 
-    def __init__(self, x, y, v, backend=None, jitter=True, lines=None, ref=1, prior=None):
+    def __init__(self, x, y, v, backend=None, jitter=True, lines=None, ref=1, prior=None, continuum=0):
+        from .continuum import check_terms
+        self.continuum = check_terms(continuum)
         self.x = numpy.ascontiguousarray(x, dtype=float)
         self.y = numpy.ascontiguousarray(y, dtype=float)
         self.v = numpy.ascontiguousarray(v, dtype=float)
@@ -175,9 +183,15 @@ class MuseProblem(object):
             self.priortransform_batch = lambda cubes: _transform_batch(cubes, table)
         if backend is None:
             from .like import MuseSpectra
-            backend = MuseSpectra(self.x, self.y, self.v, lines=self.lines, ref=self.ref)
+            backend = MuseSpectra(self.x, self.y, self.v, lines=self.lines, ref=self.ref, continuum=self.continuum)
         elif hasattr(backend, "lines") and (backend.lines, backend.ref) != (self.lines, self.ref):
             raise ValueError("the backend was made with another line list than the problem")
+        elif getattr(backend, "continuum", 0) != self.continuum:
+            from . import parallel
+            if isinstance(backend, parallel.ShardedMuse):
+                raise ValueError("continuum = %d: sharded runs do not fit a per-spectrum continuum" % self.continuum)
+            raise ValueError("the backend was made with continuum = %r, the problem with %d"
+                             % (getattr(backend, "continuum", 0), self.continuum))
         self.backend = backend
         self.ncalls = 0
         self.nevals = 0
@@ -258,10 +272,11 @@ class TemplateScorer(object):
 
 
 def run(x, y, v, nlive_points=400, nsuperset_draws=10, use_graph=True, max_samples=0, min_samples=0,
-        tolerance=0.5, seed=1, backend=None, jitter=True, fused=True, native=None, lines=None, ref=1, prior=None):
+        tolerance=0.5, seed=1, backend=None, jitter=True, fused=True, native=None, lines=None, ref=1, prior=None,
+        continuum=0):
     """The whole analysis (musefuse.py:607-648); returns ``(results, sampler, problem, duration)``."""
     from .sample import build_sampler, integrate
-    problem = MuseProblem(x, y, v, backend=backend, jitter=jitter, lines=lines, ref=ref, prior=prior)
+    problem = MuseProblem(x, y, v, backend=backend, jitter=jitter, lines=lines, ref=ref, prior=prior, continuum=continuum)
     start = time.time()
     sampler = build_sampler(problem, nlive_points, nsuperset_draws, use_graph, seed, batched=False, fused=fused, native=native)
     results = integrate(sampler, tolerance, min_samples, max_samples)
@@ -270,13 +285,16 @@ def run(x, y, v, nlive_points=400, nsuperset_draws=10, use_graph=True, max_sampl
     return results, sampler, problem, time.time() - start
 
 
-def distributed_backend(x, y, v, lines=None, ref=1):
+def distributed_backend(x, y, v, lines=None, ref=1, continuum=0):
     """One process per GPU (torchrun): this rank's block of spectra and variances on its GPU behind
-    :class:`parallel.ShardedMuse`; None in a single process (see sample.distributed_backend)."""
+    :class:`parallel.ShardedMuse`; None in a single process (see sample.distributed_backend).  Sharded runs
+    fit no per-spectrum continuum: ValueError."""
     from . import sample
     from .parallel import ShardedMuse
     if sample.distributed_setup() is None:
         return None
+    if continuum:
+        raise ValueError("continuum = %r: sharded runs do not fit a per-spectrum continuum (run in one process)" % (continuum,))
     from .like import MuseSpectra
     return ShardedMuse(x, y, v, lambda xs, ys, vs, **kw: MuseSpectra(xs, ys, vs, **kw), lines=lines, ref=ref)
 
@@ -292,11 +310,21 @@ def main(argv=None):
             lines, ref, prior = read_lines(os.environ['MUSE_LINES'])
         except ValueError as e:
             sys.exit("MUSE_LINES: %s" % e)
+    continuum = 0
+    if os.environ.get('MUSE_CONTINUUM'):
+        from .continuum import MAX_TERMS
+        try:
+            continuum = int(os.environ['MUSE_CONTINUUM'])
+            if not 0 <= continuum <= MAX_TERMS:
+                raise ValueError
+        except ValueError:
+            sys.exit("MUSE_CONTINUUM: %r is not an integer in 0..%d (terms of the per-spectrum polynomial)"
+                     % (os.environ['MUSE_CONTINUUM'], MAX_TERMS))
     data = gen.load(argv[1], ndata)
     nlive_points = int(os.environ.get('NLIVE_POINTS', '400'))
     results, sampler, problem, duration = run(
-        data['x'], data['y'], data['v'], nlive_points=nlive_points, lines=lines, ref=ref, prior=prior,
-        backend=distributed_backend(data['x'], data['y'], data['v'], lines, ref),
+        data['x'], data['y'], data['v'], nlive_points=nlive_points, lines=lines, ref=ref, prior=prior, continuum=continuum,
+        backend=distributed_backend(data['x'], data['y'], data['v'], lines, ref, continuum),
         nsuperset_draws=int(os.environ.get('SUPERSET_DRAWS', '10')), use_graph=os.environ.get('USE_GRAPH', '1') == '1',
         max_samples=int(os.environ.get('MAXSAMPLES', 100000)), min_samples=int(os.environ.get('MINSAMPLES', 0)))
     from .sample import write_outputs

@@ -149,9 +149,12 @@ class ShardedMuse(object):
     mask)``: like.MuseSpectra) over all data sets, this rank scoring only its block of spectra and
     variances.  ``backend_factory(x, y_block, v_block)`` builds the per-rank scorer; with a line list
     (``lines``, ``ref``: like.MuseSpectra) it is called with those two as keywords as well, so that every
-    rank sets the same list on its local handle."""
+    rank sets the same list on its local handle.  A per-spectrum continuum (``continuum > 0``) is not
+    part of sharded runs: ValueError."""
 
-    def __init__(self, x, y, v, backend_factory, lines=None, ref=1):
+    def __init__(self, x, y, v, backend_factory, lines=None, ref=1, continuum=0):
+        if continuum:
+            raise ValueError("continuum = %r: sharded runs do not fit a per-spectrum continuum (run in one process)" % (continuum,))
         torch, dist = _dist()
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.ndata = y.shape[1]
@@ -162,6 +165,7 @@ class ShardedMuse(object):
         kw = dict(lines=lines, ref=ref) if lines is not None else {}
         self.local = backend_factory(x, np.ascontiguousarray(y[:, self.lo:self.hi]), np.ascontiguousarray(v[:, self.lo:self.hi]), **kw)
         self.lines, self.ref = lines, (ref if lines is not None else 1)
+        self.continuum = 0
 
     def _sharded(self, call, rows_in, data_mask):
         if data_mask is None:

@@ -26,12 +26,13 @@ import numpy
 MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
 
 
-def default_backend(x, y, noise_level, v=None):
-    """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood."""
+def default_backend(x, y, noise_level, v=None, continuum=0):
+    """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood
+    (``continuum``: like.MuseSpectra)."""
     from .like import GaussLineSpectra, MuseSpectra
     if v is None:
         return GaussLineSpectra(x, y, noise_level=noise_level)
-    return MuseSpectra(x, y, v)
+    return MuseSpectra(x, y, v, continuum=continuum)
 
 
 def host_curves(curves):
@@ -55,7 +56,9 @@ class CurveProblem(object):
     """``x`` f64[nx], ``y`` (and ``v``) f64[nx, ndata] in the reference's layout.  ``model(xs[B, ndim]) ->
     curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Without ``v``
     the likelihood is ``-0.5 sum_j ((curve_j - y_j) / noise_level)**2`` (sample.py:64-71); with per-pixel
-    variances ``v`` the scale-marginalised one of cmuselike.c:45-64 (``noise_level`` is not used).
+    variances ``v`` the scale-marginalised one of cmuselike.c:45-64 (``noise_level`` is not used), with
+    ``continuum=P`` (1..4; needs ``v``) a polynomial of P Legendre terms profiled out per spectrum as well
+    (:mod:`massivedatans_amd.continuum`).
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
     L[B, M]`` (tests put a numpy scorer there; the state is then the numpy one); by default the spectra go
@@ -63,7 +66,12 @@ class CurveProblem(object):
 
     Gives ``sample.build_sampler`` what it reads of a problem."""
 
-    def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None):
+    def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None,
+                 continuum=0):
+        from .continuum import check_terms
+        self.continuum = check_terms(continuum)
+        if self.continuum and v is None:
+            raise ValueError("continuum = %d needs the variances v (the scale-marginalised likelihood)" % self.continuum)
         self.x = numpy.ascontiguousarray(x, dtype=float)
         self.y = numpy.ascontiguousarray(y, dtype=float)
         self.v = None if v is None else numpy.ascontiguousarray(v, dtype=float)
@@ -75,7 +83,13 @@ class CurveProblem(object):
         self.priortransform_batch = priortransform_batch
         self.noise_level = float(noise_level)
         self.jitter_sigma = float(jitter_sigma)
-        self.backend = default_backend(self.x, self.y, self.noise_level, self.v) if backend is None else backend
+        if backend is None:
+            kw = dict(continuum=self.continuum) if self.continuum else {}
+            backend = default_backend(self.x, self.y, self.noise_level, self.v, **kw)
+        self.backend = backend
+        if getattr(backend, "continuum", 0) != self.continuum:
+            raise ValueError("the backend was made with continuum = %r, the problem with %d"
+                             % (getattr(backend, "continuum", 0), self.continuum))
         if jitter_sigma > 0:
             self.multi_loglikelihood_batch = None         # (every evaluation draws its noise: one candidate at a time)
         self.ncalls = 0
