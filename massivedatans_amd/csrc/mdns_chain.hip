@@ -213,7 +213,7 @@ bool launch_chain_accept(const mdns_spectra *s, const ChainSpec &spec, const dou
 	const int nst = nxp / kCH;
 	ProfileScope prof(0);
 #define CHAIN_LAUNCH(NST) hipLaunchKernelGGL((k_chain_accept<NST>), dim3(ntiles * nbt), dim3(256), lds, c->stream, \
-	s->d_y, s->ld, s->nx, nxp, s->d_x, spec, d_props, d_counts, box_dev, scale, d_rows_in, d_rows_dev, M, ntiles, d_higher, d_flags, stamp, trail, \
+	s->d_y.get(), s->ld, s->nx, nxp, s->d_x.get(), spec, d_props, d_counts, box_dev, scale, d_rows_in, d_rows_dev, M, ntiles, d_higher, d_flags, stamp, trail, \
 	(JointHeader *) d_header)
 	if (nst <= 8) { note_kernel(0, "k_chain_accept<8>"); CHAIN_LAUNCH(8); }
 	else if (nst <= 16) { note_kernel(0, "k_chain_accept<16>"); CHAIN_LAUNCH(16); }

@@ -573,7 +573,7 @@ bool chunk_fits(const mdns_spectra *s, int M, int B)
 	// 10 000 x 32: 43.2 / 36.9 and 10 000 x 128: 49.5 / 44.8: with every spectrum selected and several
 	// candidate tiles the lane kernel on the channel-major replica reads perfectly coalesced.
 	if (M > 4096 && B > 8) return false;
-	return groups <= most && cols_nx(s->nx) <= 8 * 32 && s->d_x != nullptr;
+	return groups <= most && cols_nx(s->nx) <= 8 * 32 && s->d_x.get() != nullptr;
 }
 
 bool launch_chunk_accept(const mdns_spectra *s, const double *d_params_mapped, int B, double scale,
@@ -588,7 +588,7 @@ bool launch_chunk_accept(const mdns_spectra *s, const double *d_params_mapped, i
 	const int nst = nxp / kCH;
 	ProfileScope prof(0);
 #define CHUNK_LAUNCH(NST) hipLaunchKernelGGL((k_chunk_accept<NST>), dim3(ntiles * nbt), dim3(256), lds, c->stream, \
-	s->d_y, s->ld, s->nx, nxp, s->d_x, d_params_mapped, B, scale, d_rows_in, d_rows_dev, M, ntiles, d_higher, d_flags, stamp, trail, (JointHeader *) d_header)
+	s->d_y.get(), s->ld, s->nx, nxp, s->d_x.get(), d_params_mapped, B, scale, d_rows_in, d_rows_dev, M, ntiles, d_higher, d_flags, stamp, trail, (JointHeader *) d_header)
 	if (nst <= 8) { note_kernel(0, "k_chunk_accept<8>"); CHUNK_LAUNCH(8); }
 	else if (nst <= 16) { note_kernel(0, "k_chunk_accept<16>"); CHUNK_LAUNCH(16); }
 	else if (nst <= 26) { note_kernel(0, "k_chunk_accept<26>"); CHUNK_LAUNCH(26); }
@@ -668,9 +668,9 @@ bool launch_gauss_mfma_filter(const mdns_spectra *s, const double *d_yT, const d
 			const bool ksplit = ks && ks[0] == '1';
 			const int rt = (M + 15) / 16;
 #define GG_LAUNCH(NC) do { if (ksplit) hipLaunchKernelGGL((k_gauss_gemm_filter<NC, true>), dim3(rt, (nbt + NC - 1) / NC), dim3(256), 0, c->stream, \
-			d_yG, nxg, s->nx, d_model_g, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest); \
+			d_yG, nxg, s->nx, d_model_g, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq.get(), d_flags, d_amb, trail.stamp, d_lowest); \
 		else hipLaunchKernelGGL((k_gauss_gemm_filter<NC, false>), dim3((rt + 3) / 4, (nbt + NC - 1) / NC), dim3(256), 0, c->stream, \
-			d_yG, nxg, s->nx, d_model_g, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest); } while (0)
+			d_yG, nxg, s->nx, d_model_g, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq.get(), d_flags, d_amb, trail.stamp, d_lowest); } while (0)
 			if (nc == 4) GG_LAUNCH(4); else if (nc == 2) GG_LAUNCH(2); else GG_LAUNCH(1);
 #undef GG_LAUNCH
 			if (!launched("k_gauss_gemm_filter")) return false;
@@ -681,7 +681,7 @@ bool launch_gauss_mfma_filter(const mdns_spectra *s, const double *d_yT, const d
 			ProfileScope prof(0);
 			note_kernel(0, "k_gauss_mfma_direct<%d>", nc);
 #define GD_LAUNCH(NC) hipLaunchKernelGGL((k_gauss_mfma_direct<NC>), dim3((M + 15) / 16, gy), dim3(256), 0, c->stream, \
-			d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest, \
+			d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_thr_rows, M, nbt, d_higher, (const double *) s->d_ysq.get(), d_flags, d_amb, trail.stamp, d_lowest, \
 			(const double *) c->mfma_zeros.get())
 			if (nc == 4) GD_LAUNCH(4); else if (nc == 2) GD_LAUNCH(2); else GD_LAUNCH(1);
 #undef GD_LAUNCH
@@ -694,13 +694,13 @@ bool launch_gauss_mfma_filter(const mdns_spectra *s, const double *d_yT, const d
 		note_kernel(0, "k_gauss_mfma_filter");
 #define MFMA_LAUNCH(D, P) hipLaunchKernelGGL((k_gauss_mfma_filter<32, 32, D, P>), dim3(blocks), dim3(256), 0, c->stream, \
 		                   d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_thr_rows, M, nspec, nbt, ngroups, d_higher, \
-		                   (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest)
+		                   (const double *) s->d_ysq.get(), d_flags, d_amb, trail.stamp, d_lowest)
 		// chunks of 40 channels where they leave fewer padded channels than chunks of 32 (200 channels:
 		// none against 24 -- the padded k-steps multiply zeros: 34.1 against 38.9 us on the same box)
 		const bool forty = pr == 0 && (nxp + 39) / 40 * 40 < (nxp + 31) / 32 * 32;
 		if (forty) hipLaunchKernelGGL((k_gauss_mfma_filter<32, 40, 1, 0>), dim3(blocks), dim3(256), 0, c->stream,
 		                              d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_thr_rows, M, nspec, nbt, ngroups, d_higher,
-		                              (const double *) s->d_ysq, d_flags, d_amb, trail.stamp, d_lowest);
+		                              (const double *) s->d_ysq.get(), d_flags, d_amb, trail.stamp, d_lowest);
 		else switch (pr) {
 		case 1: MFMA_LAUNCH(1, 1); break;
 		case 2: MFMA_LAUNCH(1, 2); break;
@@ -716,7 +716,7 @@ bool launch_gauss_mfma_filter(const mdns_spectra *s, const double *d_yT, const d
 	const size_t lds = ((size_t) nxp * 4 + 4) * sizeof(double);
 	const int nst = nxp / kCH;
 #define EXACT_LAUNCH(NST) hipLaunchKernelGGL((k_exact_list<NST>), dim3(ntiles), dim3(256), lds, c->stream, \
-	s->d_y, s->ld, nxp, d_model_t, scale, d_thr_rows, M, ntiles, d_higher, B, (const int *) d_amb, trail.stamp, (const int *) d_lowest, d_flags, trail, \
+	s->d_y.get(), s->ld, nxp, d_model_t, scale, d_thr_rows, M, ntiles, d_higher, B, (const int *) d_amb, trail.stamp, (const int *) d_lowest, d_flags, trail, \
 	(JointHeader *) d_header)
 	if (nst <= 8) EXACT_LAUNCH(8); else if (nst <= 16) EXACT_LAUNCH(16); else if (nst <= 26) EXACT_LAUNCH(26); else EXACT_LAUNCH(32);
 #undef EXACT_LAUNCH

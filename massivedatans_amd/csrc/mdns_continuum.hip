@@ -332,7 +332,7 @@ static void continuum_launch(const mdns_spectra *s, const double *d_model, int l
                              double *d_scale, double *d_coef, dim3 grid, int bchunk, hipStream_t stream)
 {
 	const int nx = s->nx;
-#define CONT_ARGS (const double *) s->d_y, (const double *) s->d_w, s->ld, nx, (const double *) s->d_ct, (const double *) s->d_cfac, \
+#define CONT_ARGS (const double *) s->d_y.get(), (const double *) s->d_w.get(), s->ld, nx, (const double *) s->d_ct.get(), (const double *) s->d_cfac.get(), \
 		d_model, ldm, B, d_rows, M, d_out, bchunk, d_scale, d_coef
 	if (nx <= 512) hipLaunchKernelGGL((k_continuum_rows<1, P>), grid, dim3(kBlock), 0, stream, CONT_ARGS);
 	else if (nx <= 1024) hipLaunchKernelGGL((k_continuum_rows<2, P>), grid, dim3(kBlock), 0, stream, CONT_ARGS);
@@ -347,7 +347,7 @@ bool launch_continuum_rows(const mdns_spectra *s, const double *d_model, int ldm
 {
 	Context *c = ctx();
 	const int P = s->continuum;
-	if (P < 1 || P > kContMax || !s->d_ct || !s->d_cfac) { set_error("launch_continuum_rows: no continuum is set on these spectra"); return false; }
+	if (P < 1 || P > kContMax || !s->d_ct.get() || !s->d_cfac.get()) { set_error("launch_continuum_rows: no continuum is set on these spectra"); return false; }
 	if (B <= 0 || M <= 0) return true;
 	int blocks = M < c->num_cus * 8 ? M : c->num_cus * 8;
 	// few rows, several candidates: split the candidates over grid.y until ~2 workgroups per CU (as launch_muse_rows)
@@ -384,50 +384,41 @@ extern "C" int mdns_spectra_set_continuum(mdns_spectra *s, int P)
 	if (P < 0 || P > kContMax) { set_error("mdns_spectra_set_continuum: P=%d (0: off, 1..%d terms)", P, kContMax); return 1; }
 	if (P == 0) {
 		if (!MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
-		if (s->d_ct) (void) hipFree(s->d_ct);
-		if (s->d_cfac) (void) hipFree(s->d_cfac);
-		s->d_ct = s->d_cfac = nullptr;
+		s->d_ct.release(); s->d_cfac.release();
 		s->continuum = 0;
 		return 0;
 	}
-	if (!s->d_w || !s->d_x) { set_error("mdns_spectra_set_continuum: the spectra need variances and a wavelength grid"); return 1; }
+	if (!s->d_w.get() || !s->d_x.get()) { set_error("mdns_spectra_set_continuum: the spectra need variances and a wavelength grid"); return 1; }
 	if (s->nx < P) { set_error("mdns_spectra_set_continuum: spectrum 0 has %d channels, fewer than the %d terms", s->nx, P); return 1; }
 	const int ldm = model_ld(s->nx);
-	double *d_t = nullptr, *d_fac = nullptr;
-	int *d_status = nullptr;
+	// made in locals and installed on success: the former setting stays in force when this call fails
+	DeviceBuffer<double> t_buf, fac_buf;
+	DeviceBuffer<int> status_buf;
 	int status = INT_MAX;
-	bool ok = MDNS_HIP(hipMalloc((void **) &d_t, (size_t) ldm * sizeof(double))) &&
-	          MDNS_HIP(hipMalloc((void **) &d_fac, ((size_t) s->ndata * kContRec + 1) * sizeof(double))) &&
-	          MDNS_HIP(hipMalloc((void **) &d_status, sizeof(int))) &&
-	          MDNS_HIP(hipMemcpyAsync(d_status, &status, sizeof(int), hipMemcpyHostToDevice, c->stream));
+	bool ok = t_buf.make((size_t) ldm) && fac_buf.make((size_t) s->ndata * kContRec + 1) && status_buf.make(1) &&
+	          MDNS_HIP(hipMemcpyAsync(status_buf.get(), &status, sizeof(int), hipMemcpyHostToDevice, c->stream));
+	double *const d_t = t_buf.get(), *const d_fac = fac_buf.get();
+	int *const d_status = status_buf.get();
 	if (ok) {
-		hipLaunchKernelGGL(k_continuum_t, dim3((ldm + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const double *) s->d_x, s->nx, d_t, ldm);
+		hipLaunchKernelGGL(k_continuum_t, dim3((ldm + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const double *) s->d_x.get(), s->nx, d_t, ldm);
 		ok = launched("k_continuum_t");
 	}
 	if (ok && s->ndata > 0) {
 		const int blocks = s->ndata < c->num_cus * 8 ? s->ndata : c->num_cus * 8;
-#define CONT_SETUP(PP) hipLaunchKernelGGL((k_continuum_setup<PP>), dim3(blocks), dim3(kBlock), 0, c->stream, (const double *) s->d_y, \
-		(const double *) s->d_w, s->ld, s->nx, (const double *) d_t, s->ndata, d_fac, d_status)
+#define CONT_SETUP(PP) hipLaunchKernelGGL((k_continuum_setup<PP>), dim3(blocks), dim3(kBlock), 0, c->stream, (const double *) s->d_y.get(), \
+		(const double *) s->d_w.get(), s->ld, s->nx, (const double *) d_t, s->ndata, d_fac, d_status)
 		if (P == 1) CONT_SETUP(1); else if (P == 2) CONT_SETUP(2); else if (P == 3) CONT_SETUP(3); else CONT_SETUP(4);
 #undef CONT_SETUP
 		ok = launched("k_continuum_setup");
 	}
 	ok = ok && MDNS_HIP(hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
 	ok = MDNS_HIP(hipStreamSynchronize(c->stream)) && ok;
-	if (d_status) (void) hipFree(d_status);
 	if (ok && status != INT_MAX) {
 		set_error("mdns_spectra_set_continuum: spectrum %d has fewer than %d channels with weight", status, P);
 		ok = false;
 	}
-	if (!ok) {
-		// (the former setting stays in force)
-		if (d_t) (void) hipFree(d_t);
-		if (d_fac) (void) hipFree(d_fac);
-		return 1;
-	}
-	if (s->d_ct) (void) hipFree(s->d_ct);
-	if (s->d_cfac) (void) hipFree(s->d_cfac);
-	s->d_ct = d_t; s->d_cfac = d_fac;
+	if (!ok) return 1;
+	s->d_ct = std::move(t_buf); s->d_cfac = std::move(fac_buf);
 	s->continuum = P;
 	return 0;
 }

@@ -346,16 +346,15 @@ static bool upload_rows(const double *h_src, int ndata, int nx, int layout, doub
 	// stage the host array as it is, then re-lay it on the device into [ndata, ld] rows
 	Context *c = ctx();
 	const size_t n = (size_t) ndata * nx;
-	double *d_tmp = nullptr;
-	if (!MDNS_HIP(hipMalloc((void **) &d_tmp, (n ? n : 1) * sizeof(double)))) return false;
+	DeviceBuffer<double> tmp;
+	if (!tmp.make(n)) return false;
+	double *const d_tmp = tmp.get();
 	bool ok = MDNS_HIP(hipMemcpyAsync(d_tmp, h_src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
 	if (ok) {
 		if (layout == MDNS_LAYOUT_CHANNEL_MAJOR) ok = launch_transpose(d_tmp, nx, ndata, d_dst, ld, invert, ndata);
 		else ok = launch_copy_rows(d_tmp, nx, ndata, d_dst, ld, invert);
 	}
-	ok = MDNS_HIP(hipStreamSynchronize(c->stream)) && ok;
-	(void) hipFree(d_tmp);
-	return ok;
+	return MDNS_HIP(hipStreamSynchronize(c->stream)) && ok;      // (drained before `tmp` goes)
 }
 
 extern "C" mdns_spectra *mdns_spectra_create(const double *x, const double *y, const double *v,
@@ -371,28 +370,26 @@ extern "C" mdns_spectra *mdns_spectra_create(const double *x, const double *y, c
 	s->ndata = ndata; s->nx = nx; s->ld = (nx + 1) & ~1;
 	// +2 doubles of slack: the row kernels read whole 16-byte pairs
 	const size_t elems = (size_t) ndata * s->ld + 2;
-	bool ok = MDNS_HIP(hipMalloc((void **) &s->d_y, elems * sizeof(double)));
-	ok = ok && MDNS_HIP(hipMemsetAsync(s->d_y, 0, elems * sizeof(double), c->stream));
-	ok = ok && upload_rows(y, ndata, nx, layout, s->d_y, s->ld, false);
+	bool ok = s->d_y.make(elems, true);
+	ok = ok && upload_rows(y, ndata, nx, layout, s->d_y.get(), s->ld, false);
 	if (ok && !v && nx > 0 && ndata > 0) {
 		// K1 also keeps a channel-major replica, in tiles of 64 spectra, for candidate batches
 		// (the tiling kernel writes every element, padding included)
 		s->ldT = ((ndata + 63) / 64) * 64;
 		const size_t telems = (size_t) cols_nx(nx) * s->ldT;
-		ok = MDNS_HIP(hipMalloc((void **) &s->d_yT, telems * sizeof(double)));
-		ok = ok && launch_tile_columns(s->d_y, s->ld, ndata, nx, nullptr, s->d_yT);
-		ok = ok && MDNS_HIP(hipMalloc((void **) &s->d_ysq, (size_t) ndata * sizeof(double)));
-		ok = ok && launch_row_sumsq(s->d_y, s->ld, nx, ndata, s->d_ysq);
+		ok = s->d_yT.make(telems);
+		ok = ok && launch_tile_columns(s->d_y.get(), s->ld, ndata, nx, nullptr, s->d_yT.get());
+		ok = ok && s->d_ysq.make((size_t) ndata);
+		ok = ok && launch_row_sumsq(s->d_y.get(), s->ld, nx, ndata, s->d_ysq.get());
 		ok = ok && MDNS_HIP(hipStreamSynchronize(c->stream));
 	}
 	if (ok && v) {
-		ok = MDNS_HIP(hipMalloc((void **) &s->d_w, elems * sizeof(double)));
-		ok = ok && MDNS_HIP(hipMemsetAsync(s->d_w, 0, elems * sizeof(double), c->stream));
-		ok = ok && upload_rows(v, ndata, nx, layout, s->d_w, s->ld, true);
+		ok = s->d_w.make(elems, true);
+		ok = ok && upload_rows(v, ndata, nx, layout, s->d_w.get(), s->ld, true);
 	}
 	if (ok && x) {
-		ok = MDNS_HIP(hipMalloc((void **) &s->d_x, (nx ? nx : 1) * sizeof(double)));
-		ok = ok && MDNS_HIP(hipMemcpyAsync(s->d_x, x, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+		ok = s->d_x.make((size_t) nx);
+		ok = ok && MDNS_HIP(hipMemcpyAsync(s->d_x.get(), x, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
 		ok = ok && MDNS_HIP(hipStreamSynchronize(c->stream));
 	}
 	if (!ok) { mdns_spectra_destroy(s); return nullptr; }
@@ -404,16 +401,7 @@ extern "C" void mdns_spectra_destroy(mdns_spectra *s)
 	if (!s) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
-	// (the grow-only buffers free themselves)
-	void *bufs[] = {s->d_y, s->d_yT, s->d_w, s->d_x, s->d_ysq, s->d_ct, s->d_cfac};
-	for (void *b : bufs) if (b) (void) hipFree(b);
-	if (s->d_yG) (void) hipFree(s->d_yG);
-	if (s->d_fyw) (void) hipFree(s->d_fyw);
-	if (s->d_fyw_t) (void) hipFree(s->d_fyw_t);
-	if (s->d_fw_t) (void) hipFree(s->d_fw_t);
-	if (s->d_fa) (void) hipFree(s->d_fa);
-	if (s->d_fw && s->fw_owned) (void) hipFree(s->d_fw);
-	delete s;
+	delete s;           // (its blocks free themselves)
 }
 extern "C" int mdns_spectra_ndata(const mdns_spectra *s) { return s ? s->ndata : -1; }
 extern "C" int mdns_spectra_nparams(const mdns_spectra *s) { return s ? muse_nparams(s) : -1; }
@@ -467,11 +455,11 @@ bool ensure_selection(mdns_spectra *s, size_t doubles) { return s->d_sel.fit(dou
 int gauss_loglike_cols_dev(mdns_spectra *s, const double *d_params, int B, double noise_level,
                            const int *d_row_ids, int M, double *d_Lout)
 {
-	if (!s->d_yT) { set_error("the lane kernel needs the channel-major replica (spectra without variances)"); return 1; }
+	if (!s->d_yT.get()) { set_error("the lane kernel needs the channel-major replica (spectra without variances)"); return 1; }
 	const double scale = -0.5 / (noise_level * noise_level);
 	const int bt = gauss_cols_tile(M, B);
 	if (!ensure_model(s, (size_t) cols_nx(s->nx) * (B + bt))) return 1;
-	if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model.get())) return 1;
+	if (!launch_gauss_model_t(s->d_x.get(), s->nx, d_params, B, bt, s->d_model.get())) return 1;
 	// A selection is first copied into a compact replica (coalesced row reads, one pass)
 	// when the lane kernel would otherwise gather its columns once per candidate tile:
 	// many tiles, or a sparse selection (measured: 1 000 of 10 000 spectra, B = 256: 59 us
@@ -479,10 +467,10 @@ int gauss_loglike_cols_dev(mdns_spectra *s, const double *d_params, int B, doubl
 	const bool sparse = (size_t) M * 8 < (size_t) s->ndata;
 	if (d_row_ids && (B >= 128 || sparse)) {
 		if (!ensure_selection(s, (size_t) ((M + 63) / 64) * 64 * cols_nx(s->nx))) return 1;
-		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
+		if (!launch_tile_columns(s->d_y.get(), s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
 		return launch_gauss_cols(s, s->d_sel.get(), s->d_model.get(), bt, B, scale, nullptr, M, d_Lout) ? 0 : 1;
 	}
-	return launch_gauss_cols(s, s->d_yT, s->d_model.get(), bt, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
+	return launch_gauss_cols(s, s->d_yT.get(), s->d_model.get(), bt, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 }  // namespace mdns
 
@@ -491,7 +479,7 @@ extern "C" int mdns_gauss_loglike_batch_dev(mdns_spectra *s, const double *d_par
                                             double *d_Lout)
 {
 	if (!ctx() || !check_batch(s, B, M, "mdns_gauss_loglike_batch_dev")) return 1;
-	if (!s->d_x) { set_error("spectra were created without a wavelength grid"); return 1; }
+	if (!s->d_x.get()) { set_error("spectra were created without a wavelength grid"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const double scale = -0.5 / (noise_level * noise_level);
 	// Two kernels, chosen by shape only (never by data), so a run is reproducible:
@@ -507,13 +495,13 @@ extern "C" int mdns_gauss_loglike_batch_dev(mdns_spectra *s, const double *d_par
 	const bool dense = (size_t) M * 8 >= (size_t) s->ndata;
 	// dense: the lane kernel pays a ~17 us pipeline fill, the row kernel ~6.5 us plus more per
 	// eval; they cross near 1.5e5 evals (B = 12 at 10 000 spectra, B = 2 at 100 000: 27 vs 38 us)
-	bool use_cols = s->d_yT && ((dense && B >= 2 && (long long) M * B >= 150000) || B >= 32);
+	bool use_cols = s->d_yT.get() && ((dense && B >= 2 && (long long) M * B >= 150000) || B >= 32);
 	if (forced && !strcmp(forced, "rows")) use_cols = false;
-	if (forced && !strcmp(forced, "cols") && s->d_yT) use_cols = true;
+	if (forced && !strcmp(forced, "cols") && s->d_yT.get()) use_cols = true;
 	if (use_cols) return gauss_loglike_cols_dev(s, d_params, B, noise_level, d_row_ids, M, d_Lout);
 	const int ldm = model_ld(s->nx);
 	if (!s->d_model.fit((size_t) B * ldm)) return 1;
-	if (!launch_gauss_model(s->d_x, s->nx, d_params, B, s->d_model.get(), ldm)) return 1;
+	if (!launch_gauss_model(s->d_x.get(), s->nx, d_params, B, s->d_model.get(), ldm)) return 1;
 	return launch_gauss_rows(s, s->d_model.get(), ldm, B, scale, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
@@ -521,7 +509,7 @@ extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypre
                                            const int *d_row_ids, int M, double *d_Lout)
 {
 	if (!ctx() || !check_batch(s, B, M, "mdns_muse_loglike_batch_dev")) return 1;
-	if (!s->d_w) { set_error("spectra were created without variances"); return 1; }
+	if (!s->d_w.get()) { set_error("spectra were created without variances"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const int ldm = model_ld(s->nx);
 	if (!s->d_model.fit((size_t) B * ldm)) return 1;
@@ -533,7 +521,7 @@ extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypre
 static int lines_loglike_dev(mdns_spectra *s, const double *d_params, int B, const int *d_row_ids, int M, double *d_Lout, const char *who)
 {
 	if (!ctx() || !check_batch(s, B, M, who)) return 1;
-	if (!s->d_w || !s->d_x) { set_error("spectra need variances and a wavelength grid"); return 1; }
+	if (!s->d_w.get() || !s->d_x.get()) { set_error("spectra need variances and a wavelength grid"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	const int ldm = model_ld(s->nx);
 	if (!s->d_model.fit((size_t) B * ldm)) return 1;
@@ -639,7 +627,7 @@ extern "C" int mdns_lines_template_batch(mdns_spectra *s, const double *params, 
 	Context *c = ctx();
 	if (!c) return 1;
 	if (!s || !params || !out || B < 0) { set_error("mdns_lines_template_batch: bad arguments (B=%d)", B); return 1; }
-	if (!s->d_x) { set_error("mdns_lines_template_batch: spectra were created without a wavelength grid"); return 1; }
+	if (!s->d_x.get()) { set_error("mdns_lines_template_batch: spectra were created without a wavelength grid"); return 1; }
 	if (B == 0 || s->nx == 0) return 0;
 	const int ldm = model_ld(s->nx);
 	const size_t pbytes = (size_t) B * muse_nparams(s) * sizeof(double);
@@ -725,8 +713,8 @@ extern "C" int mdns_gauss_like(const void *xp, const void *yyp, int ndata, int n
 	} else {
 		// the grid belongs to the call, not to the registration (clike.c:35 takes x every call)
 		Context *c = ctx();
-		if (!s->d_x && !MDNS_HIP(hipMalloc((void **) &s->d_x, nx * sizeof(double)))) return 1;
-		if (!MDNS_HIP(hipMemcpyAsync(s->d_x, xp, nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+		if (!s->d_x.get() && !s->d_x.make((size_t) nx)) return 1;
+		if (!MDNS_HIP(hipMemcpyAsync(s->d_x.get(), xp, nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 		if (!MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
 	}
 	const double params[3] = {A, mu, sig};
@@ -896,64 +884,6 @@ extern "C" double mdns_most_distant_nearest_neighbor(const void *xx, int nsample
 // ---------------------------------------------------------------------------------------
 // resident RadFriends region (members + radius)
 // ---------------------------------------------------------------------------------------
-struct mdns_region {
-	const double *d_members = nullptr;
-	double *owned = nullptr;          // == d_members when this handle allocated them
-	int K = 0, ndim = 0;
-	double radius = NAN;              // maxdistance, host copy
-	double thresh_sq = NAN;           // membership threshold on squared distances, host copy
-	// A radius computation ends on the device: the last workgroup of the bootstrap kernel
-	// writes {radius, threshold} to d_res (for the membership kernel, stream order) and to
-	// h_res (mapped host memory), then h_res->seq = seq.  The host polls for that.
-	double *d_round = nullptr;        // per-round max of squared nearest-chosen distances (slab or own_round)
-	double *own_round = nullptr;
-	int round_cap = 0;
-	RegionResult *d_res = nullptr;
-	RegionResult *h_res = nullptr;    // hipHostMalloc (mapped, coherent)
-	RegionResult *h_res_dev = nullptr;   // its device address
-	unsigned *d_counter = nullptr;
-	int slot = -1;                    // result slot (take_result_slot)
-	unsigned long long seq = 0;
-	bool on_device = false;           // the membership kernel must use d_res
-	bool pending = false;             // the host copies still have to be fetched (async path)
-	size_t owned_bytes = 0, own_round_bytes = 0;      // pool_take sizes
-	void *d_chosen = nullptr; size_t chosen_bytes = 0;
-	void *d_points = nullptr; size_t points_bytes = 0;
-	void *d_counts = nullptr; size_t counts_bytes = 0;
-};
-
-// Result slots ({radius, threshold} on the device, its mapped host mirror and the ticket
-// counter) come from slabs allocated once: the host code builds a region handle per region,
-// and hipHostMalloc per handle was a millisecond each.
-static constexpr int kSlabSlots = 64;
-static constexpr int kSlotRounds = 16;    // per-round maxima kept in the slab (more: own buffer)
-struct ResultSlab { RegionResult *d_res; unsigned *d_counter; RegionResult *h_res, *h_res_dev; double *d_round; };
-static std::vector<ResultSlab> g_slabs;
-static std::vector<int> g_free_slots;
-
-static int take_result_slot()
-{
-	if (g_free_slots.empty()) {
-		ResultSlab slab = {nullptr, nullptr, nullptr, nullptr, nullptr};
-		const bool ok =
-		    MDNS_HIP(hipMalloc((void **) &slab.d_res, kSlabSlots * sizeof(RegionResult))) &&
-		    MDNS_HIP(hipMalloc((void **) &slab.d_counter, kSlabSlots * sizeof(unsigned))) &&
-		    MDNS_HIP(hipMemset(slab.d_counter, 0, kSlabSlots * sizeof(unsigned))) &&
-		    MDNS_HIP(hipMalloc((void **) &slab.d_round, kSlabSlots * kSlotRounds * sizeof(double))) &&
-		    MDNS_HIP(hipMemset(slab.d_round, 0, kSlabSlots * kSlotRounds * sizeof(double))) &&
-		    MDNS_HIP(hipHostMalloc((void **) &slab.h_res, kSlabSlots * sizeof(RegionResult), hipHostMallocMapped | hipHostMallocCoherent)) &&
-		    MDNS_HIP(hipHostGetDevicePointer((void **) &slab.h_res_dev, slab.h_res, 0));
-		if (!ok) return -1;
-		memset(slab.h_res, 0, kSlabSlots * sizeof(RegionResult));
-		const int base = (int) g_slabs.size() * kSlabSlots;
-		g_slabs.push_back(slab);
-		for (int i = kSlabSlots - 1; i >= 0; i--) g_free_slots.push_back(base + i);
-	}
-	const int slot = g_free_slots.back();
-	g_free_slots.pop_back();
-	return slot;
-}
-
 // Device buffers of the region handles come from a small cache: the host code builds a region
 // per rebuild of a constrained draw (thousands per run), and hipMalloc / hipFree per buffer were a
 // quarter of a millisecond per region.  Everything runs on one stream, so a buffer handed back
@@ -986,14 +916,78 @@ static void pool_give(void *p, size_t bytes)
 	g_pool.push_back({bytes, p});
 }
 
-// make *p hold at least `need` bytes (contents are not kept)
-static bool pool_fit(void **p, size_t *cap, size_t need)
+// A block taken from the pool; it goes back there with its owner.
+struct PoolBlock {
+	void *p = nullptr;
+	size_t bytes = 0;
+	PoolBlock() = default;
+	PoolBlock(const PoolBlock &) = delete;
+	PoolBlock &operator=(const PoolBlock &) = delete;
+	~PoolBlock() { pool_give(p, bytes); }
+	// holds at least `need` bytes afterwards (contents are not kept); false (error set): the block is empty
+	bool fit(size_t need)
+	{
+		if (need <= bytes) return true;
+		pool_give(p, bytes);
+		bytes = 0;
+		p = pool_take(need, &bytes);
+		return p != nullptr;
+	}
+};
+
+struct mdns_region {
+	const double *d_members = nullptr;
+	PoolBlock owned;                  // the members, when this handle allocated them
+	int K = 0, ndim = 0;
+	double radius = NAN;              // maxdistance, host copy
+	double thresh_sq = NAN;           // membership threshold on squared distances, host copy
+	// A radius computation ends on the device: the last workgroup of the bootstrap kernel
+	// writes {radius, threshold} to d_res (for the membership kernel, stream order) and to
+	// h_res (mapped host memory), then h_res->seq = seq.  The host polls for that.
+	double *d_round = nullptr;        // per-round max of squared nearest-chosen distances (slab or own_round)
+	PoolBlock own_round;
+	int round_cap = 0;
+	RegionResult *d_res = nullptr;
+	RegionResult *h_res = nullptr;    // hipHostMalloc (mapped, coherent)
+	RegionResult *h_res_dev = nullptr;   // its device address
+	unsigned *d_counter = nullptr;
+	int slot = -1;                    // result slot (take_result_slot)
+	unsigned long long seq = 0;
+	bool on_device = false;           // the membership kernel must use d_res
+	bool pending = false;             // the host copies still have to be fetched (async path)
+	PoolBlock d_chosen, d_points, d_counts;
+};
+
+// Result slots ({radius, threshold} on the device, its mapped host mirror and the ticket
+// counter) come from slabs allocated once: the host code builds a region handle per region,
+// and hipHostMalloc per handle was a millisecond each.
+static constexpr int kSlabSlots = 64;
+static constexpr int kSlotRounds = 16;    // per-round maxima kept in the slab (more: own buffer)
+struct ResultSlab {
+	DeviceBuffer<RegionResult> d_res;
+	DeviceBuffer<unsigned> d_counter;
+	DeviceBuffer<double> d_round;
+	PinnedBuffer h_res{hipHostMallocMapped | hipHostMallocCoherent};
+};
+// kept for the life of the process and, like the context, never destroyed: owners must not free through a runtime
+// that is being torn down at exit
+static std::vector<ResultSlab> &g_slabs = *new std::vector<ResultSlab>;
+static std::vector<int> g_free_slots;
+
+static int take_result_slot()
 {
-	if (need <= *cap) return true;
-	pool_give(*p, *cap);
-	*cap = 0;
-	*p = pool_take(need, cap);
-	return *p != nullptr;
+	if (g_free_slots.empty()) {
+		// (a slab that fails part-way frees what it made on return: nothing is left behind, g_slabs does not grow)
+		ResultSlab slab;
+		if (!slab.d_res.make(kSlabSlots) || !slab.d_counter.make(kSlabSlots, true) ||
+		    !slab.d_round.make(kSlabSlots * kSlotRounds, true) || !slab.h_res.make(kSlabSlots * sizeof(RegionResult))) return -1;
+		const int base = (int) g_slabs.size() * kSlabSlots;
+		g_slabs.push_back(std::move(slab));
+		for (int i = kSlabSlots - 1; i >= 0; i--) g_free_slots.push_back(base + i);
+	}
+	const int slot = g_free_slots.back();
+	g_free_slots.pop_back();
+	return slot;
 }
 
 static bool region_fetch(mdns_region *r);
@@ -1046,22 +1040,22 @@ static bool region_launch_radius(mdns_region *r, bool (*launch)(const double *, 
 	return true;
 }
 
-static mdns_region *region_new(const double *d_members, double *owned, int K, int ndim)
+// d_members == nullptr: the members are the region's own block (r->owned, filled by the caller)
+static bool region_init(mdns_region *r, const double *d_members, int K, int ndim)
 {
-	mdns_region *r = new mdns_region();
-	r->d_members = d_members; r->owned = owned; r->K = K; r->ndim = ndim;
+	r->d_members = d_members ? d_members : (const double *) r->owned.p; r->K = K; r->ndim = ndim;
 	r->slot = take_result_slot();
-	if (r->slot < 0) { mdns_region_destroy(r); return nullptr; }
+	if (r->slot < 0) return false;
 	const ResultSlab &slab = g_slabs[r->slot / kSlabSlots];
 	const int i = r->slot % kSlabSlots;
-	r->d_res = slab.d_res + i;
-	r->d_counter = slab.d_counter + i;
-	r->h_res = slab.h_res + i;
-	r->h_res_dev = slab.h_res_dev + i;
-	r->d_round = slab.d_round + (size_t) i * kSlotRounds;      // zero: every finishing computation leaves it so
+	r->d_res = slab.d_res.get() + i;
+	r->d_counter = slab.d_counter.get() + i;
+	r->h_res = (RegionResult *) slab.h_res.get() + i;
+	r->h_res_dev = (RegionResult *) slab.h_res.dev() + i;
+	r->d_round = slab.d_round.get() + (size_t) i * kSlotRounds;      // zero: every finishing computation leaves it so
 	r->round_cap = kSlotRounds;
 	r->seq = r->h_res->seq;            // a recycled slot keeps counting from where it was
-	return r;
+	return true;
 }
 
 extern "C" mdns_region *mdns_region_create(const double *members, int K, int ndim)
@@ -1070,13 +1064,11 @@ extern "C" mdns_region *mdns_region_create(const double *members, int K, int ndi
 	if (!c) return nullptr;
 	if (!members || K <= 0 || ndim <= 0) { set_error("mdns_region_create: bad arguments (K=%d ndim=%d)", K, ndim); return nullptr; }
 	const size_t bytes = (size_t) K * ndim * sizeof(double);
-	size_t got = 0;
-	double *d = (double *) pool_take(bytes, &got);
-	if (!d) return nullptr;
-	if (!MDNS_HIP(hipMemcpyAsync(d, members, bytes, hipMemcpyHostToDevice, c->stream)) ||
-	    !MDNS_HIP(hipStreamSynchronize(c->stream))) { pool_give(d, got); return nullptr; }
-	mdns_region *r = region_new(d, d, K, ndim);
-	if (r) r->owned_bytes = got; else pool_give(d, got);
+	mdns_region *r = new mdns_region();
+	if (!r->owned.fit(bytes) ||
+	    !MDNS_HIP(hipMemcpyAsync(r->owned.p, members, bytes, hipMemcpyHostToDevice, c->stream)) ||
+	    !MDNS_HIP(hipStreamSynchronize(c->stream)) ||
+	    !region_init(r, nullptr, K, ndim)) { mdns_region_destroy(r); return nullptr; }
 	return r;
 }
 
@@ -1096,18 +1088,15 @@ static mdns_region *create_bootstrapped(const double *members, int K, int ndim, 
 	}
 	const size_t mbytes = (size_t) K * ndim * sizeof(double), pbytes = (size_t) K * sizeof(unsigned);
 	const size_t poff = (mbytes + 255) & ~(size_t) 255;
-	size_t got = 0;
-	char *d = (char *) pool_take(poff + pbytes, &got);
-	if (!d) return nullptr;
-	char *pin = (char *) pinned_scratch(poff + pbytes);
-	if (!pin) { pool_give(d, got); return nullptr; }
+	mdns_region *r = new mdns_region();
+	char *pin = r->owned.fit(poff + pbytes) ? (char *) pinned_scratch(poff + pbytes) : nullptr;
+	if (!pin) { mdns_region_destroy(r); return nullptr; }
+	char *const d = (char *) r->owned.p;
 	memcpy(pin, members, mbytes);
 	memcpy(pin + poff, packed, pbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(d, pin, poff + pbytes, hipMemcpyHostToDevice, c->stream))) { pool_give(d, got); return nullptr; }
-	mdns_region *r = region_new((const double *) d, (double *) d, K, ndim);
-	if (!r) { (void) hipStreamSynchronize(c->stream); pool_give(d, got); return nullptr; }
-	r->owned_bytes = got;
-	if (!region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) (d + poff), nbootstraps)) {
+	if (!MDNS_HIP(hipMemcpyAsync(d, pin, poff + pbytes, hipMemcpyHostToDevice, c->stream))) { mdns_region_destroy(r); return nullptr; }
+	if (!region_init(r, nullptr, K, ndim) ||
+	    !region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) (d + poff), nbootstraps)) {
 		(void) hipStreamSynchronize(c->stream);
 		mdns_region_destroy(r);
 		return nullptr;
@@ -1142,7 +1131,9 @@ extern "C" mdns_region *mdns_region_wrap_dev(const double *d_members, int K, int
 {
 	if (!ctx()) return nullptr;
 	if (!d_members || K <= 0 || ndim <= 0) { set_error("mdns_region_wrap_dev: bad arguments"); return nullptr; }
-	return region_new(d_members, nullptr, K, ndim);
+	mdns_region *r = new mdns_region();
+	if (!region_init(r, d_members, K, ndim)) { mdns_region_destroy(r); return nullptr; }
+	return r;
 }
 
 extern "C" void mdns_region_destroy(mdns_region *r)
@@ -1151,13 +1142,8 @@ extern "C" void mdns_region_destroy(mdns_region *r)
 	// a radius computation still in flight writes the result slot: let it land before the slot
 	// can go to another handle (the buffers themselves are reused in stream order)
 	if (r->pending && ctx()) (void) region_fetch(r);
-	pool_give(r->owned, r->owned_bytes);
-	pool_give(r->own_round, r->own_round_bytes);
-	pool_give(r->d_chosen, r->chosen_bytes);
-	pool_give(r->d_points, r->points_bytes);
-	pool_give(r->d_counts, r->counts_bytes);
 	if (r->slot >= 0) g_free_slots.push_back(r->slot);
-	delete r;
+	delete r;           // (its blocks go back to the pool)
 }
 
 extern "C" int mdns_region_set_radius(mdns_region *r, double maxdistance)
@@ -1202,8 +1188,8 @@ extern "C" int mdns_region_bootstrap_radius_async(mdns_region *r, const double *
 	if (nbootstraps <= 0) { set_error("mdns_region_bootstrap_radius: nbootstraps=%d", nbootstraps); return 1; }
 	if (!region_fetch(r)) return 1;             // a previous result may still be travelling
 	if (r->round_cap < nbootstraps) {
-		if (!pool_fit((void **) &r->own_round, &r->own_round_bytes, (size_t) nbootstraps * sizeof(double))) return 1;
-		r->d_round = r->own_round;
+		if (!r->own_round.fit((size_t) nbootstraps * sizeof(double))) return 1;
+		r->d_round = (double *) r->own_round.p;
 		// zero once: every finishing computation hands its slots back zeroed
 		if (!MDNS_HIP(hipMemsetAsync(r->d_round, 0, (size_t) nbootstraps * sizeof(double), c->stream))) return 1;
 		r->round_cap = nbootstraps;
@@ -1223,9 +1209,9 @@ extern "C" double mdns_region_bootstrap_radius(mdns_region *r, const double *cho
 	if (!c || !r) return NAN;
 	const size_t n = (size_t) r->K * (nbootstraps > 0 ? nbootstraps : 0);
 	if (n == 0) { set_error("mdns_region_bootstrap_radius: nbootstraps=%d", nbootstraps); return NAN; }
-	if (!pool_fit(&r->d_chosen, &r->chosen_bytes, n * sizeof(double))) return NAN;
-	if (!MDNS_HIP(hipMemcpyAsync(r->d_chosen, chosen, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return NAN;
-	return mdns_region_bootstrap_radius_dev(r, (const double *) r->d_chosen, nbootstraps);
+	if (!r->d_chosen.fit(n * sizeof(double))) return NAN;
+	if (!MDNS_HIP(hipMemcpyAsync(r->d_chosen.p, chosen, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return NAN;
+	return mdns_region_bootstrap_radius_dev(r, (const double *) r->d_chosen.p, nbootstraps);
 }
 
 extern "C" double mdns_region_bootstrap_radius_packed(mdns_region *r, const unsigned *packed, int nbootstraps)
@@ -1235,9 +1221,9 @@ extern "C" double mdns_region_bootstrap_radius_packed(mdns_region *r, const unsi
 	if (nbootstraps <= 0 || nbootstraps > 16 || !packed) { set_error("mdns_region_bootstrap_radius_packed: nbootstraps=%d (1..16)", nbootstraps); return NAN; }
 	if (!region_fetch(r)) return NAN;
 	const size_t bytes = (size_t) r->K * sizeof(unsigned);
-	if (!pool_fit(&r->d_chosen, &r->chosen_bytes, bytes)) return NAN;
-	if (!MDNS_HIP(hipMemcpyAsync(r->d_chosen, packed, bytes, hipMemcpyHostToDevice, c->stream))) return NAN;
-	if (!region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) r->d_chosen, nbootstraps)) return NAN;
+	if (!r->d_chosen.fit(bytes)) return NAN;
+	if (!MDNS_HIP(hipMemcpyAsync(r->d_chosen.p, packed, bytes, hipMemcpyHostToDevice, c->stream))) return NAN;
+	if (!region_launch_radius(r, launch_bootstrap_packed, (const unsigned *) r->d_chosen.p, nbootstraps)) return NAN;
 	return mdns_region_radius(r);
 }
 
@@ -1309,10 +1295,9 @@ extern "C" int mdns_region_count(mdns_region *r, const double *points, int M, in
 	if (!c || !r) return 1;
 	if (M <= 0) return M < 0;
 	const size_t n = (size_t) M * r->ndim;
-	if (!pool_fit(&r->d_points, &r->points_bytes, n * sizeof(double)) ||
-	    !pool_fit(&r->d_counts, &r->counts_bytes, (size_t) M * sizeof(int))) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(r->d_points, points, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (mdns_region_count_dev(r, (const double *) r->d_points, M, (int *) r->d_counts) != 0) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(counts, r->d_counts, (size_t) M * sizeof(int), hipMemcpyDeviceToHost, c->stream))) return 1;
+	if (!r->d_points.fit(n * sizeof(double)) || !r->d_counts.fit((size_t) M * sizeof(int))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(r->d_points.p, points, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (mdns_region_count_dev(r, (const double *) r->d_points.p, M, (int *) r->d_counts.p) != 0) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(counts, r->d_counts.p, (size_t) M * sizeof(int), hipMemcpyDeviceToHost, c->stream))) return 1;
 	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }

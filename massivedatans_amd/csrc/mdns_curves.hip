@@ -119,7 +119,7 @@ bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, i
 	Context *c = ctx();
 	if (B <= 0 || M <= 0) return true;
 	const dim3 grid((M + kCurveSpectra - 1) / kCurveSpectra, (B + kCurveCands - 1) / kCurveCands);
-	hipLaunchKernelGGL(k_curve_rows, grid, dim3(256), 0, c->stream, (const double *) s->d_y, s->ld, s->nx, d_curves, ldc, B,
+	hipLaunchKernelGGL(k_curve_rows, grid, dim3(256), 0, c->stream, (const double *) s->d_y.get(), s->ld, s->nx, d_curves, ldc, B,
 	                   d_rows, M, scale, d_out);
 	return launched("k_curve_rows");
 }

@@ -278,16 +278,17 @@ using namespace mdns;
 
 struct mdns_groups {
 	int nlive = 0, ndata = 0;
-	int *d_idsT = nullptr;             // [ndata][nlive]
-	int *d_tmp = nullptr;              // [nlive][ndata] staging of set_ids / get_ids
-	int *d_label = nullptr;            // [ndata] by data set
-	int *d_rows = nullptr;             // [3 * ndata]: selection, or (rows | slots | new ids) of a replacement
-	int *d_labels = nullptr;           // [ndata] by position in the selection
+	DeviceBuffer<int> d_idsT;          // [ndata][nlive]
+	DeviceBuffer<int> d_tmp;           // [nlive][ndata] staging of set_ids / get_ids
+	DeviceBuffer<int> d_label;         // [ndata] by data set
+	DeviceBuffer<int> d_rows;          // [3 * ndata]: selection, or (rows | slots | new ids) of a replacement
+	DeviceBuffer<int> d_labels;        // [ndata] by position in the selection
 	// per id; grown with the pile of accepted points.  One block:
 	//   header | touched bit map | plabel | point labels (out)
-	char *d_points = nullptr;  long long cap_points = 0;
+	DeviceBuffer<char> d_points;  long long cap_points = 0;
 	PinnedBuffer h_pin;
-	GroupsBox *h_box = nullptr, *h_box_dev = nullptr;  long long box_cap = 0;   // room for box_cap ids
+	PinnedBuffer box{hipHostMallocMapped | hipHostMallocCoherent};             // room for box_cap ids
+	GroupsBox *h_box = nullptr, *h_box_dev = nullptr;  long long box_cap = 0;   // views of `box`, set once it is whole
 	unsigned long long box_seq = 0;
 	bool have_ids = false;
 	int last_M = -1;  long long last_npoints = 0, last_ndistinct = 0;      // of the last components call (-1: ids changed since)
@@ -302,8 +303,8 @@ struct mdns_groups {
 static constexpr size_t kHeaderBytes = 512;            // sizeof(GroupsHeader) rounded up: keeps what follows aligned
 static_assert(sizeof(GroupsHeader) <= kHeaderBytes, "header grew");
 static size_t words_of(long long npoints) { return (size_t) ((npoints + 63) / 64); }
-static GroupsHeader *hdr_of(mdns_groups *g) { return (GroupsHeader *) g->d_points; }
-static unsigned long long *touched_of(mdns_groups *g) { return (unsigned long long *) (g->d_points + kHeaderBytes); }
+static GroupsHeader *hdr_of(mdns_groups *g) { return (GroupsHeader *) g->d_points.get(); }
+static unsigned long long *touched_of(mdns_groups *g) { return (unsigned long long *) (g->d_points.get() + kHeaderBytes); }
 static PLabel *plabel_of(mdns_groups *g) { return (PLabel *) (touched_of(g) + words_of(g->cap_points)); }
 static int *pout_of(mdns_groups *g) { return (int *) (plabel_of(g) + g->cap_points); }
 
@@ -313,27 +314,26 @@ static bool groups_fit_points(mdns_groups *g, long long npoints)
 	Context *c = ctx();
 	long long cap = g->cap_points > 0 ? g->cap_points : 4096;
 	while (cap < npoints) cap *= 2;                                    // (a multiple of 64: the regions stay 8-byte aligned)
-	if (g->d_points) { (void) hipStreamSynchronize(c->stream); (void) hipFree(g->d_points); g->d_points = nullptr; g->cap_points = 0; }
+	g->cap_points = 0;
 	const size_t bytes = kHeaderBytes + words_of(cap) * 8 + (size_t) cap * (sizeof(PLabel) + sizeof(int));
-	if (!MDNS_HIP(hipMalloc((void **) &g->d_points, bytes))) return false;
+	// header and stamps start at zero: call numbers start at 1
+	if (!all_or_none(g->d_points.make(bytes) &&
+	                 MDNS_HIP(hipMemsetAsync(g->d_points.get(), 0, kHeaderBytes + words_of(cap) * 8 + (size_t) cap * sizeof(PLabel), c->stream)),
+	                 g->d_points)) return false;
 	g->cap_points = cap;
 	g->last_M = -1;
-	// header and stamps start at zero: call numbers start at 1
-	return MDNS_HIP(hipMemsetAsync(g->d_points, 0, kHeaderBytes + words_of(cap) * 8 + (size_t) cap * sizeof(PLabel), c->stream));
+	return true;
 }
 
 // mapped host block with room for `ids` distinct ids
 static bool groups_fit_box(mdns_groups *g, long long ids)
 {
 	if (g->h_box && ids <= g->box_cap) return true;
-	Context *c = ctx();
 	long long cap = g->box_cap > 0 ? g->box_cap : 4096;
 	while (cap < ids) cap *= 2;
-	if (g->h_box) { (void) hipStreamSynchronize(c->stream); (void) hipHostFree(g->h_box); g->h_box = nullptr; g->box_cap = 0; }
-	const size_t bytes = sizeof(GroupsBox) + (size_t) cap * sizeof(int);
-	if (!MDNS_HIP(hipHostMalloc((void **) &g->h_box, bytes, hipHostMallocMapped | hipHostMallocCoherent)) ||
-	    !MDNS_HIP(hipHostGetDevicePointer((void **) &g->h_box_dev, g->h_box, 0))) return false;
-	memset(g->h_box, 0, sizeof(GroupsBox));
+	g->h_box = g->h_box_dev = nullptr; g->box_cap = 0;
+	if (!g->box.make(sizeof(GroupsBox) + (size_t) cap * sizeof(int))) return false;
+	g->h_box = (GroupsBox *) g->box.get(); g->h_box_dev = (GroupsBox *) g->box.dev();
 	g->h_box->seq = g->box_seq;
 	g->box_cap = cap;
 	return true;
@@ -344,9 +344,6 @@ extern "C" void mdns_groups_destroy(mdns_groups *g)
 	if (!g) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
-	if (g->h_box) (void) hipHostFree(g->h_box);
-	void *bufs[] = {g->d_idsT, g->d_tmp, g->d_label, g->d_rows, g->d_labels, g->d_points};
-	for (void *b : bufs) if (b) (void) hipFree(b);
 	delete g;
 }
 
@@ -359,13 +356,13 @@ extern "C" mdns_groups *mdns_groups_create(int nlive, int ndata)
 	g->nlive = nlive; g->ndata = ndata;
 	const size_t nd = (size_t) ndata;
 	const bool ok =
-	    MDNS_HIP(hipMalloc((void **) &g->d_idsT, (size_t) nlive * nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &g->d_tmp, (size_t) nlive * nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &g->d_label, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &g->d_rows, 3 * nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &g->d_labels, nd * sizeof(int))) &&
+	    g->d_idsT.make((size_t) nlive * nd) &&
+	    g->d_tmp.make((size_t) nlive * nd) &&
+	    g->d_label.make(nd) &&
+	    g->d_rows.make(3 * nd) &&
+	    g->d_labels.make(nd) &&
 	    groups_fit_points(g, 4096);
-	if (!ok) { mdns_groups_destroy(g); return nullptr; }
+	if (!ok) { delete g; return nullptr; }
 	return g;
 }
 
@@ -374,9 +371,9 @@ extern "C" int mdns_groups_set_ids(mdns_groups *g, const int32_t *ids)
 	Context *c = ctx();
 	if (!c || !g || !ids) return 1;
 	const size_t bytes = (size_t) g->nlive * g->ndata * sizeof(int);
-	if (!MDNS_HIP(hipMemcpyAsync(g->d_tmp, ids, bytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(g->d_tmp.get(), ids, bytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	hipLaunchKernelGGL(k_groups_transpose, dim3((g->ndata + 31) / 32, (g->nlive + 31) / 32), dim3(kBlock), 0, c->stream,
-	                   g->d_tmp, g->nlive, g->ndata, g->d_idsT);
+	                   g->d_tmp.get(), g->nlive, g->ndata, g->d_idsT.get());
 	if (!MDNS_HIP(hipGetLastError()) || !MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
 	g->have_ids = true;
 	g->last_M = -1;
@@ -389,9 +386,9 @@ extern "C" int mdns_groups_get_ids(mdns_groups *g, int32_t *ids)
 	if (!c || !g || !ids) return 1;
 	const size_t bytes = (size_t) g->nlive * g->ndata * sizeof(int);
 	hipLaunchKernelGGL(k_groups_transpose, dim3((g->nlive + 31) / 32, (g->ndata + 31) / 32), dim3(kBlock), 0, c->stream,
-	                   g->d_idsT, g->ndata, g->nlive, g->d_tmp);
+	                   g->d_idsT.get(), g->ndata, g->nlive, g->d_tmp.get());
 	return MDNS_HIP(hipGetLastError()) &&
-	       MDNS_HIP(hipMemcpyAsync(ids, g->d_tmp, bytes, hipMemcpyDeviceToHost, c->stream)) &&
+	       MDNS_HIP(hipMemcpyAsync(ids, g->d_tmp.get(), bytes, hipMemcpyDeviceToHost, c->stream)) &&
 	       MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }
 
@@ -411,9 +408,9 @@ extern "C" int mdns_groups_replace(mdns_groups *g, const int32_t *rows, const in
 	memcpy(pin, rows, (size_t) n * 4);
 	memcpy(pin + (size_t) n * 4, slots, (size_t) n * 4);
 	memcpy(pin + (size_t) n * 8, new_ids, (size_t) n * 4);
-	if (!MDNS_HIP(hipMemcpyAsync(g->d_rows, pin, (size_t) 3 * n * 4, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(g->d_rows.get(), pin, (size_t) 3 * n * 4, hipMemcpyHostToDevice, c->stream))) return 1;
 	hipLaunchKernelGGL(k_groups_replace, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-	                   g->d_idsT, g->ndata, g->nlive, g->d_rows, g->d_rows + n, g->d_rows + 2 * n, n, &hdr_of(g)->status);
+	                   g->d_idsT.get(), g->ndata, g->nlive, g->d_rows.get(), g->d_rows.get() + n, g->d_rows.get() + 2 * n, n, &hdr_of(g)->status);
 	g->last_M = -1;
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
@@ -455,7 +452,7 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 		if (!g->h_rows.fit((size_t) g->ndata * 4)) return 1;              // (room for every data set: made once)
 		memcpy(g->h_rows.get(), rows, (size_t) M * 4);
 	}
-	int *d_rows = rows ? g->d_rows : nullptr;
+	int *d_rows = rows ? g->d_rows.get() : nullptr;
 	// Nothing is cleared: point labels and the rounds' "moved" flags carry the number of the batch
 	// of rounds they belong to, the component counter is put back to zero by the kernel that reads it.
 	if (g->call >= 0x7ffffff0) {                                     // stamps start over (once in 2^31 batches)
@@ -472,14 +469,14 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 		if (total > 0) flag = ++g->call;                              // (labels keep the stamp `call`; only the flags move on)
 		for (int r = 0; r < batch; r++)
 			hipLaunchKernelGGL(k_groups_round, dim3((M + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
-			                   g->d_idsT, g->nlive, d_rows, rows && total == 0 && r == 0 ? (const int *) g->h_rows.dev() : nullptr, M, npoints,
-			                   plabel_of(g), g->d_label, total == 0 && r == 0 ? 1 : 0, call,
+			                   g->d_idsT.get(), g->nlive, d_rows, rows && total == 0 && r == 0 ? (const int *) g->h_rows.dev() : nullptr, M, npoints,
+			                   plabel_of(g), g->d_label.get(), total == 0 && r == 0 ? 1 : 0, call,
 			                   flag, &hdr_of(g)->changed[r], &hdr_of(g)->status, kSweeps);
 		total += batch;
 		// optimistically everything that follows a converged state, in the same round trip
 		const int finish_blocks = (M + kBlock - 1) / kBlock;
 		hipLaunchKernelGGL(k_groups_finish, dim3(finish_blocks + (unsigned) ((npoints + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-		                   g->d_label, (const int *) d_rows, M, g->d_labels, hdr_of(g), finish_blocks, plabel_of(g), npoints, call, touched_of(g));
+		                   g->d_label.get(), (const int *) d_rows, M, g->d_labels.get(), hdr_of(g), finish_blocks, plabel_of(g), npoints, call, touched_of(g));
 		hipLaunchKernelGGL(k_groups_compact, dim3(1), dim3(1024), 0, c->stream, touched_of(g), (long long) nw, pout_of(g), hdr_of(g),
 		                   g->h_box_dev, ++g->box_seq);
 		if (!MDNS_HIP(hipGetLastError())) return 1;
@@ -549,7 +546,7 @@ extern "C" int mdns_groups_id_labels(mdns_groups *g, int32_t *labels, int32_t *i
 		                   plabel_of(g), (const int *) list, ndistinct, g->label_call, out);
 		if (!MDNS_HIP(hipGetLastError())) return 1;
 	}
-	if (labels && !MDNS_HIP(hipMemcpyAsync(labels, g->d_labels, (size_t) M * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
+	if (labels && !MDNS_HIP(hipMemcpyAsync(labels, g->d_labels.get(), (size_t) M * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
 	if (id_labels && ndistinct > 0 && !MDNS_HIP(hipMemcpyAsync(id_labels, out, (size_t) ndistinct * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
 	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }
@@ -566,7 +563,7 @@ extern "C" int mdns_groups_labels(mdns_groups *g, int32_t *labels, int32_t *poin
 		hipLaunchKernelGGL(k_groups_point_labels, dim3((unsigned) ((np + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
 		                   plabel_of(g), np, g->label_call, pout_of(g));
 	if (!MDNS_HIP(hipGetLastError())) return 1;
-	if (labels && !MDNS_HIP(hipMemcpyAsync(labels, g->d_labels, (size_t) M * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
+	if (labels && !MDNS_HIP(hipMemcpyAsync(labels, g->d_labels.get(), (size_t) M * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
 	if (point_labels && !MDNS_HIP(hipMemcpyAsync(point_labels, pout_of(g), (size_t) np * 4, hipMemcpyDeviceToHost, c->stream))) return 1;
 	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }

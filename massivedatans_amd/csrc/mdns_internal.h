@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <utility>
 #include "mdns.h"
 
 namespace mdns {
@@ -24,15 +26,29 @@ bool launched(const char *name);
 enum class Wait { ok, timeout, failed, empty };
 Wait wait_seq(const volatile unsigned long long *at, unsigned long long want, hipError_t *err = nullptr);
 
-// ---- grow-only scratch ---------------------------------------------------------------------
-// How large a block that has to hold `need` elements of `elem` bytes is made: half as much again, in whole pages of
-// 4 KiB.  The ONE growth policy of every DeviceBuffer and PinnedBuffer.
+// ---- owned memory: grow-only scratch and exact-size blocks ------------------------------------
+// Two owners, DeviceBuffer<T> and PinnedBuffer, and two ways to fill one:
+//   fit(n)   grow-only SCRATCH of a call: holds >= n afterwards, made half as much again so that the next, slightly
+//            larger call finds room; contents are not kept across a growth.
+//   make(n)  a RESIDENT block of a handle (d_y, live, h_box ...): exactly n, at least one element, made once and kept
+//            until the owner dies or is made again.  No growth policy: a resident array must not take half as much again.
+// Handles hold owners, so `delete handle` (after ONE synchronise of the stream) frees everything and no destroy function
+// lists members.  Everything else (kernel arguments, JointArrays, JointTrail, typed mailbox pointers, last_yT ...) is
+// a view: a raw pointer taken with get() AFTER the owner is made.  A group of blocks made lazily on first use is made
+// in locals or under all_or_none(), and its views are set last: it is whole or absent, never half there.
+//
+// How large a block that has to hold `need` elements of `elem` bytes is made by fit(): half as much again, in whole pages
+// of 4 KiB.  The ONE growth policy of every DeviceBuffer and PinnedBuffer.
 constexpr size_t grown_bytes(size_t need, size_t elem) { return ((need + need / 2) * elem + 4095) / 4096 * 4096; }
 static_assert(grown_bytes(0, 8) == 0, "nothing asked, nothing made");
 static_assert(grown_bytes(1, 8) == 4096, "one element: one page");
 static_assert(grown_bytes(341, 8) == 4096, "341 + 170 doubles = 4088 bytes: still one page");
 static_assert(grown_bytes(342, 8) == 8192, "342 + 171 doubles = 4104 bytes: two pages");
-// The growing path (mdns_core.hip): a block that exists is freed once the context's current stream has drained -- a
+// and by make(): what is asked, one element at least
+constexpr size_t exact_bytes(size_t need, size_t elem) { return (need ? need : 1) * elem; }
+static_assert(exact_bytes(0, 8) == 8, "nothing asked: one element, as hipMalloc(0) hands out nothing to own");
+static_assert(exact_bytes(342, 8) == 2736, "342 doubles are 342 doubles: no half again, no page rounding");
+// The allocating path (mdns_core.hip): a block that exists is freed once the context's current stream has drained -- a
 // kernel may still be using it --, a first allocation waits for nothing.  zero: the new block is cleared over all its
 // `bytes`, in stream order; flags: as hipHostMalloc takes them.  nullptr (and the error set) on any failure; the old
 // block is gone either way.
@@ -41,8 +57,7 @@ void *pinned_regrow(void *old, size_t bytes, unsigned flags);
 void scratch_free(void *p, bool host);
 void *scratch_dev_pointer(void *host_block);       // of a mapped block; nullptr (and the error set) on failure
 
-// An owning, grow-only block of device memory for `cap()` elements.  Everything else (kernel arguments, JointTrail,
-// last_yT ...) is a view: a raw pointer taken with get() AFTER the fit() of the call that uses it.
+// An owning block of device memory for `cap()` elements.
 template <typename T> class DeviceBuffer {
 public:
 	DeviceBuffer() = default;
@@ -56,15 +71,16 @@ public:
 	T *get() const { return p_; }
 	size_t cap() const { return cap_; }
 	// holds >= n elements afterwards; contents are NOT kept across a growth.  false (error set): the buffer is empty
-	bool fit(size_t n) { return n <= cap_ || regrow(n, false); }
+	bool fit(size_t n) { return n <= cap_ || alloc(grown_bytes(n, sizeof(T)), false); }
 	// the same; a newly allocated block is zero over its whole capacity, in stream order
-	bool fit_zeroed(size_t n) { return n <= cap_ || regrow(n, true); }
+	bool fit_zeroed(size_t n) { return n <= cap_ || alloc(grown_bytes(n, sizeof(T)), true); }
+	// holds exactly max(n, 1) elements afterwards (zero: cleared in stream order), whatever it held before
+	bool make(size_t n, bool zero = false) { return alloc(exact_bytes(n, sizeof(T)), zero); }
 	// (whoever calls has made sure that nothing on the device uses the block any more)
 	void release() { if (p_) scratch_free(p_, false); p_ = nullptr; cap_ = 0; }
 private:
-	bool regrow(size_t n, bool zero)
+	bool alloc(size_t bytes, bool zero)
 	{
-		const size_t bytes = grown_bytes(n, sizeof(T));
 		p_ = (T *) device_regrow(p_, bytes, zero);
 		cap_ = p_ ? bytes / sizeof(T) : 0;
 		return p_ != nullptr;
@@ -73,23 +89,33 @@ private:
 	size_t cap_ = 0;
 };
 
-// The same for pinned host memory, counted in bytes; `flags` as hipHostMalloc takes them.  dev(): a mapped block as
-// the device sees it.
+// The same for pinned host memory, counted in bytes; `flags` as hipHostMalloc takes them (they travel with a move).
+// dev(): a mapped block as the device sees it.
 class PinnedBuffer {
 public:
 	explicit PinnedBuffer(unsigned flags = hipHostMallocDefault) : flags_(flags) {}
-	PinnedBuffer(const PinnedBuffer &) = delete;       // (nothing copies or moves one)
-	PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+	PinnedBuffer(PinnedBuffer &&o) noexcept : p_(o.p_), dev_(o.dev_), cap_(o.cap_), flags_(o.flags_) { o.p_ = o.dev_ = nullptr; o.cap_ = 0; }
+	PinnedBuffer &operator=(PinnedBuffer &&o) noexcept
+	{
+		if (this != &o) { release(); p_ = o.p_; dev_ = o.dev_; cap_ = o.cap_; flags_ = o.flags_; o.p_ = o.dev_ = nullptr; o.cap_ = 0; }
+		return *this;
+	}
 	~PinnedBuffer() { release(); }
 	char *get() const { return p_; }
 	char *dev() const { return dev_; }
 	size_t cap() const { return cap_; }
-	bool fit(size_t bytes) { return bytes <= cap_ || regrow(bytes); }
+	bool fit(size_t bytes) { return bytes <= cap_ || alloc(grown_bytes(bytes, 1)); }
+	// exactly max(bytes, 1) bytes, all zero, whatever it held before
+	bool make(size_t bytes)
+	{
+		if (!alloc(exact_bytes(bytes, 1))) return false;
+		memset(p_, 0, cap_);
+		return true;
+	}
 	void release() { if (p_) scratch_free(p_, true); p_ = dev_ = nullptr; cap_ = 0; }
 private:
-	bool regrow(size_t bytes)
+	bool alloc(size_t want)
 	{
-		const size_t want = grown_bytes(bytes, 1);
 		p_ = (char *) pinned_regrow(p_, want, flags_);
 		dev_ = nullptr; cap_ = 0;
 		if (p_ && (flags_ & hipHostMallocMapped) && !(dev_ = (char *) scratch_dev_pointer(p_))) release();
@@ -100,6 +126,14 @@ private:
 	size_t cap_ = 0;
 	unsigned flags_;
 };
+
+// A group of blocks that only make sense together: `ok` is the && chain that made (and cleared, and filled) them;
+// when it failed every one of them is released, so the group is whole or absent and the next call tries again.
+template <class... B> bool all_or_none(bool ok, B &...b)
+{
+	if (!ok) (b.release(), ...);
+	return ok;
+}
 
 // ---- per-process context (one process drives one GPU) -----------------------------------
 struct Context {
@@ -144,15 +178,16 @@ struct mdns_spectra {
 	int ndata = 0;      // number of spectra (rows)
 	int nx = 0;         // channels per spectrum
 	int ld = 0;         // row stride in doubles (nx rounded up to even => 16-byte aligned rows)
-	double *d_y = nullptr;   // [ndata, ld]   one spectrum per row
-	double *d_yT = nullptr;  // [ldT/64][cols_nx(nx)][64] channel-major replica in tiles of 64 spectra
-	                         // (K1 lane kernel), or nullptr
-	int ldT = 0;             // ndata rounded up to a multiple of 64 (zero padded)
-	double *d_w = nullptr;   // [ndata, ld] inverse variances 1/v (K2), or nullptr
-	double *d_x = nullptr;   // [nx] wavelength grid, or nullptr
-	double *d_ysq = nullptr; // [ndata] sum of squares of every spectrum (K1 accept filter), or nullptr
-	double *d_yG = nullptr;  // K1 on the matrix cores with operands straight from memory (k_gauss_gemm_filter): the spectra in
-	                         // tiles of 16 rows, channel pair by channel pair (tiled16_at), channels padded to 16; or nullptr
+	// resident blocks, made once at their exact size (make); "or empty": get() == nullptr
+	mdns::DeviceBuffer<double> d_y;    // [ndata, ld]   one spectrum per row
+	mdns::DeviceBuffer<double> d_yT;   // [ldT/64][cols_nx(nx)][64] channel-major replica in tiles of 64 spectra
+	                                   // (K1 lane kernel), or empty
+	int ldT = 0;                       // ndata rounded up to a multiple of 64 (zero padded)
+	mdns::DeviceBuffer<double> d_w;    // [ndata, ld] inverse variances 1/v (K2), or empty
+	mdns::DeviceBuffer<double> d_x;    // [nx] wavelength grid, or empty
+	mdns::DeviceBuffer<double> d_ysq;  // [ndata] sum of squares of every spectrum (K1 accept filter), or empty
+	mdns::DeviceBuffer<double> d_yG;   // K1 on the matrix cores with operands straight from memory (k_gauss_gemm_filter): the spectra in
+	                                   // tiles of 16 rows, channel pair by channel pair (tiled16_at), channels padded to 16; or empty
 	mdns::DeviceBuffer<double> d_selG;                 // the same of the current selection
 	mdns::DeviceBuffer<double> d_model_g;              // templates in the same tiling
 	// per-handle grow-only device buffers for the host-pointer batch API
@@ -162,11 +197,10 @@ struct mdns_spectra {
 	mdns::DeviceBuffer<double> d_out;
 	mdns::DeviceBuffer<double> d_sel;                  // compact replica of the current selection (K1 lane kernel)
 	// K2 on the matrix cores (mdns_k2gemm.hip), made on first use: y w and w [ndata, ldf] with ldf = nx rounded
-	// up to 16 (zero padded; d_fw is d_w itself when the strides agree), A = sum y^2 w [ndata]
-	double *d_fyw = nullptr, *d_fw = nullptr, *d_fa = nullptr;
-	double *d_fyw_t = nullptr, *d_fw_t = nullptr;       // the same two in tiles of 16 rows (mdns_k2gemm.hip, tiled_at)
+	// up to 16 (zero padded), A = sum y^2 w [ndata]; all five or none (muse_filter_prepare)
+	mdns::DeviceBuffer<double> d_fyw, d_fw, d_fa;
+	mdns::DeviceBuffer<double> d_fyw_t, d_fw_t;         // the same two in tiles of 16 rows (mdns_k2gemm.hip, tiled_at)
 	int ldf = 0;
-	bool fw_owned = false;
 	// the template model: nlines == 0 the built-in three lines (k_muse3_model, 5 parameters), else `lines`
 	// (k_lines_model, nlines + 2 parameters); fixed once a joint state exists on the handle (njoint)
 	int nlines = 0;
@@ -177,7 +211,7 @@ struct mdns_spectra {
 	// [-1, 1] (zero padded), d_cfac [ndata][kContRec] per spectrum the Cholesky factor of G = sum w b b^T (off-diagonal
 	// entries, then the RECIPROCALS of the diagonal) and beta = G^-1 sum w b y.  Fixed like the line list (njoint)
 	int continuum = 0;
-	double *d_ct = nullptr, *d_cfac = nullptr;
+	mdns::DeviceBuffer<double> d_ct, d_cfac;
 };
 
 namespace mdns {

@@ -376,20 +376,25 @@ struct ChunkScore { int path, B, flag; };
 struct mdns_joint {
 	mdns_spectra *s = nullptr;
 	int nlive = 0, cap = 0, ndata = 0;
+	// the sampler state: its four arrays, and `st`, the view of them that the kernels take by value (filled once they
+	// are made, and again when mdns_joint_reserve replaces the shelves)
+	DeviceBuffer<double> live, shelfL, higher;
+	DeviceBuffer<int> shelfn;
 	JointArrays st = {};
-	int *d_running = nullptr;  int nrun = 0;
-	double *d_Lmin = nullptr;          // [ndata] by position in the running list
-	int *d_argmin_run = nullptr;       // [ndata] by position in the running list
-	int *d_argmin = nullptr;           // [ndata] by data set
+	DeviceBuffer<int> d_running;  int nrun = 0;
+	DeviceBuffer<double> d_Lmin;       // [ndata] by position in the running list
+	DeviceBuffer<int> d_argmin_run;    // [ndata] by position in the running list
+	DeviceBuffer<int> d_argmin;        // [ndata] by data set
 	DeviceBuffer<unsigned long long> d_keep;
-	int *d_status = nullptr;           // sticky failure bits of advance
+	DeviceBuffer<int> d_status;        // sticky failure bits of advance
 	// one allocation: accept flags | header | fill bits | likelihood row  (the model kernel of a
 	// chunk clears flags + header; header onward is what the host reads)
-	int *d_flags = nullptr;
+	DeviceBuffer<int> d_flags;
 	char *d_result = nullptr;          // = (char *) (d_flags + kFlagInts)
 	// the outcome of a commit without the likelihood row: mapped host memory a kernel behind the
 	// commit pass writes and the host polls (JointMailbox)
-	JointMailbox *h_box = nullptr, *h_box_dev = nullptr;
+	PinnedBuffer box{hipHostMallocMapped | hipHostMallocCoherent};
+	JointMailbox *h_box = nullptr, *h_box_dev = nullptr;       // views of `box`
 	unsigned long long box_seq = 0;
 	bool box_pending = false;          // a commit was launched whose mailbox has not been read
 	// the trail of the accept pass (JointTrail): grown to candidates x tiles of the largest chunk
@@ -397,7 +402,8 @@ struct mdns_joint {
 	int trail_stamp = 0;
 	bool trail_valid = false;          // the last score left a trail for its chunk
 	// staging of the host-pointer draw
-	double *d_params = nullptr;
+	DeviceBuffer<char> d_params;
+	double *params() const { return (double *) d_params.get(); }
 	int *d_rows = nullptr;             // inside d_params' block, behind the candidates
 	PinnedBuffer h_pin;
 	// what the last score launched with (commit uses the same spectra replica and templates)
@@ -418,8 +424,9 @@ struct mdns_joint {
 	int kind = 0;
 	int nparams = 3;                   // kind 1: of the spectra's template model (5, or its line list's G + 2)
 	bool counted = false;              // this state is in the spectra's njoint (the model is fixed while it lives)
-	double *d_msq = nullptr;                                // templates' sums of squares (guarded accept filter, kind 0)
-	int *d_filter_scratch = nullptr;                        // matrix-core filter: ambiguous marks
+	// made on first use, each by itself
+	DeviceBuffer<double> d_msq;                             // templates' sums of squares (guarded accept filter, kind 0)
+	DeviceBuffer<int> d_filter_scratch;                     // matrix-core filter: ambiguous marks (zero when made)
 	DeviceBuffer<double> d_dense;                           // L[B, M] of a chunk (kind 1)
 	DeviceBuffer<double> d_jitter;
 	DeviceBuffer<double> d_curves;                          // model curves of a chunk that came as a host array
@@ -434,26 +441,31 @@ struct mdns_joint {
 	int chunk_seq = 1;
 	// what the chunk kernels read directly: candidates, then the selection's row ids, in host
 	// memory mapped into the device
-	char *h_in = nullptr, *h_in_dev = nullptr;
+	PinnedBuffer in_block{hipHostMallocMapped};
+	char *h_in = nullptr, *h_in_dev = nullptr;             // views of `in_block`
 	// no shelf holds more than this many entries (set by prepare from the purge's keep bits, +1 per
 	// accepted chunk, -1 per advance): when it reaches the capacity the shelves are grown
 	int shelf_bound = 0;
 	// the first batch of a region without a host look in between (mdns_backend_chain_*, mdns_chain.hip)
-	ChainBox *h_chain = nullptr, *h_chain_dev = nullptr;   // mapped
-	double *d_chain_props = nullptr;
-	int *d_chain_counts = nullptr, *d_chain_ticket = nullptr;
-	int *d_commit_ticket = nullptr;    // workgroups of a commit pass that are done (k_joint_commit_trail publishing by itself)
-	// the likelihood noise in band form (mdns_backend_draw_band / _commit)
-	BandBox *h_band = nullptr, *h_band_dev = nullptr;
-	BandScratch *d_band = nullptr;
-	double *d_bound = nullptr;                // [MDNS_JOINT_MAX_BATCH] bounds, then room for one noise row [ndata]
+	// its four blocks are made together on first use, all or none: h_chain set, they are there
+	PinnedBuffer chain_box{hipHostMallocMapped};
+	ChainBox *h_chain = nullptr, *h_chain_dev = nullptr;   // views of `chain_box`
+	DeviceBuffer<double> d_chain_props;
+	DeviceBuffer<int> d_chain_counts, d_chain_ticket;      // (the ticket zero between launches)
+	DeviceBuffer<int> d_commit_ticket; // workgroups of a commit pass that are done (k_joint_commit_trail publishing by itself)
+	// the likelihood noise in band form (mdns_backend_draw_band / _commit): three blocks made together on first use, all
+	// or none: h_band set, they are there
+	PinnedBuffer band_box{hipHostMallocMapped};
+	BandBox *h_band = nullptr, *h_band_dev = nullptr;      // views of `band_box`
+	DeviceBuffer<BandScratch> d_band;         // (zero between launches)
+	DeviceBuffer<double> d_bound;             // [MDNS_JOINT_MAX_BATCH] bounds, then room for one noise row [ndata]
 	unsigned long long band_seq = 0;
 	int band_B = 0;
 	bool band_pending = false;        // a chunk begun and not collected (mdns_backend_draw_band_begin / _end)
 	bool band_exact = true;           // d_dense holds the exact likelihoods of the chunk (not the matrix-core filter's)
 	// a chunk in two halves (mdns_backend_draw_score / _commit): one 0 / 1 vote per candidate, what the ranks
 	// of a sharded run MAX-reduce in between
-	int *d_votes = nullptr;
+	DeviceBuffer<int> d_votes;
 	ChunkScore half = {0, 0, 0};       // what the score of the halves left for their commit
 	unsigned long long chain_seq = 0;
 	int chain_state = 0;               // 0 none, 1 counts only (poll h_chain->seq), 2 full (poll the commit's mailbox)
@@ -472,12 +484,6 @@ extern "C" void mdns_joint_destroy(mdns_joint *j)
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
 	if (j->s && j->counted) j->s->njoint--;
-	void *bufs[] = {j->st.live, j->st.shelfL, j->st.shelfn, j->st.higher, j->d_running, j->d_Lmin, j->d_argmin_run,
-	                j->d_argmin, j->d_status, j->d_flags, j->d_params, j->d_msq, j->d_filter_scratch, j->d_chain_props,
-	                j->d_chain_counts, j->d_chain_ticket, j->d_commit_ticket, j->d_votes, j->d_band, j->d_bound};
-	for (void *b : bufs) if (b) (void) hipFree(b);
-	void *pinned[] = {j->h_in, j->h_chain, j->h_band, j->h_box};
-	for (void *b : pinned) if (b) (void) hipHostFree(b);
 	delete j;
 }
 
@@ -486,41 +492,34 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	Context *c = ctx();
 	if (!c) return nullptr;
 	if (!s || nlive <= 0 || s->ndata <= 0) { set_error("mdns_joint_create: bad arguments (nlive=%d)", nlive); return nullptr; }
-	if (!s->d_x || (!s->d_yT && !s->d_w)) { set_error("mdns_joint_create: the spectra need a wavelength grid"); return nullptr; }
+	if (!s->d_x.get() || (!s->d_yT.get() && !s->d_w.get())) { set_error("mdns_joint_create: the spectra need a wavelength grid"); return nullptr; }
 	if (shelf_cap < 4) shelf_cap = 4;
 	mdns_joint *j = new mdns_joint();
 	j->s = s; j->nlive = nlive; j->cap = shelf_cap; j->ndata = s->ndata;
 	// spectra with variances: the scale-marginalised likelihood against the three-line template
-	j->kind = s->d_w ? 1 : 0;
+	j->kind = s->d_w.get() ? 1 : 0;
 	j->nparams = j->kind == 1 ? muse_nparams(s) : 3;
 	const size_t nd = (size_t) s->ndata;
 	const size_t res = (size_t) kFlagInts * sizeof(int) + result_bytes(s->ndata);
+	static_assert(sizeof(JointHeader) % sizeof(int) == 0, "d_flags is counted in ints");
 	bool ok =
-	    MDNS_HIP(hipMalloc((void **) &j->st.live, (size_t) nlive * nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->st.shelfL, (size_t) shelf_cap * nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->st.shelfn, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->st.higher, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_running, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_Lmin, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_argmin_run, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_argmin, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_status, sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &j->d_flags, res)) &&
+	    j->live.make((size_t) nlive * nd) && j->shelfL.make((size_t) shelf_cap * nd) && j->shelfn.make(nd) && j->higher.make(nd) &&
+	    j->d_running.make(nd) && j->d_Lmin.make(nd) && j->d_argmin_run.make(nd) && j->d_argmin.make(nd) && j->d_status.make(1) &&
+	    j->d_flags.make(res / sizeof(int)) &&
 	    // candidates [B, 3] followed by the selection's row ids: one staging block (kind 1: candidates [B, nparams] alone)
-	    MDNS_HIP(hipMalloc((void **) &j->d_params, (size_t) MDNS_JOINT_MAX_BATCH * kJointParamsMost * sizeof(double) + nd * sizeof(int) + 16)) &&
-	    MDNS_HIP(hipHostMalloc((void **) &j->h_box, sizeof(JointMailbox) + ((nd + 63) / 64) * 8, hipHostMallocMapped | hipHostMallocCoherent)) &&
-	    MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_box_dev, j->h_box, 0));
+	    j->d_params.make((size_t) MDNS_JOINT_MAX_BATCH * kJointParamsMost * sizeof(double) + nd * sizeof(int) + 16) &&
+	    j->box.make(sizeof(JointMailbox) + ((nd + 63) / 64) * 8);
 	if (ok) {
-		memset(j->h_box, 0, sizeof(JointMailbox) + ((nd + 63) / 64) * 8);
-		j->d_result = (char *) (j->d_flags + kFlagInts);
-		j->st.nlive = nlive; j->st.cap = shelf_cap; j->st.ndata = s->ndata;
+		j->h_box = (JointMailbox *) j->box.get(); j->h_box_dev = (JointMailbox *) j->box.dev();
+		j->d_result = (char *) (j->d_flags.get() + kFlagInts);
+		j->st = {j->live.get(), j->shelfL.get(), j->shelfn.get(), j->higher.get(), nlive, shelf_cap, s->ndata};
 		std::vector<int> all(nd);
 		for (size_t i = 0; i < nd; i++) all[i] = (int) i;
 		ok = MDNS_HIP(hipMemsetAsync(j->st.shelfn, 0, nd * sizeof(int), c->stream)) &&
-		     MDNS_HIP(hipMemsetAsync(j->d_status, 0, sizeof(int), c->stream)) &&
-		     MDNS_HIP(hipMemsetAsync(j->d_flags, 0, res, c->stream)) &&
-		     MDNS_HIP(hipMemsetAsync(j->d_argmin, 0, nd * sizeof(int), c->stream)) &&
-		     MDNS_HIP(hipMemcpyAsync(j->d_running, all.data(), nd * sizeof(int), hipMemcpyHostToDevice, c->stream));
+		     MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) &&
+		     MDNS_HIP(hipMemsetAsync(j->d_flags.get(), 0, res, c->stream)) &&
+		     MDNS_HIP(hipMemsetAsync(j->d_argmin.get(), 0, nd * sizeof(int), c->stream)) &&
+		     MDNS_HIP(hipMemcpyAsync(j->d_running.get(), all.data(), nd * sizeof(int), hipMemcpyHostToDevice, c->stream));
 		if (ok) {
 			hipLaunchKernelGGL(k_joint_fill, dim3(256), dim3(kBlock), 0, c->stream, j->st.higher, nd, (double) NAN);
 			ok = MDNS_HIP(hipGetLastError()) && joint_sync(c);
@@ -544,13 +543,13 @@ extern "C" int mdns_joint_reserve(mdns_joint *j, int shelf_cap)
 	int cap = j->cap;
 	while (cap < shelf_cap) cap *= 2;
 	const size_t nd = (size_t) j->ndata;
-	double *bigger = nullptr;
-	if (!MDNS_HIP(hipMalloc((void **) &bigger, (size_t) cap * nd * sizeof(double)))) return 1;
+	DeviceBuffer<double> bigger;                  // (the old block stays when anything here fails)
+	if (!bigger.make((size_t) cap * nd)) return 1;
 	// entry-major layout: the old array is a prefix of the new one
-	if (!MDNS_HIP(hipMemcpyAsync(bigger, j->st.shelfL, (size_t) j->cap * nd * sizeof(double), hipMemcpyDeviceToDevice, c->stream)) ||
-	    !joint_sync(c)) { (void) hipFree(bigger); return 1; }
-	(void) hipFree(j->st.shelfL);
-	j->st.shelfL = bigger;
+	if (!MDNS_HIP(hipMemcpyAsync(bigger.get(), j->st.shelfL, (size_t) j->cap * nd * sizeof(double), hipMemcpyDeviceToDevice, c->stream)) ||
+	    !joint_sync(c)) return 1;
+	j->shelfL = std::move(bigger);
+	j->st.shelfL = j->shelfL.get();
 	j->cap = j->st.cap = cap;
 	return 0;
 }
@@ -561,7 +560,7 @@ static int joint_reset(mdns_joint *j)
 	j->prepared = false;
 	j->shelf_bound = 0;
 	return MDNS_HIP(hipMemsetAsync(j->st.shelfn, 0, (size_t) j->ndata * sizeof(int), c->stream)) &&
-	       MDNS_HIP(hipMemsetAsync(j->d_status, 0, sizeof(int), c->stream)) ? 0 : 1;
+	       MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) ? 0 : 1;
 }
 
 extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double noise_level)
@@ -574,9 +573,9 @@ extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double
 	char *pin = j->h_pin.get();
 	j->noise_level = noise_level;
 	memcpy(pin, params, (size_t) j->nlive * 24);
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, (size_t) j->nlive * 24, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, (size_t) j->nlive * 24, hipMemcpyHostToDevice, c->stream))) return 1;
 	// always the lane kernel: every likelihood of a run is then the same chain of operations
-	if (gauss_loglike_cols_dev(j->s, j->d_params, j->nlive, noise_level, nullptr, j->ndata, j->st.live) != 0) return 1;
+	if (gauss_loglike_cols_dev(j->s, j->params(), j->nlive, noise_level, nullptr, j->ndata, j->st.live) != 0) return 1;
 	if (joint_reset(j) != 0) return 1;
 	return joint_sync(c) ? 0 : 1;
 }
@@ -591,8 +590,8 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 	if (!j->h_pin.fit(pbytes)) return 1;
 	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	if (mdns_lines_loglike_batch_dev(j->s, j->d_params, j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (mdns_lines_loglike_batch_dev(j->s, j->params(), j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
 	if (jitter) {
 		// (musefuse.py:535 adds its noise to the initial points' likelihoods too)
 		if (!j->d_jitter.fit(n)) return 1;
@@ -652,7 +651,7 @@ extern "C" int mdns_joint_undo_advance_dev(mdns_joint *j)
 	if (!j->prepared) { set_error("mdns_joint_undo_advance_dev: nothing to take back"); return 1; }
 	if (j->nrun == 0) return 0;
 	hipLaunchKernelGGL(k_joint_undo_advance, dim3((j->nrun + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-	                   j->st, j->d_running, j->nrun, j->d_argmin, j->d_Lmin);
+	                   j->st, j->d_running.get(), j->nrun, j->d_argmin.get(), j->d_Lmin.get());
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -694,7 +693,7 @@ extern "C" int mdns_joint_set_running(mdns_joint *j, const int *rows, int nrun)
 			set_error("mdns_joint_set_running: rows must be ascending indices below %d", j->ndata);
 			return 1;
 		}
-	if (nrun > 0 && (!MDNS_HIP(hipMemcpyAsync(j->d_running, rows, (size_t) nrun * sizeof(int), hipMemcpyHostToDevice, c->stream)) ||
+	if (nrun > 0 && (!MDNS_HIP(hipMemcpyAsync(j->d_running.get(), rows, (size_t) nrun * sizeof(int), hipMemcpyHostToDevice, c->stream)) ||
 	                 !joint_sync(c))) return 1;
 	j->nrun = nrun;
 	return 0;
@@ -709,7 +708,7 @@ extern "C" int mdns_joint_prepare_dev(mdns_joint *j)
 	j->prepared = true;
 	if (j->nrun == 0) return 0;
 	hipLaunchKernelGGL(k_joint_prepare, dim3((j->nrun + 15) / 16), dim3(kBlock), 0, c->stream,
-	                   j->st, j->d_running, j->nrun, j->d_Lmin, j->d_argmin_run, j->d_argmin, j->d_keep.get(), kw);
+	                   j->st, j->d_running.get(), j->nrun, j->d_Lmin.get(), j->d_argmin_run.get(), j->d_argmin.get(), j->d_keep.get(), kw);
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -724,8 +723,8 @@ extern "C" int mdns_joint_prepare(mdns_joint *j, double *Lmin, int *argmin, unsi
 	const size_t o1 = n * 8, o2 = o1 + ((n * 4 + 7) & ~(size_t) 7);
 	if (!j->h_pin.fit(o2 + n * kw * 8)) return 1;
 	char *pin = j->h_pin.get();
-	if (!MDNS_HIP(hipMemcpyAsync(pin, j->d_Lmin, n * 8, hipMemcpyDeviceToHost, c->stream)) ||
-	    !MDNS_HIP(hipMemcpyAsync(pin + o1, j->d_argmin_run, n * 4, hipMemcpyDeviceToHost, c->stream)) ||
+	if (!MDNS_HIP(hipMemcpyAsync(pin, j->d_Lmin.get(), n * 8, hipMemcpyDeviceToHost, c->stream)) ||
+	    !MDNS_HIP(hipMemcpyAsync(pin + o1, j->d_argmin_run.get(), n * 4, hipMemcpyDeviceToHost, c->stream)) ||
 	    !MDNS_HIP(hipMemcpyAsync(pin + o2, j->d_keep.get(), n * kw * 8, hipMemcpyDeviceToHost, c->stream)) ||
 	    !joint_sync(c)) return 1;
 	if (Lmin) memcpy(Lmin, pin, n * 8);
@@ -750,7 +749,7 @@ extern "C" int mdns_joint_advance_dev(mdns_joint *j)
 	if (!j->prepared) { set_error("mdns_joint_advance: no prepare since the state was set"); return 1; }
 	if (j->nrun == 0) return 0;
 	hipLaunchKernelGGL(k_joint_advance, dim3((j->nrun + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-	                   j->st, j->d_running, j->nrun, j->d_argmin, j->d_status);
+	                   j->st, j->d_running.get(), j->nrun, j->d_argmin.get(), j->d_status.get());
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -759,7 +758,7 @@ extern "C" int mdns_joint_advance(mdns_joint *j)
 	Context *c = ctx();
 	if (mdns_joint_advance_dev(j) != 0) return 1;
 	int status = 0;
-	if (!MDNS_HIP(hipMemcpyAsync(&status, j->d_status, sizeof(int), hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(&status, j->d_status.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c)) return 1;
 	if (status) { set_error("mdns_joint_advance: a running data set had an empty shelf"); return 1; }
 	if (j->shelf_bound > 0) j->shelf_bound--;
 	return 0;
@@ -817,7 +816,7 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 	if (B == 0 || M == 0) {
 		// nothing to score: no flag can be set; still hand commit a clean header
 		j->scored_M = M;
-		return MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kZeroInts * sizeof(int), c->stream)) ? 0 : 1;
+		return MDNS_HIP(hipMemsetAsync(j->d_flags.get(), 0, (size_t) kZeroInts * sizeof(int), c->stream)) ? 0 : 1;
 	}
 	const double scale = -0.5 / (noise_level * noise_level);
 	const int filter = gauss_filter_pays(s, M, B);
@@ -825,39 +824,38 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 	bool gemm_form = false;
 	if (!ensure_model(s, (size_t) cols_nx(s->nx) * (B + bt))) return 1;
 	if (filter) {
-		if (!j->d_msq && !MDNS_HIP(hipMalloc((void **) &j->d_msq, (size_t) (MDNS_JOINT_MAX_BATCH + 16) * sizeof(double)))) return 1;
-		if (filter == 2 && !j->d_filter_scratch) {
-			const size_t bytes = (size_t) (MDNS_JOINT_MAX_BATCH + 16) * sizeof(int);
-			if (!MDNS_HIP(hipMalloc((void **) &j->d_filter_scratch, bytes)) || !MDNS_HIP(hipMemsetAsync(j->d_filter_scratch, 0, bytes, c->stream))) return 1;
-		}
+		if (!j->d_msq.get() && !j->d_msq.make(MDNS_JOINT_MAX_BATCH + 16)) return 1;
+		if (filter == 2 && !j->d_filter_scratch.get() && !j->d_filter_scratch.make(MDNS_JOINT_MAX_BATCH + 16, true)) return 1;
 		// (the matrix-core filter with tiled operands wants the templates in its tiling too)
 		double *model_g = nullptr;
-		if (filter == 2 && gauss_mfma_form() == 2 && !d_row_ids && !s->d_yG) {
-			// (the whole set in tiles of 16 rows: made on first use)
-			if (!MDNS_HIP(hipMalloc((void **) &s->d_yG, (size_t) ((s->ndata + 15) / 16) * 16 * tiled16_nx(s->nx) * sizeof(double))) ||
-			    !launch_tile_rows16(s->d_y, s->ld, s->ndata, s->nx, nullptr, s->d_yG)) return 1;
+		if (filter == 2 && gauss_mfma_form() == 2 && !d_row_ids && !s->d_yG.get()) {
+			// (the whole set in tiles of 16 rows: made on first use, installed once its tiles are on their way)
+			DeviceBuffer<double> yG;
+			if (!yG.make((size_t) ((s->ndata + 15) / 16) * 16 * tiled16_nx(s->nx)) ||
+			    !launch_tile_rows16(s->d_y.get(), s->ld, s->ndata, s->nx, nullptr, yG.get())) return 1;
+			s->d_yG = std::move(yG);
 		}
-		if (filter == 2 && gauss_mfma_form() == 2 && (d_row_ids || s->d_yG)) {
+		if (filter == 2 && gauss_mfma_form() == 2 && (d_row_ids || s->d_yG.get())) {
 			if (!s->d_model_g.fit((size_t) ((B + 15) / 16) * 16 * tiled16_nx(s->nx))) return 1;
 			model_g = s->d_model_g.get();
 		}
-		if (!launch_gauss_model_tsq(s->d_x, s->nx, d_params, B, bt, s->d_model.get(), j->d_msq, j->d_flags, kZeroInts, model_g)) return 1;
+		if (!launch_gauss_model_tsq(s->d_x.get(), s->nx, d_params, B, bt, s->d_model.get(), j->d_msq.get(), j->d_flags.get(), kZeroInts, model_g)) return 1;
 		gemm_form = model_g != nullptr;
-	} else if (!launch_gauss_model_t(s->d_x, s->nx, d_params, B, bt, s->d_model.get(), j->d_flags, kZeroInts)) return 1;
-	const double *yT = s->d_yT;
+	} else if (!launch_gauss_model_t(s->d_x.get(), s->nx, d_params, B, bt, s->d_model.get(), j->d_flags.get(), kZeroInts)) return 1;
+	const double *yT = s->d_yT.get();
 	const int *gather = d_row_ids;
 	// a sparse selection, or many candidate tiles over a selection: first a compact replica of
 	// the selected spectra (one coalesced pass) instead of gathering columns in every tile
 	const bool sparse = (size_t) M * 8 < (size_t) s->ndata;
-	const double *yG = s->d_yG;
+	const double *yG = s->d_yG.get();
 	if (d_row_ids && gemm_form) {
 		// (its own compact replica of the selection, in its tiling)
 		if (!s->d_selG.fit((size_t) ((M + 15) / 16) * 16 * tiled16_nx(s->nx))) return 1;
-		if (!launch_tile_rows16(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_selG.get())) return 1;
+		if (!launch_tile_rows16(s->d_y.get(), s->ld, M, s->nx, d_row_ids, s->d_selG.get())) return 1;
 		yG = s->d_selG.get();
 	} else if (d_row_ids && (B >= 128 || sparse || filter == 2)) {
 		if (!ensure_selection(s, (size_t) ((M + 63) / 64) * 64 * cols_nx(s->nx))) return 1;
-		if (!launch_tile_columns(s->d_y, s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
+		if (!launch_tile_columns(s->d_y.get(), s->ld, M, s->nx, d_row_ids, s->d_sel.get())) return 1;
 		yT = s->d_sel.get();
 		gather = nullptr;
 	}
@@ -865,28 +863,26 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 	if (!joint_trail(j, B, M, &trail)) return 1;
 	if (filter == 2) {
 		int *lowest = (int *) &((JointHeader *) j->d_result)->pad;
-		if (!launch_gauss_mfma_filter(s, yT, s->d_model.get(), B, scale, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest,
-		                              j->d_filter_scratch, j->d_result, gemm_form ? yG : nullptr, gemm_form ? s->d_model_g.get() : nullptr)) return 1;
+		if (!launch_gauss_mfma_filter(s, yT, s->d_model.get(), B, scale, d_row_ids, M, j->st.higher, j->d_flags.get(), j->d_msq.get(), trail, lowest,
+		                              j->d_filter_scratch.get(), j->d_result, gemm_form ? yG : nullptr, gemm_form ? s->d_model_g.get() : nullptr)) return 1;
 	} else if (filter) {
 		// issue-bound launch: the guarded filter decides -- same flags and trail, bit for bit.  Its
 		// "lowest flagged candidate so far" lives in the header's spare word (cleared with the flags).
 		int *lowest = (int *) &((JointHeader *) j->d_result)->pad;
-		if (!launch_gauss_cols_filter(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, j->d_msq, trail, lowest)) return 1;
-	} else if (!launch_gauss_cols_accept(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags, trail)) return 1;
+		if (!launch_gauss_cols_filter(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags.get(), j->d_msq.get(), trail, lowest)) return 1;
+	} else if (!launch_gauss_cols_accept(s, yT, s->d_model.get(), bt, B, scale, gather, d_row_ids, M, j->st.higher, j->d_flags.get(), trail)) return 1;
 	j->trail_valid = true;
 	j->last_yT = yT; j->last_gather = gather; j->last_bt = bt; j->last_B = B; j->last_scale = scale;
 	j->scored_M = M;
 	return 0;
 }
 
-extern "C" int *mdns_joint_flags_dev(mdns_joint *j) { return j ? j->d_flags : nullptr; }
+extern "C" int *mdns_joint_flags_dev(mdns_joint *j) { return j ? j->d_flags.get() : nullptr; }
 extern "C" const void *mdns_joint_result_dev(mdns_joint *j) { return j ? j->d_result : nullptr; }
 
 static bool commit_ticket(mdns_joint *j)
 {
-	if (j->d_commit_ticket) return true;
-	Context *c = ctx();
-	return MDNS_HIP(hipMalloc((void **) &j->d_commit_ticket, sizeof(int))) && MDNS_HIP(hipMemsetAsync(j->d_commit_ticket, 0, sizeof(int), c->stream));
+	return j->d_commit_ticket.get() || j->d_commit_ticket.make(1, true);
 }
 
 // the fill words of a chunk's outcome: behind the header in d_result
@@ -911,7 +907,7 @@ static bool commit_from_trail(mdns_joint *j, const int *thr_rows, int M, int B, 
 	}
 	// (its last workgroup fills the mailbox)
 	return commit_ticket(j) && launch_joint_commit_trail(thr_rows, M, B, decides, trail, j->st, j->d_result, result_bits(j), value, j->h_box_dev,
-	                                                     ++j->box_seq, j->d_commit_ticket);
+	                                                     ++j->box_seq, j->d_commit_ticket.get());
 }
 
 static int joint_commit_dev(mdns_joint *j, const int *d_row_ids, int M, bool want_row, const char *who)
@@ -937,11 +933,11 @@ static int joint_commit_dev(mdns_joint *j, const int *d_row_ids, int M, bool wan
 	if (!want_row && j->trail_valid) {
 		// who beats its threshold, and with which likelihood, is in the trail of the accept pass:
 		// nothing is computed again
-		if (!commit_from_trail(j, d_row_ids, M, j->last_B, j->d_flags, 1, false)) return 1;
+		if (!commit_from_trail(j, d_row_ids, M, j->last_B, j->d_flags.get(), 1, false)) return 1;
 	} else {
 		double *Lrow = (double *) (j->d_result + sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8);
 		if (!launch_gauss_cols_commit(j->s, j->last_yT, j->s->d_model.get(), j->last_bt, j->last_B, j->last_scale, j->last_gather,
-		                              d_row_ids, M, j->d_flags, j->st, j->d_result, result_bits(j), Lrow)) return 1;
+		                              d_row_ids, M, j->d_flags.get(), j->st, j->d_result, result_bits(j), Lrow)) return 1;
 		launch_publish(j, c, M);
 	}
 	j->trail_valid = false;                                             // a chunk is committed once
@@ -1018,12 +1014,12 @@ static int joint_stage_and_score(mdns_joint *j, const double *params, int B, dou
 	if (pbytes) memcpy(pin, params, pbytes);
 	if (rbytes) memcpy(pin + pbytes, row_ids, rbytes);
 	if (pbytes + rbytes &&
-	    !MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes + rbytes, hipMemcpyHostToDevice, c->stream))) return 1;
-	j->d_rows = (int *) ((char *) j->d_params + pbytes);
+	    !MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes + rbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	j->d_rows = (int *) ((char *) j->params() + pbytes);
 	j->staged_rows = row_ids != nullptr;
 	j->staged_M = M;
 	j->staged_in_bytes = in_bytes;
-	const int rc = mdns_joint_score_dev(j, j->d_params, B, noise_level, row_ids ? j->d_rows : nullptr, M);
+	const int rc = mdns_joint_score_dev(j, j->params(), B, noise_level, row_ids ? j->d_rows : nullptr, M);
 	j->staged_valid = rc == 0;
 	return rc;
 }
@@ -1131,8 +1127,8 @@ extern "C" int mdns_backend_draw_begin(void *joint, const int *rows, int M)
 	if (!j->prepared) { set_error("mdns_backend_draw_begin: thresholds are not set (call mdns_joint_prepare first)"); return 1; }
 	j->sel_open = false;
 	if (!j->h_in) {
-		if (!MDNS_HIP(hipHostMalloc((void **) &j->h_in, kInParams + (size_t) j->ndata * sizeof(int), hipHostMallocMapped)) ||
-		    !MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_in_dev, j->h_in, 0))) return 1;
+		if (!j->in_block.make(kInParams + (size_t) j->ndata * sizeof(int))) return 1;
+		j->h_in = j->in_block.get(); j->h_in_dev = j->in_block.dev();
 	}
 	if (!j->d_sel_rows.fit((size_t) j->ndata)) return 1;
 	if (rows) {
@@ -1193,7 +1189,7 @@ static SelectionIO selection_for_accept(const mdns_joint *j)
 static int next_chunk_flag(mdns_joint *j, Context *c)
 {
 	if (j->chunk_seq == 0x7fffffff) {
-		if (!MDNS_HIP(hipMemsetAsync(j->d_flags, 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 0;
+		if (!MDNS_HIP(hipMemsetAsync(j->d_flags.get(), 0, (size_t) kFlagInts * sizeof(int), c->stream))) return 0;
 		j->chunk_seq = 1;
 	}
 	return ++j->chunk_seq;
@@ -1212,7 +1208,7 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 		if (!j->h_pin.fit(pbytes)) return 1;
 		char *pin = j->h_pin.get();
 		memcpy(pin, params, pbytes);
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+		if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 		const int *d_rows;
 		if (!selection_to_device(j, c, &d_rows)) return 1;
 		if (!j->d_dense.fit(n)) return 1;
@@ -1221,12 +1217,12 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 			// (pageable source: the runtime stages it and returns when the caller's buffer is free)
 			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 		}
-		if (mdns_lines_loglike_batch_dev(j->s, j->d_params, B, d_rows, M, j->d_dense.get()) != 0) return 1;
+		if (mdns_lines_loglike_batch_dev(j->s, j->params(), B, d_rows, M, j->d_dense.get()) != 0) return 1;
 		const int flag = next_chunk_flag(j, c);
 		if (!flag) return 1;
 		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
 		                   j->d_dense.get(), jitter ? (const double *) j->d_jitter.get() : nullptr, B, M, d_rows, (const double *) j->st.higher,
-		                   j->d_flags, flag, (JointHeader *) j->d_result);
+		                   j->d_flags.get(), flag, (JointHeader *) j->d_result);
 		out->path = 1; out->flag = flag;
 		return 0;
 	}
@@ -1244,7 +1240,7 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 		const int flag = next_chunk_flag(j, c);
 		if (!flag) return 1;
 		if (!launch_chunk_accept(j->s, (const double *) j->h_in_dev, B, scale, rows.in, rows.out, M, j->st.higher,
-		                         j->d_flags, flag, trail, j->d_result)) return 1;
+		                         j->d_flags.get(), flag, trail, j->d_result)) return 1;
 		if (j->sel_rows) j->sel_on_device = true;
 		out->path = 2; out->flag = flag;
 		return 0;
@@ -1252,10 +1248,10 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 	if (!j->h_pin.fit(pbytes)) return 1;
 	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_params, pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;
-	if (mdns_joint_score_dev(j, j->d_params, B, j->noise_level, d_rows, M) != 0) return 1;
+	if (mdns_joint_score_dev(j, j->params(), B, j->noise_level, d_rows, M) != 0) return 1;
 	out->path = 3; out->flag = 1;
 	return 0;
 }
@@ -1277,8 +1273,8 @@ static int backend_commit(mdns_joint *j, Context *c, const ChunkScore &sc, const
 		if (!commit_from_trail(j, thr_rows, M, sc.B, decides, value, true)) return 1;
 	} else {
 		// the lane kernels' flags are 0 / 1 themselves: votes go back into them
-		if (decides != j->d_flags &&
-		    !MDNS_HIP(hipMemcpyAsync(j->d_flags, decides, (size_t) sc.B * sizeof(int), hipMemcpyDeviceToDevice, c->stream))) return 1;
+		if (decides != j->d_flags.get() &&
+		    !MDNS_HIP(hipMemcpyAsync(j->d_flags.get(), decides, (size_t) sc.B * sizeof(int), hipMemcpyDeviceToDevice, c->stream))) return 1;
 		if (joint_commit_dev(j, thr_rows, M, false, who) != 0) return 1;
 	}
 	j->box_pending = true;
@@ -1310,7 +1306,7 @@ extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B,
 	if (B == 0 || M == 0) return 0;
 	ChunkScore sc;
 	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_chunk") != 0) return 1;
-	if (backend_commit(j, c, sc, j->d_flags, sc.flag, "mdns_backend_draw_chunk") != 0) return 1;
+	if (backend_commit(j, c, sc, j->d_flags.get(), sc.flag, "mdns_backend_draw_chunk") != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
 }
 
@@ -1329,9 +1325,9 @@ static int draw_curves_dev(mdns_joint *j, Context *c, const double *d_curves, in
 	const int flag = next_chunk_flag(j, c);
 	if (!flag) return 1;
 	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-	                   j->d_dense.get(), d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags, flag, (JointHeader *) j->d_result);
+	                   j->d_dense.get(), d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags.get(), flag, (JointHeader *) j->d_result);
 	const ChunkScore sc = {1, B, flag};
-	if (backend_commit(j, c, sc, j->d_flags, flag, who) != 0) return 1;
+	if (backend_commit(j, c, sc, j->d_flags.get(), flag, who) != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
 }
 
@@ -1421,13 +1417,10 @@ extern "C" int mdns_backend_chain_begin(void *joint, void *region, const mdns_ch
 		return 1;
 	}
 	if (!j->h_chain) {
-		if (!MDNS_HIP(hipHostMalloc((void **) &j->h_chain, sizeof(ChainBox), hipHostMallocMapped)) ||
-		    !MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_chain_dev, j->h_chain, 0)) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_chain_props, (size_t) kChainMost * kChainDim * sizeof(double))) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_chain_counts, (size_t) kChainMost * sizeof(int))) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_chain_ticket, sizeof(int))) ||
-		    !MDNS_HIP(hipMemsetAsync(j->d_chain_ticket, 0, sizeof(int), c->stream))) return 1;
-		memset(j->h_chain, 0, sizeof(ChainBox));
+		if (!all_or_none(j->chain_box.make(sizeof(ChainBox)) && j->d_chain_props.make((size_t) kChainMost * kChainDim) &&
+		                 j->d_chain_counts.make(kChainMost) && j->d_chain_ticket.make(1, true),
+		                 j->chain_box, j->d_chain_props, j->d_chain_counts, j->d_chain_ticket)) return 1;
+		j->h_chain = (ChainBox *) j->chain_box.get(); j->h_chain_dev = (ChainBox *) j->chain_box.dev();
 	}
 	const int M = j->sel_M;
 	// the chunk rides along when the problem is the Gaussian line with the library's own prior
@@ -1451,25 +1444,25 @@ extern "C" int mdns_backend_chain_begin(void *joint, void *region, const mdns_ch
 	j->h_chain->nkept = -1; j->h_chain->B = -1;
 	j->chain_n = rq->n;
 	if (!full) {
-		const CountMail mail = {j->d_chain_ticket, &j->h_chain_dev->seq, ++j->chain_seq};
-		if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props, j->d_chain_counts, &mail)) return 1;
+		const CountMail mail = {j->d_chain_ticket.get(), &j->h_chain_dev->seq, ++j->chain_seq};
+		if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props.get(), j->d_chain_counts.get(), &mail)) return 1;
 		j->chain_state = 1;
 		return 0;
 	}
 	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
-	if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props, j->d_chain_counts, nullptr)) return 1;
+	if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props.get(), j->d_chain_counts.get(), nullptr)) return 1;
 	JointTrail trail;
 	if (!joint_trail(j, limit, M, &trail)) return 1;
 	const SelectionIO rows = selection_for_accept(j);
 	const double scale = -0.5 / (j->noise_level * j->noise_level);
 	const int flag = next_chunk_flag(j, c);
 	if (!flag) return 1;
-	if (!launch_chain_accept(j->s, spec, j->d_chain_props, j->d_chain_counts, j->h_chain_dev, scale, rows.in, rows.out, M,
-	                         j->st.higher, j->d_flags, flag, trail, j->d_result)) return 1;
+	if (!launch_chain_accept(j->s, spec, j->d_chain_props.get(), j->d_chain_counts.get(), j->h_chain_dev, scale, rows.in, rows.out, M,
+	                         j->st.higher, j->d_flags.get(), flag, trail, j->d_result)) return 1;
 	if (j->sel_rows) j->sel_on_device = true;
 	// (committed as a two-launch chunk of `limit` candidates: the first min(kept, limit) proposals)
 	const ChunkScore sc = {2, limit, flag};
-	if (backend_commit(j, c, sc, j->d_flags, flag, "mdns_backend_chain_begin") != 0) return 1;
+	if (backend_commit(j, c, sc, j->d_flags.get(), flag, "mdns_backend_chain_begin") != 0) return 1;
 	j->chain_state = 2;
 	return 0;
 }
@@ -1491,7 +1484,7 @@ extern "C" int mdns_backend_chain_end(void *joint, void *region, int *counts, in
 		case Wait::timeout: set_error("chain: no membership counts within MDNS_POLL_TIMEOUT_S"); return 1;
 		case Wait::failed: set_error("chain: the membership count failed: %s", hipGetErrorString(e)); return 1;
 		case Wait::empty:
-			(void) hipMemsetAsync(j->d_chain_ticket, 0, sizeof(int), c->stream);
+			(void) hipMemsetAsync(j->d_chain_ticket.get(), 0, sizeof(int), c->stream);
 			set_error("chain: the membership count finished without a result");
 			return 1;
 		}
@@ -1522,7 +1515,7 @@ __global__ void k_flags_to_votes(const int *__restrict__ flags, int value, int *
 	if (b < B) votes[b] = flags[b] == value ? 1 : 0;
 }
 
-extern "C" int *mdns_joint_votes_dev(mdns_joint *j) { return j ? j->d_votes : nullptr; }
+extern "C" int *mdns_joint_votes_dev(mdns_joint *j) { return j ? j->d_votes.get() : nullptr; }
 
 // first half: the score, then one 0 / 1 vote per candidate from its accept flags
 extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B, const double *jitter)
@@ -1533,14 +1526,14 @@ extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B,
 	if (!j->sel_open) { set_error("mdns_backend_draw_score: no draw begun"); return 1; }
 	const int M = j->sel_M;
 	if (!check_draw(j, B, M, "mdns_backend_draw_score")) return 1;
-	if (!j->d_votes && !MDNS_HIP(hipMalloc((void **) &j->d_votes, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int)))) return 1;
+	if (!j->d_votes.get() && !j->d_votes.make(MDNS_JOINT_MAX_BATCH)) return 1;
 	j->half = {0, B, 0};
-	if (!MDNS_HIP(hipMemsetAsync(j->d_votes, 0, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int), c->stream))) return 1;
+	if (!MDNS_HIP(hipMemsetAsync(j->d_votes.get(), 0, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int), c->stream))) return 1;
 	if (B == 0 || M == 0) { j->half.path = -1; return 0; }          // (nothing of this rank's is selected: no vote)
 	ChunkScore sc;
 	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_score") != 0) return 1;
 	j->half = sc;
-	hipLaunchKernelGGL(k_flags_to_votes, dim3((B + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const int *) j->d_flags, sc.flag, j->d_votes, B);
+	hipLaunchKernelGGL(k_flags_to_votes, dim3((B + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const int *) j->d_flags.get(), sc.flag, j->d_votes.get(), B);
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
 }
 
@@ -1559,11 +1552,11 @@ extern "C" int mdns_backend_draw_commit(void *joint, int *accepted, unsigned lon
 		// nothing of this handle's was scored: the accepted candidate is whoever the votes name
 		const int B = sc.B;
 		std::vector<int> votes((size_t) (B > 0 ? B : 1), 0);
-		if (B > 0 && (!MDNS_HIP(hipMemcpyAsync(votes.data(), j->d_votes, (size_t) B * sizeof(int), hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c))) return 1;
+		if (B > 0 && (!MDNS_HIP(hipMemcpyAsync(votes.data(), j->d_votes.get(), (size_t) B * sizeof(int), hipMemcpyDeviceToHost, c->stream)) || !joint_sync(c))) return 1;
 		for (int b = 0; b < B; b++) if (votes[b]) { *accepted = b; break; }
 		return 0;
 	}
-	if (backend_commit(j, c, sc, j->d_votes, 1, "mdns_backend_draw_commit") != 0) return 1;
+	if (backend_commit(j, c, sc, j->d_votes.get(), 1, "mdns_backend_draw_commit") != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
 }
 
@@ -1580,25 +1573,25 @@ static int band_launch(mdns_joint *j, bool filtered)
 	Context *c = ctx();
 	const int B = j->band_B, M = j->sel_M;
 	const int *d_rows = selection_rows(j);
-	const double *d_p = j->d_bound, *d_b = j->d_bound + (size_t) B * j->nparams;
+	const double *d_p = j->d_bound.get(), *d_b = j->d_bound.get() + (size_t) B * j->nparams;
 	if (filtered) {
 		const int ldm = model_ld(j->s->nx) + 16;            // (not a power of two: mdns_k2gemm.hip, muse_filter_ld)
 		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;
-		const MuseBandOut out = {&j->d_band->counter, j->d_band->clear, j->d_band->maybe, j->d_band->pair_b, j->d_band->pair_k,
-		                         j->d_band->pair_L, j->d_band->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
+		const MuseBandOut out = {&j->d_band.get()->counter, j->d_band.get()->clear, j->d_band.get()->maybe, j->d_band.get()->pair_b, j->d_band.get()->pair_k,
+		                         j->d_band.get()->pair_L, j->d_band.get()->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_filter(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
-	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w && j->s->d_x && j->s->continuum == 0) {
+	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w.get() && j->s->d_x.get() && j->s->continuum == 0) {
 		// small chunks (pairs of candidates per workgroup): templates, then ONE kernel that scores, votes and publishes
 		const int ldm = model_ld(j->s->nx);
 		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;
-		const MuseBandFused fused = {j->d_band, j->h_band_dev, ++j->band_seq, j->st.higher, d_b, &((JointHeader *) j->d_result)->status};
+		const MuseBandFused fused = {j->d_band.get(), j->h_band_dev, ++j->band_seq, j->st.higher, d_b, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_rows(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->d_dense.get(), 0, &fused)) return 1;
 	} else {
 		if (mdns_lines_loglike_batch_dev(j->s, d_p, B, d_rows, M, j->d_dense.get()) != 0) return 1;
 		hipLaunchKernelGGL(k_joint_band, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream, (const double *) j->d_dense.get(),
-		                   d_b, B, M, d_rows, (const double *) j->st.higher, j->d_band, (JointHeader *) j->d_result, j->h_band_dev, ++j->band_seq);
+		                   d_b, B, M, d_rows, (const double *) j->st.higher, j->d_band.get(), (JointHeader *) j->d_result, j->h_band_dev, ++j->band_seq);
 	}
-	if (filtered) hipLaunchKernelGGL(k_joint_band_publish, dim3(1), dim3(kBlock), 0, c->stream, j->d_band, B, j->h_band_dev, ++j->band_seq);
+	if (filtered) hipLaunchKernelGGL(k_joint_band_publish, dim3(1), dim3(kBlock), 0, c->stream, j->d_band.get(), B, j->h_band_dev, ++j->band_seq);
 	if (!MDNS_HIP(hipGetLastError())) return 1;
 	j->band_exact = !filtered;
 	return 0;
@@ -1617,12 +1610,9 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 	const int M = j->sel_M;
 	if (!check_draw(j, B, M, "mdns_backend_draw_band") || B == 0 || M == 0) return 1;
 	if (!j->h_band) {
-		if (!MDNS_HIP(hipHostMalloc((void **) &j->h_band, sizeof(BandBox), hipHostMallocMapped)) ||
-		    !MDNS_HIP(hipHostGetDevicePointer((void **) &j->h_band_dev, j->h_band, 0)) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_band, sizeof(BandScratch))) ||
-		    !MDNS_HIP(hipMemsetAsync(j->d_band, 0, sizeof(BandScratch), c->stream)) ||
-		    !MDNS_HIP(hipMalloc((void **) &j->d_bound, (kBandRowAt + j->ndata) * sizeof(double)))) return 1;
-		memset(j->h_band, 0, sizeof(BandBox));
+		if (!all_or_none(j->band_box.make(sizeof(BandBox)) && j->d_band.make(1, true) && j->d_bound.make(kBandRowAt + j->ndata),
+		                 j->band_box, j->d_band, j->d_bound)) return 1;
+		j->h_band = (BandBox *) j->band_box.get(); j->h_band_dev = (BandBox *) j->band_box.dev();
 	}
 	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
 	const size_t pbytes = (size_t) B * j->nparams * sizeof(double), bbytes = (size_t) B * sizeof(double), n = (size_t) B * M;
@@ -1630,7 +1620,7 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 	char *pin = j->h_pin.get();
 	memcpy(pin, params, pbytes);
 	memcpy(pin + pbytes, bound, bbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_bound, pin, pbytes + bbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->d_bound.get(), pin, pbytes + bbytes, hipMemcpyHostToDevice, c->stream))) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;              // (band_launch takes it from the handle)
 	if (!j->d_dense.fit(n)) return 1;
@@ -1710,7 +1700,7 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 		muse_filter_note(2);
 	}
 	j->band_B = 0;
-	double *d_row = j->d_bound + kBandRowAt;
+	double *d_row = j->d_bound.get() + kBandRowAt;
 	if (!j->h_pin.fit((size_t) M * sizeof(double))) return 1;
 	char *pin = j->h_pin.get();
 	memcpy(pin, jitter_row, (size_t) M * sizeof(double));

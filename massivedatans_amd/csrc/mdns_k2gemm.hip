@@ -357,7 +357,7 @@ bool muse_filter_applies(const mdns_spectra *s, int B, int M)
 		const char *forced = getenv("MDNS_K2_FILTER");
 		g_filter_mode = forced && forced[0] == '0' ? 0 : (forced && forced[0] == '1' ? 1 : -1);
 	}
-	if (!s || !s->d_w || !s->d_x || s->nx < 1 || B < 1 || M < 1) return false;
+	if (!s || !s->d_w.get() || !s->d_x.get() || s->nx < 1 || B < 1 || M < 1) return false;
 	if (s->continuum > 0) return false;          // (its rounding bound is that of K2's formula, not of the continuum's)
 	if (g_filter_mode == 0) return false;
 	if (g_filter_mode == 1) return true;
@@ -373,23 +373,22 @@ int muse_filter_ld(int nx) { return ((nx + 15) & ~15) + 16; }
 
 bool muse_filter_prepare(mdns_spectra *s)
 {
-	if (s->d_fyw) return true;
+	if (s->d_fyw.get()) return true;
 	Context *c = ctx();
 	const int ldf = muse_filter_ld(s->nx);
 	const size_t elems = (size_t) s->ndata * ldf, telems = (size_t) ((s->ndata + 15) / 16) * 16 * ldf;
-	double *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // y w, w (row-major), y w, w (tiled), A
-	const size_t want[5] = {elems, elems, telems, telems, (size_t) s->ndata};
-	bool ok = true;
-	for (int t = 0; t < 5 && ok; t++) ok = MDNS_HIP(hipMalloc((void **) &buf[t], (want[t] ? want[t] : 1) * sizeof(double)));
-	// (the rows past the last one of the last tile multiply as zeros)
-	for (int t = 2; t < 4 && ok; t++) ok = MDNS_HIP(hipMemsetAsync(buf[t], 0, (telems ? telems : 1) * sizeof(double), c->stream));
+	// made in locals, installed when all five are filled: y w, w (row-major), y w, w (tiled: the rows past the last one
+	// of the last tile multiply as zeros), A
+	DeviceBuffer<double> fyw, fw, fyw_t, fw_t, fa;
+	bool ok = fyw.make(elems) && fw.make(elems) && fyw_t.make(telems, true) && fw_t.make(telems, true) && fa.make((size_t) s->ndata);
 	if (ok && s->ndata > 0) {
-		hipLaunchKernelGGL(k_muse_filter_prepare, dim3(s->ndata), dim3(256), 0, c->stream, (const double *) s->d_y, (const double *) s->d_w,
-		                   s->ld, s->nx, buf[0], buf[1], ldf, buf[2], buf[3], buf[4]);
+		hipLaunchKernelGGL(k_muse_filter_prepare, dim3(s->ndata), dim3(256), 0, c->stream, (const double *) s->d_y.get(), (const double *) s->d_w.get(),
+		                   s->ld, s->nx, fyw.get(), fw.get(), ldf, fyw_t.get(), fw_t.get(), fa.get());
 		ok = MDNS_HIP(hipGetLastError());
 	}
-	if (!ok) { for (double *b : buf) if (b) (void) hipFree(b); return false; }
-	s->d_fyw = buf[0]; s->d_fw = buf[1]; s->fw_owned = true; s->d_fyw_t = buf[2]; s->d_fw_t = buf[3]; s->d_fa = buf[4]; s->ldf = ldf;
+	if (!ok) return false;
+	s->d_fyw = std::move(fyw); s->d_fw = std::move(fw); s->d_fyw_t = std::move(fyw_t); s->d_fw_t = std::move(fw_t); s->d_fa = std::move(fa);
+	s->ldf = ldf;
 	muse_filter_note(3);
 	return true;
 }
@@ -431,7 +430,7 @@ bool launch_muse_filter(mdns_spectra *s, const double *d_model, int ldm, int B, 
 		}
 		note_kernel(1, tiled ? "k_muse_gemm_band_sk<%d, tiled>" : "k_muse_gemm_band_sk<%d>", nc);
 #define K2_SK(NC, T) hipLaunchKernelGGL((k_muse_gemm_band_sk<NC, T>), dim3((unsigned) P), dim3(512), 0, c->stream, \
-		(const double *) (T ? s->d_fyw_t : s->d_fyw), (const double *) (T ? s->d_fw_t : s->d_fw), s->ldf, (const double *) s->d_fa, d_templ, ldm, B, d_rows, M, bt, \
+		(const double *) (T ? s->d_fyw_t.get() : s->d_fyw.get()), (const double *) (T ? s->d_fw_t.get() : s->d_fw.get()), s->ldf, (const double *) s->d_fa.get(), d_templ, ldm, B, d_rows, M, bt, \
 		d_higher, d_bound, gamma, out, c->sk_scratch.get(), c->sk_delivered.get(), (const double *) c->sk_zeros.get())
 		{
 			ProfileScope prof(1);
@@ -449,7 +448,7 @@ bool launch_muse_filter(mdns_spectra *s, const double *d_model, int ldm, int B, 
 	while (kw > 4 && (s->ldf >> 4) - 1 < 2 * kw) kw >>= 1;
 	note_kernel(1, "k_muse_gemm_band<%d, %d>", nc, kw);
 #define K2_LAUNCH(NC, KW) hipLaunchKernelGGL((k_muse_gemm_band<NC, KW>), dim3(rt, bt), dim3(64 * KW), 0, c->stream, \
-		(const double *) s->d_fyw, (const double *) s->d_fw, s->ldf, (const double *) s->d_fa, d_model, ldm, B, d_rows, M, d_higher, d_bound, gamma, out)
+		(const double *) s->d_fyw.get(), (const double *) s->d_fw.get(), s->ldf, (const double *) s->d_fa.get(), d_model, ldm, B, d_rows, M, d_higher, d_bound, gamma, out)
 #define K2_PICK(NC) do { if (kw == 4) K2_LAUNCH(NC, 4); else K2_LAUNCH(NC, 8); } while (0)
 	{
 		ProfileScope prof(1);
@@ -470,7 +469,7 @@ extern "C" int mdns_muse_filter_dev(mdns_spectra *s, const double *d_ypred, int 
 {
 	using namespace mdns;
 	if (!ctx() || !s || !d_ypred || !d_thr || !d_bound || !d_out || B < 1 || M < 1 || M > s->ndata) { set_error("mdns_muse_filter_dev: bad arguments"); return 1; }
-	if (!s->d_w) { set_error("spectra were created without variances"); return 1; }
+	if (!s->d_w.get()) { set_error("spectra were created without variances"); return 1; }
 	if (s->continuum > 0) { set_error("mdns_muse_filter_dev: a continuum is set on these spectra (the filter bounds K2 without one)"); return 1; }
 	const int ldm = model_ld(s->nx) + 16;
 	if (!ensure_model(s, (size_t) B * ldm) || !launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;

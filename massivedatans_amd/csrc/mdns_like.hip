@@ -1232,7 +1232,7 @@ int gauss_filter_pays(const mdns_spectra *s, int M, int B)
 	// 49.5 us against 43.9 for the three / two kernels).  It is the default where those passes are
 	// small beside the product: 122 us against 189 at 50 000 x 256, 101 against 162 at 10 000 x 1024.
 	static const char *forced = getenv("MDNS_K1_FILTER");
-	if (s->d_ysq == nullptr || gauss_cols_tile(M, B) < 8) return 0;
+	if (s->d_ysq.get() == nullptr || gauss_cols_tile(M, B) < 8) return 0;
 	if (forced && forced[0] == '1') return 1;
 	if (forced && forced[0] == '0') return 0;
 	// the exact re-score behind the matrix-core forms (k_exact_list) holds a spectrum in at most 32 stages of 8 channels,
@@ -1300,7 +1300,7 @@ bool launch_gauss_cols_filter(const mdns_spectra *s, const double *d_yT, const d
 	ProfileScope prof(0);
 	note_kernel(0, "k_gauss_cols_filter<%d>", bt);
 #define FILTER_LAUNCH(BT) hipLaunchKernelGGL((k_gauss_cols_filter<BT>), dim3(blocks), dim3(256), 0, c->stream, \
-	d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_rows, d_thr_rows, M, ntiles, nq_xcd, nbt, cu_slots, d_higher, (const double *) s->d_ysq, d_flags, trail, d_lowest)
+	d_yT, nxp, s->nx, d_model_t, d_msq, B, scale, d_rows, d_thr_rows, M, ntiles, nq_xcd, nbt, cu_slots, d_higher, (const double *) s->d_ysq.get(), d_flags, trail, d_lowest)
 	if (bt == 16) FILTER_LAUNCH(16); else FILTER_LAUNCH(8);
 #undef FILTER_LAUNCH
 	return launched("k_gauss_cols_filter");
@@ -1337,10 +1337,10 @@ bool launch_muse_model(const mdns_spectra *s, const double *d_params, int B, dou
 	Context *c = ctx();
 	dim3 grid((ldm + kBlock * kMuseModelPer - 1) / (kBlock * kMuseModelPer), B);
 	if (s->nlines == 0) {
-		hipLaunchKernelGGL(k_muse3_model, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x, s->nx, d_params, d_model, ldm);
+		hipLaunchKernelGGL(k_muse3_model, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x.get(), s->nx, d_params, d_model, ldm);
 		return launched("k_muse3_model");
 	}
-#define LINES_LAUNCH(G) case G: hipLaunchKernelGGL(k_lines_model<G>, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x, s->nx, d_params, d_model, ldm, s->lines); break
+#define LINES_LAUNCH(G) case G: hipLaunchKernelGGL(k_lines_model<G>, grid, dim3(kBlock), 0, c->stream, (const double *) s->d_x.get(), s->nx, d_params, d_model, ldm, s->lines); break
 	switch (s->nlines) {
 	LINES_LAUNCH(1); LINES_LAUNCH(2); LINES_LAUNCH(3); LINES_LAUNCH(4); LINES_LAUNCH(5); LINES_LAUNCH(6);
 	default: set_error("k_lines_model: %d lines (1..%d)", s->nlines, kLinesMax); return false;
@@ -1398,10 +1398,10 @@ static void launch_gauss_rows_t(const mdns_spectra *s, const double *d_model, in
 	note_kernel(0, "k_gauss_rows<%d, %d, %d, %s>", NP, BT, R, B <= BT ? "true" : "false");
 	if (B <= BT)
 		hipLaunchKernelGGL((k_gauss_rows<NP, BT, R, true>), dim3(blocks), dim3(kBlock), 0, stream,
-		                   s->d_y, s->ld, s->nx, d_model, ldm, B, scale, d_rows, M, d_out);
+		                   s->d_y.get(), s->ld, s->nx, d_model, ldm, B, scale, d_rows, M, d_out);
 	else
 		hipLaunchKernelGGL((k_gauss_rows<NP, BT, R, false>), dim3(blocks), dim3(kBlock), 0, stream,
-		                   s->d_y, s->ld, s->nx, d_model, ldm, B, scale, d_rows, M, d_out);
+		                   s->d_y.get(), s->ld, s->nx, d_model, ldm, B, scale, d_rows, M, d_out);
 }
 
 bool launch_gauss_rows(const mdns_spectra *s, const double *d_model, int ldm, int B, double scale,
@@ -1423,7 +1423,7 @@ bool launch_gauss_rows(const mdns_spectra *s, const double *d_model, int ldm, in
 		int blocks = (M + 3) / 4;
 		if (blocks > c->num_cus * 8) blocks = c->num_cus * 8;
 		hipLaunchKernelGGL((k_gauss_rows_generic<4>), dim3(blocks), dim3(kBlock), 0, c->stream,
-		                   s->d_y, s->ld, nx, d_model, ldm, B, scale, d_rows, M, d_out);
+		                   s->d_y.get(), s->ld, nx, d_model, ldm, B, scale, d_rows, M, d_out);
 	}
 	return launched("k_gauss_rows");
 }
@@ -1470,18 +1470,18 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
 	note_kernel(1, two_rows ? "k_muse_rows2<%d>" : (variant == 1 ? "k_muse_rows<%d, 2>" : "k_muse_rows<%d, 1>"),
 	            nx <= 512 ? 1 : nx <= 1024 ? 2 : nx <= 2048 ? 4 : 8);
 #define MUSE_LAUNCH(NP) do { if (two_rows) hipLaunchKernelGGL((k_muse_rows2<NP>), dim3((blocks + 1) / 2), dim3(kBlock), 0, c->stream, \
-		s->d_y, s->d_w, s->ld, nx, d_model, ldm, B, d_rows, M, d_out); \
+		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out); \
 	else if (variant == 1) hipLaunchKernelGGL((k_muse_rows<NP, 2>), dim3(blocks, gy), dim3(kBlock), 0, c->stream, \
-		s->d_y, s->d_w, s->ld, nx, d_model, ldm, B, d_rows, M, d_out, bchunk, fused); \
+		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out, bchunk, fused); \
 	else hipLaunchKernelGGL((k_muse_rows<NP, 1>), dim3(blocks), dim3(kBlock), 0, c->stream, \
-		s->d_y, s->d_w, s->ld, nx, d_model, ldm, B, d_rows, M, d_out, B, none); } while (0)
+		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out, B, none); } while (0)
 	if (nx <= 512) MUSE_LAUNCH(1);
 	else if (nx <= 1024) MUSE_LAUNCH(2);
 	else if (nx <= 2048) MUSE_LAUNCH(4);
 	else if (nx <= 4096) MUSE_LAUNCH(8);
 	else
 		hipLaunchKernelGGL(k_muse_rows_generic, dim3(blocks), dim3(kBlock), 0, c->stream,
-		                   s->d_y, s->d_w, s->ld, nx, d_model, ldm, B, d_rows, M, d_out);
+		                   s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out);
 #undef MUSE_LAUNCH
 	return launched("k_muse_rows");
 }

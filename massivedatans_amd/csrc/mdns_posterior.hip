@@ -413,15 +413,15 @@ enum { kTimeMoments, kTimeVar, kTimeQuant, kTimeResample, kTimePhases };
 
 struct mdns_posterior {
 	int nsamp = 0, ndata = 0, ndim = 0;
-	double *d_w = nullptr, *d_L = nullptr, *d_x = nullptr;
+	DeviceBuffer<double> d_w, d_L, d_x;
 	int nslices = 1, rows_per_slice = 1;
 	// per data set: max of lw, sum of exp(lw - max), rows in F, row of the largest L, and the summaries
-	double *d_m = nullptr, *d_S = nullptr, *d_lognorm = nullptr, *d_ess = nullptr, *d_mean = nullptr, *d_std = nullptr;
-	int *d_n = nullptr, *d_imax = nullptr;
+	DeviceBuffer<double> d_m, d_S, d_lognorm, d_ess, d_mean, d_std;
+	DeviceBuffer<int> d_n, d_imax;
 	bool normed = false;
 	// slice partials: max pass (m | L of the largest | count | row), sums [S][ndata][2 + ndim]
-	double *d_pm = nullptr, *d_pL = nullptr, *d_part = nullptr;
-	int *d_pn = nullptr, *d_parg = nullptr;
+	DeviceBuffer<double> d_pm, d_pL, d_part;
+	DeviceBuffer<int> d_pn, d_parg;
 	hipEvent_t ev[kTimePhases + 1] = {};
 	double ms[kTimePhases] = {};
 };
@@ -440,14 +440,14 @@ bool post_norm(mdns_posterior *h, hipStream_t st)
 {
 	if (h->normed) return true;
 	const dim3 grid((h->ndata + kWave - 1) / kWave, h->nslices), small((h->ndata + 255) / 256);
-	hipLaunchKernelGGL(k_post_max, grid, dim3(kWave), 0, st, h->d_w, h->d_L, h->nsamp, h->ndata, h->rows_per_slice,
-	                   h->d_pm, h->d_pn, h->d_pL, h->d_parg);
-	hipLaunchKernelGGL(k_post_max_combine, small, dim3(256), 0, st, h->d_pm, h->d_pn, h->d_pL, h->d_parg, h->nslices, h->ndata,
-	                   h->d_m, h->d_n, h->d_imax);
-	hipLaunchKernelGGL(k_post_sums, grid, dim3(kWave), 0, st, h->d_w, h->d_L, h->d_x, h->nsamp, h->ndata, h->ndim,
-	                   h->rows_per_slice, h->d_m, h->d_part);
-	hipLaunchKernelGGL(k_post_sums_combine, small, dim3(256), 0, st, h->d_part, h->nslices, h->ndata, h->ndim, h->d_m, h->d_n,
-	                   h->d_S, h->d_lognorm, h->d_ess, h->d_mean);
+	hipLaunchKernelGGL(k_post_max, grid, dim3(kWave), 0, st, h->d_w.get(), h->d_L.get(), h->nsamp, h->ndata, h->rows_per_slice,
+	                   h->d_pm.get(), h->d_pn.get(), h->d_pL.get(), h->d_parg.get());
+	hipLaunchKernelGGL(k_post_max_combine, small, dim3(256), 0, st, h->d_pm.get(), h->d_pn.get(), h->d_pL.get(), h->d_parg.get(), h->nslices, h->ndata,
+	                   h->d_m.get(), h->d_n.get(), h->d_imax.get());
+	hipLaunchKernelGGL(k_post_sums, grid, dim3(kWave), 0, st, h->d_w.get(), h->d_L.get(), h->d_x.get(), h->nsamp, h->ndata, h->ndim,
+	                   h->rows_per_slice, h->d_m.get(), h->d_part.get());
+	hipLaunchKernelGGL(k_post_sums_combine, small, dim3(256), 0, st, h->d_part.get(), h->nslices, h->ndata, h->ndim, h->d_m.get(), h->d_n.get(),
+	                   h->d_S.get(), h->d_lognorm.get(), h->d_ess.get(), h->d_mean.get());
 	if (!post_launch_ok("mdns_posterior (moments)")) return false;
 	h->normed = true;
 	return true;
@@ -456,10 +456,10 @@ bool post_norm(mdns_posterior *h, hipStream_t st)
 bool post_var(mdns_posterior *h, hipStream_t st)
 {
 	const dim3 grid((h->ndata + kWave - 1) / kWave, h->nslices), small((h->ndata + 255) / 256);
-	hipLaunchKernelGGL(k_post_var, grid, dim3(kWave), 0, st, h->d_w, h->d_L, h->d_x, h->nsamp, h->ndata, h->ndim,
-	                   h->rows_per_slice, h->d_m, h->d_mean, h->d_part);
-	hipLaunchKernelGGL(k_post_var_combine, small, dim3(256), 0, st, h->d_part, h->nslices, h->ndata, h->ndim, h->d_S, h->d_n,
-	                   h->d_std);
+	hipLaunchKernelGGL(k_post_var, grid, dim3(kWave), 0, st, h->d_w.get(), h->d_L.get(), h->d_x.get(), h->nsamp, h->ndata, h->ndim,
+	                   h->rows_per_slice, h->d_m.get(), h->d_mean.get(), h->d_part.get());
+	hipLaunchKernelGGL(k_post_var_combine, small, dim3(256), 0, st, h->d_part.get(), h->nslices, h->ndata, h->ndim, h->d_S.get(), h->d_n.get(),
+	                   h->d_std.get());
 	return post_launch_ok("mdns_posterior (std)");
 }
 
@@ -504,9 +504,6 @@ extern "C" void mdns_posterior_destroy(mdns_posterior *h)
 	if (!h) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
-	void *bufs[] = {h->d_w, h->d_L, h->d_x, h->d_m, h->d_S, h->d_lognorm, h->d_ess, h->d_mean, h->d_std, h->d_n, h->d_imax,
-	                h->d_pm, h->d_pL, h->d_part, h->d_pn, h->d_parg};
-	for (void *b : bufs) if (b) (void) hipFree(b);
 	for (hipEvent_t e : h->ev) if (e) (void) hipEventDestroy(e);
 	delete h;
 }
@@ -531,27 +528,16 @@ extern "C" mdns_posterior *mdns_posterior_create(const double *w, const double *
 	bool ok = true;
 	for (hipEvent_t &e : h->ev) ok = ok && MDNS_HIP(hipEventCreate(&e));
 	ok = ok &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_w, ns * nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_L, ns * nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_x, ns * nd * ndim * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_m, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_S, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_lognorm, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_ess, nd * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_mean, nd * ndim * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_std, nd * ndim * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_n, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_imax, nd * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_pm, ps * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_pL, ps * sizeof(double))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_pn, ps * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_parg, ps * sizeof(int))) &&
-	    MDNS_HIP(hipMalloc((void **) &h->d_part, ps * (2 + ndim) * sizeof(double))) &&
-	    MDNS_HIP(hipMemcpyAsync(h->d_w, w, ns * nd * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
-	    MDNS_HIP(hipMemcpyAsync(h->d_L, L, ns * nd * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
-	    MDNS_HIP(hipMemcpyAsync(h->d_x, x, ns * nd * ndim * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    h->d_w.make(ns * nd) && h->d_L.make(ns * nd) && h->d_x.make(ns * nd * ndim) &&
+	    h->d_m.make(nd) && h->d_S.make(nd) && h->d_lognorm.make(nd) && h->d_ess.make(nd) &&
+	    h->d_mean.make(nd * ndim) && h->d_std.make(nd * ndim) && h->d_n.make(nd) && h->d_imax.make(nd) &&
+	    h->d_pm.make(ps) && h->d_pL.make(ps) && h->d_pn.make(ps) && h->d_parg.make(ps) &&
+	    h->d_part.make(ps * (2 + ndim)) &&
+	    MDNS_HIP(hipMemcpyAsync(h->d_w.get(), w, ns * nd * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipMemcpyAsync(h->d_L.get(), L, ns * nd * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipMemcpyAsync(h->d_x.get(), x, ns * nd * ndim * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
 	    MDNS_HIP(hipStreamSynchronize(c->stream));
-	if (!ok) { mdns_posterior_destroy(h); return nullptr; }
+	if (!ok) { mdns_posterior_destroy(h); return nullptr; }      // (it also destroys the events)
 	return h;
 }
 
@@ -565,15 +551,15 @@ extern "C" int mdns_posterior_summary(mdns_posterior *h, const double *q, int nq
 		if (!(q[j] > 0.0 && q[j] <= 1.0)) { set_error("mdns_posterior_summary: q[%d]=%g outside (0, 1]", j, q[j]); return 1; }
 	hipStream_t st = c->stream;
 	const size_t nd = (size_t) h->ndata, ndim = (size_t) h->ndim;
-	double *d_q = nullptr, *d_quant = nullptr, *d_xt = nullptr;
-	unsigned long long *d_wt = nullptr;
+	DeviceBuffer<double> q_buf, quant_buf, xt_buf;              // of this call (free themselves)
+	DeviceBuffer<unsigned long long> wt_buf;
 	const int dbatch = post_batch(h, (size_t) h->nsamp * (ndim + 1) * sizeof(double));
 	bool ok = !quant ||
-	          (MDNS_HIP(hipMalloc((void **) &d_q, nq * sizeof(double))) &&
-	           MDNS_HIP(hipMalloc((void **) &d_quant, nd * ndim * nq * sizeof(double))) &&
-	           MDNS_HIP(hipMalloc((void **) &d_xt, (size_t) dbatch * ndim * h->nsamp * sizeof(double))) &&
-	           MDNS_HIP(hipMalloc((void **) &d_wt, (size_t) dbatch * h->nsamp * sizeof(unsigned long long))) &&
-	           MDNS_HIP(hipMemcpyAsync(d_q, q, nq * sizeof(double), hipMemcpyHostToDevice, st)));
+	          (q_buf.make(nq) && quant_buf.make(nd * ndim * nq) && xt_buf.make((size_t) dbatch * ndim * h->nsamp) &&
+	           wt_buf.make((size_t) dbatch * h->nsamp) &&
+	           MDNS_HIP(hipMemcpyAsync(q_buf.get(), q, nq * sizeof(double), hipMemcpyHostToDevice, st)));
+	double *const d_q = q_buf.get(), *const d_quant = quant_buf.get(), *const d_xt = xt_buf.get();
+	unsigned long long *const d_wt = wt_buf.get();
 	ok = ok && MDNS_HIP(hipEventRecord(h->ev[kTimeMoments], st)) && post_norm(h, st) &&
 	     MDNS_HIP(hipEventRecord(h->ev[kTimeVar], st)) && (!std || post_var(h, st)) &&
 	     MDNS_HIP(hipEventRecord(h->ev[kTimeQuant], st));
@@ -582,21 +568,19 @@ extern "C" int mdns_posterior_summary(mdns_posterior *h, const double *q, int nq
 		for (int d0 = 0; ok && d0 < h->ndata; d0 += dbatch) {
 			const int dn = h->ndata - d0 < dbatch ? h->ndata - d0 : dbatch;
 			hipLaunchKernelGGL(k_post_transpose, dim3((h->nsamp + kWave - 1) / kWave, (dn + kWave - 1) / kWave), dim3(256), 0, st,
-			                   h->d_w, h->d_L, h->d_x, h->nsamp, h->ndata, h->ndim, d0, dn, h->d_m, h->d_S, d_xt, d_wt);
+			                   h->d_w.get(), h->d_L.get(), h->d_x.get(), h->nsamp, h->ndata, h->ndim, d0, dn, h->d_m.get(), h->d_S.get(), d_xt, d_wt);
 			hipLaunchKernelGGL(k_post_quantile, dim3(dn * h->ndim), dim3(kQBlock), lds, st, d_xt, d_wt, h->nsamp, h->ndim, d0,
 			                   d_q, nq, d_quant);
 			ok = post_launch_ok("mdns_posterior_summary (quantiles)");
 		}
 	}
 	ok = ok && MDNS_HIP(hipEventRecord(h->ev[kTimeResample], st)) &&
-	     post_fetch(nfinite, h->d_n, nd, st) && post_fetch(imaxL, h->d_imax, nd, st) &&
-	     post_fetch(log_norm, h->d_lognorm, nd, st) && post_fetch(ess, h->d_ess, nd, st) &&
-	     post_fetch(mean, h->d_mean, nd * ndim, st) && post_fetch(std, h->d_std, nd * ndim, st) &&
+	     post_fetch(nfinite, h->d_n.get(), nd, st) && post_fetch(imaxL, h->d_imax.get(), nd, st) &&
+	     post_fetch(log_norm, h->d_lognorm.get(), nd, st) && post_fetch(ess, h->d_ess.get(), nd, st) &&
+	     post_fetch(mean, h->d_mean.get(), nd * ndim, st) && post_fetch(std, h->d_std.get(), nd * ndim, st) &&
 	     (!quant || post_fetch(quant, (const double *) d_quant, nd * ndim * nq, st)) &&
 	     MDNS_HIP(hipStreamSynchronize(st)) && post_elapsed(h, kTimeMoments, kTimeResample);
-	if (!ok) (void) hipStreamSynchronize(st);
-	void *bufs[] = {d_q, d_quant, d_xt, d_wt};
-	for (void *b : bufs) if (b) (void) hipFree(b);
+	if (!ok) (void) hipStreamSynchronize(st);                  // (before the call's blocks go)
 	return ok ? 0 : 1;
 }
 
@@ -608,17 +592,17 @@ extern "C" int mdns_posterior_resample(mdns_posterior *h, unsigned long long see
 	if (n <= 0 || !index) { set_error("mdns_posterior_resample: n=%d, index %s", n, index ? "given" : "NULL"); return 1; }
 	hipStream_t st = c->stream;
 	const size_t nd = (size_t) h->ndata, ndim = (size_t) h->ndim;
-	int *d_index = nullptr;
-	double *d_xd = nullptr, *d_cdf = nullptr;
+	DeviceBuffer<int> index_buf;                                // of this call (free themselves)
+	DeviceBuffer<double> xd_buf, cdf_buf;
 	const int dbatch = post_batch(h, (size_t) h->nsamp * sizeof(double));
-	bool ok = MDNS_HIP(hipMalloc((void **) &d_index, nd * n * sizeof(int))) &&
-	          (!xdraws || MDNS_HIP(hipMalloc((void **) &d_xd, nd * n * ndim * sizeof(double)))) &&
-	          MDNS_HIP(hipMalloc((void **) &d_cdf, (size_t) dbatch * h->nsamp * sizeof(double))) &&
+	bool ok = index_buf.make(nd * n) && (!xdraws || xd_buf.make(nd * n * ndim)) && cdf_buf.make((size_t) dbatch * h->nsamp) &&
 	          post_norm(h, st) && MDNS_HIP(hipEventRecord(h->ev[kTimeResample], st));
+	int *const d_index = index_buf.get();
+	double *const d_xd = xd_buf.get(), *const d_cdf = cdf_buf.get();
 	for (int d0 = 0; ok && d0 < h->ndata; d0 += dbatch) {
 		const int dn = h->ndata - d0 < dbatch ? h->ndata - d0 : dbatch;
-		hipLaunchKernelGGL(k_post_resample, dim3(dn), dim3(kQBlock), 0, st, h->d_w, h->d_L, h->d_x, h->nsamp, h->ndata, h->ndim,
-		                   d0, h->d_m, h->d_n, d_cdf, seed, first_column, n, d_index, d_xd);
+		hipLaunchKernelGGL(k_post_resample, dim3(dn), dim3(kQBlock), 0, st, h->d_w.get(), h->d_L.get(), h->d_x.get(), h->nsamp, h->ndata, h->ndim,
+		                   d0, h->d_m.get(), h->d_n.get(), d_cdf, seed, first_column, n, d_index, d_xd);
 		ok = post_launch_ok("mdns_posterior_resample");
 	}
 	ok = ok && MDNS_HIP(hipEventRecord(h->ev[kTimePhases], st)) &&
@@ -629,9 +613,7 @@ extern "C" int mdns_posterior_resample(mdns_posterior *h, unsigned long long see
 		ok = MDNS_HIP(hipEventElapsedTime(&t, h->ev[kTimeResample], h->ev[kTimePhases]));
 		h->ms[kTimeResample] = t;
 	}
-	if (!ok) (void) hipStreamSynchronize(st);
-	void *bufs[] = {d_index, d_xd, d_cdf};
-	for (void *b : bufs) if (b) (void) hipFree(b);
+	if (!ok) (void) hipStreamSynchronize(st);                  // (before the call's blocks go)
 	return ok ? 0 : 1;
 }
 
