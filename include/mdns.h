@@ -415,7 +415,10 @@ int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M, long long
 /* Of the last mdns_groups_components: labels int32[M] = the lowest data-set index of the
  * component rows[i] lies in (components in ascending label order are igraph's cluster order,
  * which numbers them by their first vertex); point_labels int32[npoints] = the label of the
- * component holding live point q, -1 when no selected data set holds it.  Either may be NULL. */
+ * component holding live point q, -1 when no selected data set holds it.  Either may be NULL.
+ * "Last" means the last call that SUCCEEDED with nothing after it: a components call that fails (an id
+ * out of range, the deferred bit of a bad mdns_groups_replace, `cap` too small, refused arguments), like
+ * a change of the ids, leaves this call and mdns_groups_id_labels refused until the next success. */
 int mdns_groups_labels(mdns_groups *g, int32_t *labels, int32_t *point_labels);
 /* The same for the ids the last mdns_groups_components listed only: id_labels int32[ndistinct], in the
  * order of that list (a full mdns_groups_labels copies one label per id of the PILE, megabytes late in

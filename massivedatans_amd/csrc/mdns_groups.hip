@@ -421,6 +421,9 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 {
 	Context *c = ctx();
 	if (!c || !g || !ncomponents) return 1;
+	// the labels and stamps of the previous call are about to be replaced: whatever way this call ends
+	// other than well, mdns_groups_labels / _id_labels have nothing to return (set again on success)
+	g->last_M = -1;
 	if (!g->have_ids) { set_error("mdns_groups_components: no id matrix yet (mdns_groups_set_ids)"); return 1; }
 	if (M <= 0 || M > g->ndata || npoints <= 0 || (!rows && M != g->ndata) || (distinct && cap < 0)) {
 		set_error("mdns_groups_components: M=%d (ndata=%d) npoints=%lld", M, g->ndata, npoints);
@@ -521,6 +524,18 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 	}
 	g->last_M = M; g->last_npoints = npoints; g->last_ndistinct = nd;
 	g->label_call = call;
+	return 0;
+}
+
+// Test entry point (not in mdns.h): the next components call takes the number call + 1.  Forward only --
+// a lower number could meet stamps that are still in the per-id block -- so that the start-over of the
+// stamps at 0x7ffffff0 can be reached without 2^31 calls.
+extern "C" int mdns_groups_debug_set_call(mdns_groups *g, int call)
+{
+	if (!g) return 1;
+	if (call < g->call) { set_error("mdns_groups_debug_set_call: %d is below the current call %d", call, g->call); return 1; }
+	if (call > 0x7ffffff0) { set_error("mdns_groups_debug_set_call: %d is beyond the start-over of the stamps", call); return 1; }
+	g->call = call;
 	return 0;
 }
 

@@ -87,15 +87,19 @@ class DeviceGroups(object):
             self.size_log.append((M, int(ncomp.value), int(ndistinct.value)))
         return int(ncomp.value), self._distinct[:ndistinct.value].astype(np.int64)
 
-    def touched(self, npoints):
-        """The ids held by the selection of a fresh :meth:`components` call over all data sets,
-        as the bit map the library also offers (bit q of word q // 64)."""
+    def touched(self, npoints, rows=None):
+        """The ids held by the selection of a fresh :meth:`components` call over the data sets
+        ``rows`` (None: all), as the bit map the library also offers (bit q of word q // 64)."""
         nwords = (int(npoints) + 63) // 64
         bits = np.zeros(nwords, dtype=np.uint64)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+        M = self.ndata if rows is None else len(rows)
         ncomp, ndistinct = C.c_int(0), C.c_longlong(0)
-        _lib.check(self._lib.mdns_groups_components(self._h, None, self.ndata, int(npoints), C.addressof(ncomp),
-                                                    C.addressof(ndistinct), None, 0, _lib.ptr(bits)), "mdns_groups_components")
-        self._rows, self._npoints = None, int(npoints)
+        _lib.check(self._lib.mdns_groups_components(self._h, None if rows is None else _lib.ptr(rows), M, int(npoints),
+                                                    C.addressof(ncomp), C.addressof(ndistinct), None, 0, _lib.ptr(bits)),
+                   "mdns_groups_components")
+        self._rows, self._npoints = rows, int(npoints)
         return bits
 
     def labels(self):
