@@ -227,7 +227,8 @@ int mdns_joint_init_gauss(mdns_joint *j, const double *params, double noise_leve
 int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter);
 /* The same from model curves the caller made, curves f64[nlive][nx], for both kinds of spectra: without variances the
  * fixed-noise likelihood (mdns_curve_loglike_batch) at noise_level, which the curve chunks of this state then use too;
- * with variances the scale-marginalised one (mdns_muse_loglike_batch; noise_level is ignored).  jitter as above. */
+ * with variances the scale-marginalised one (mdns_muse_loglike_batch; noise_level is ignored), or -- on a fixed-scale
+ * handle, Part 9 -- mdns_curve_chi2_batch.  jitter as above. */
 int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter);
 /* The same from a host matrix liveL f64[nlive, ndata] (row p = live slot p). */
 int mdns_joint_set_live(mdns_joint *j, const double *liveL);
@@ -615,7 +616,8 @@ int mdns_backend_region_radius(void *joint, void *region, double *radius);
 /* mdns_backend_draw_chunk for a model the CALLER evaluates: curves f64[B][nx], one model curve per candidate, in
  * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M], both kinds of
  * state).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
- * variances) or as mdns_muse_loglike_batch (variances), decided and committed like a draw_chunk.  A draw may mix
+ * variances), as mdns_muse_loglike_batch (variances) or as mdns_curve_chi2_batch (variances, fixed scale: Part 9),
+ * decided and committed like a draw_chunk.  A draw may mix
  * parameter chunks and curve chunks.  _dev: curves (rows of ldc >= nx doubles) and jitter already in device memory,
  * read on the library stream. */
 int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
@@ -803,6 +805,37 @@ int mdns_muse_continuum_fit_batch(mdns_spectra *s, const double *ypred, int B, c
                                   double *Lout, double *scale_out, double *coef_out);
 int mdns_muse_continuum_fit_batch_dev(mdns_spectra *s, const double *d_ypred, int B, const int *d_row_ids, int M,
                                       double *d_Lout, double *d_scale_out, double *d_coef_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Part 9 -- caller-defined models at FIXED scale with per-pixel variances (csrc/mdns_curves.hip,
+ * k_curve_rows_w).
+ *
+ *   L[b][k] = -0.5 * sum_j w[row_k][j] * (curves[b][j] - y[row_k][j])**2,   w = 1/v as the handle keeps it
+ *
+ * (the constant -0.5 sum log 2 pi v is omitted, as everywhere).  A pixel is masked by w = 0 -- v = inf -- with a
+ * finite y: it then contributes nothing, bit for bit.  The amplitude of the model is the caller's parameter:
+ * nothing is fitted per spectrum.  Per pair ONE chain over the channels in ascending order, from acc = +0:
+ * d = c - y, t = w * d (rounded), acc = fma(t, d, acc); L = -0.5 * acc.  The bits of a pair do not depend on B, M,
+ * its place in the batch, ldc or the entry point.  Curve values are not validated: non-finite ones propagate as IEEE.
+ *
+ * mdns_curve_chi2_batch[_dev]: arguments, size checks and messages as mdns_curve_loglike_batch[_dev] without the
+ * noise level; pure functions of a handle WITH variances (else "spectra were created without variances"), in
+ * whatever mode it is.  B == 0 or M == 0: nothing happens.
+ *
+ * mdns_spectra_set_fixed_scale(s, 1): every curve scoring of a joint state on this handle -- mdns_joint_init_curves,
+ * mdns_backend_draw_curves[_dev] -- is this likelihood instead of the scale-marginalised one; jitter, accept, commit
+ * and mailbox are the same.  Such a state takes curve chunks ONLY: mdns_joint_init_muse3, mdns_backend_draw_chunk,
+ * mdns_backend_draw_score and mdns_backend_draw_band[_begin] fail on it (and leave it usable).  The pure batch
+ * functions (mdns_muse_loglike_batch* ...) compute what their names say in either mode.  The setter fails -- the
+ * former setting stays in force -- on a handle without variances, once a joint state exists on the handle, and
+ * while a continuum is set; mdns_spectra_set_continuum(P > 0) fails on a fixed-scale handle.
+ * mdns_spectra_fixed_scale: the current setting (-1: null handle).
+ * ------------------------------------------------------------------------------------------ */
+int mdns_curve_chi2_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout);
+int mdns_curve_chi2_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                              double *d_Lout);
+int mdns_spectra_set_fixed_scale(mdns_spectra *s, int on);
+int mdns_spectra_fixed_scale(const mdns_spectra *s);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,8 @@ ABI_SYMBOLS = (
     "mdns_backend_draw_curves", "mdns_backend_draw_curves_dev",
     # Part 8: a polynomial continuum per spectrum (csrc/mdns_continuum.hip)
     "mdns_spectra_set_continuum", "mdns_spectra_continuum", "mdns_muse_continuum_fit_batch", "mdns_muse_continuum_fit_batch_dev",
+    # Part 9: caller-made curves at fixed scale with per-pixel variances (csrc/mdns_curves.hip k_curve_rows_w)
+    "mdns_curve_chi2_batch", "mdns_curve_chi2_batch_dev", "mdns_spectra_set_fixed_scale", "mdns_spectra_fixed_scale",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -214,6 +216,10 @@ def _declare(lib):
         "mdns_spectra_continuum": (i, [vp]),
         "mdns_muse_continuum_fit_batch": (i, [vp, vp, i, vp, i, vp, vp, vp]),
         "mdns_muse_continuum_fit_batch_dev": (i, [vp, vp, i, vp, i, vp, vp, vp]),
+        "mdns_curve_chi2_batch": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_curve_chi2_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
+        "mdns_spectra_set_fixed_scale": (i, [vp, i]),
+        "mdns_spectra_fixed_scale": (i, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

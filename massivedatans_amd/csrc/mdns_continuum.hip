@@ -389,6 +389,7 @@ extern "C" int mdns_spectra_set_continuum(mdns_spectra *s, int P)
 		return 0;
 	}
 	if (!s->d_w.get() || !s->d_x.get()) { set_error("mdns_spectra_set_continuum: the spectra need variances and a wavelength grid"); return 1; }
+	if (s->fixed_scale) { set_error("mdns_spectra_set_continuum: these spectra are in fixed-scale mode (mdns_spectra_set_fixed_scale): no scale to marginalise, no continuum to profile"); return 1; }
 	if (s->nx < P) { set_error("mdns_spectra_set_continuum: spectrum 0 has %d channels, fewer than the %d terms", s->nx, P); return 1; }
 	const int ldm = model_ld(s->nx);
 	// made in locals and installed on success: the former setting stays in force when this call fails

@@ -17,6 +17,27 @@
 // from acc = 0; channels past the last one contribute fma(0, 0, acc), which changes nothing.  The value of a pair
 // therefore does not depend on B, M, where either sits in its batch, or which entry point asked.  Nothing is
 // validated: a non-finite curve value propagates as IEEE.
+//
+// The same curves at FIXED scale against per-pixel variances (include/mdns.h Part 9, mdns_curve_chi2_batch[_dev]):
+//
+//   L[b][k] = -0.5 sum_j w[row_k][j] (curves[b][j] - y[row_k][j])^2,   w = 1/v (s->d_w), w = 0 for a masked pixel
+//
+// k_curve_rows_w k_curve_rows' tiling with the weights staged exactly like the spectra: `ws` beside `ys`, both
+//                [channel pair][spectrum] in 16-byte slots, 129 slots per channel pair.  Two separate arrays and not
+//                {y, w} of one channel in one slot: a store group of ds_write_b128 is eight contiguous lanes -- eight
+//                channel pairs of one spectrum --, and its banks are (address / 4) mod 32.  Here the eight lanes are
+//                129 slots = 516 dwords apart, 4 mod 32: eight times four different banks, no conflict.  Interleaved,
+//                a lane's two slots would be channels 2 cp and 2 cp + 1, the lanes 2 x 516 dwords = 8 mod 32 apart:
+//                lanes cp and cp + 4 on the same banks, every store two-way.  LDS: 2 x 16 x 129 x 16 B + 8 KB =
+//                74 240 B, two workgroups per CU.  Per pair of channels a wave issues 4 + 8 16-byte LDS reads (48 LDS
+//                cycles) against 96 fp64 instructions (384 cycles of its SIMD): the arithmetic still bounds it.
+//
+// Per (curve, spectrum) pair the sum is ONE chain: channels in ascending order, from acc = +0:
+//     d = c - y;  t = w * d (a rounded product);  acc = fma(t, d, acc);        L = -0.5 * acc
+// Channels past the last one are staged as y = w = c = 0: fma(0 * 0, 0, acc) = acc.  A masked pixel -- w = 0 and a
+// finite y (like.WeightedSpectra sees to both) -- gives t = +-0 and fma(+-0, d, acc) = acc for every finite d, bit for
+// bit (acc = +0 stays +0: +0 + -0 = +0): the kernel does not look for masks.  As above, the bits of a pair do not
+// depend on B, M, where either sits in its batch, ldc, the grid split or the entry point.
 #include "mdns_internal.h"
 
 namespace mdns {
@@ -106,6 +127,88 @@ __global__ __launch_bounds__(256) void k_curve_rows(
 	}
 }
 
+// The fixed-scale chi^2 with per-pixel weights W [ndata][ld] (the handle's 1 / v): k_curve_rows with `ws` staged
+// beside `ys` (file header: layout, chain).  Spectrum pieces of Y and W come from the same row offsets.
+__global__ __launch_bounds__(256) void k_curve_rows_w(
+    const double *__restrict__ Y, const double *__restrict__ W, int ld, int nx, const double *__restrict__ curves, int ldc, int B,
+    const int *__restrict__ rows, int M, double *__restrict__ out)
+{
+	__shared__ __attribute__((aligned(16))) double2 ys[kCurveCH / 2][kCurveSlots];       // [channel pair][spectrum]
+	__shared__ __attribute__((aligned(16))) double2 ws[kCurveCH / 2][kCurveSlots];       // the same of the weights
+	__shared__ __attribute__((aligned(16))) double cs[kCurveCands][kCurveCH];            // [candidate][channel]
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int k0 = blockIdx.x * kCurveSpectra, b0 = blockIdx.y * kCurveCands;
+	const int cp = lane & 15, rsub = wave * 4 + (lane >> 4);
+	const int cch = threadIdx.x & 31, crow = threadIdx.x >> 5;
+	size_t at[kCurveSpectra / 16];                                            // of this thread's channel pair in its rows
+#pragma unroll
+	for (int i = 0; i < kCurveSpectra / 16; i++) {
+		const int k = k0 + rsub + 16 * i;
+		const int kk = k < M ? k : M - 1;                                     // (past the selection: its last row again, never stored)
+		at[i] = (size_t) (rows ? rows[kk] : kk) * ld + 2 * cp;
+	}
+	double2 yv[kCurveSpectra / 16], wv[kCurveSpectra / 16];
+	double cv[kCurveCands / 8];
+	auto fetch = [&](int j0) {
+		const int j = j0 + 2 * cp;
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) {
+			// (rows are 16-byte aligned and an even number of doubles long: the pair of an even channel below nx is inside)
+			double2 y = make_double2(0.0, 0.0), w = make_double2(0.0, 0.0);
+			if (j < nx) {
+				y = *reinterpret_cast<const double2 *>(Y + at[i] + j0);
+				w = *reinterpret_cast<const double2 *>(W + at[i] + j0);
+			}
+			if (j + 1 >= nx) y.y = w.y = 0.0;
+			yv[i] = y; wv[i] = w;
+		}
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 8; i++) {
+			const int b = b0 + crow + 8 * i;
+			cv[i] = b < B && j0 + cch < nx ? curves[(size_t) b * ldc + j0 + cch] : 0.0;
+		}
+	};
+	double acc[kCurveNC][2];
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) acc[c][0] = acc[c][1] = 0.0;
+	const bool working = b0 + wave * kCurveNC < B;                            // wave-uniform; an idle wave still stages
+	fetch(0);
+	for (int j0 = 0; j0 < nx; j0 += kCurveCH) {
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) { ys[cp][rsub + 16 * i] = yv[i]; ws[cp][rsub + 16 * i] = wv[i]; }
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 8; i++) cs[crow + 8 * i][cch] = cv[i];
+		__syncthreads();
+		if (j0 + kCurveCH < nx) fetch(j0 + kCurveCH);
+		if (working) {
+#pragma unroll 4
+			for (int jp = 0; jp < kCurveCH / 2; jp++) {
+				const double2 ya = ys[jp][lane], yb = ys[jp][lane + 64];
+				const double2 wa = ws[jp][lane], wb = ws[jp][lane + 64];
+#pragma unroll
+				for (int c = 0; c < kCurveNC; c++) {
+					const double2 m = *reinterpret_cast<const double2 *>(&cs[wave * kCurveNC + c][2 * jp]);
+					double d;
+					d = m.x - ya.x; acc[c][0] = fma(__dmul_rn(wa.x, d), d, acc[c][0]);
+					d = m.y - ya.y; acc[c][0] = fma(__dmul_rn(wa.y, d), d, acc[c][0]);
+					d = m.x - yb.x; acc[c][1] = fma(__dmul_rn(wb.x, d), d, acc[c][1]);
+					d = m.y - yb.y; acc[c][1] = fma(__dmul_rn(wb.y, d), d, acc[c][1]);
+				}
+			}
+		}
+		__syncthreads();
+	}
+	if (!working) return;
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) {
+		const int b = b0 + wave * kCurveNC + c;
+		if (b >= B) break;
+		const int k = k0 + lane;
+		if (k < M) out[(size_t) b * M + k] = -0.5 * acc[c][0];
+		if (k + 64 < M) out[(size_t) b * M + k + 64] = -0.5 * acc[c][1];
+	}
+}
+
 // curves [B][ldc] -> templates [B][ldm] as the K2 row kernels take them: zero behind channel nx
 __global__ __launch_bounds__(256) void k_curve_pad(const double *__restrict__ curves, int ldc, int nx, double *__restrict__ model, int ldm)
 {
@@ -124,6 +227,16 @@ bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, i
 	return launched("k_curve_rows");
 }
 
+bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
+{
+	Context *c = ctx();
+	if (B <= 0 || M <= 0) return true;
+	const dim3 grid((M + kCurveSpectra - 1) / kCurveSpectra, (B + kCurveCands - 1) / kCurveCands);
+	hipLaunchKernelGGL(k_curve_rows_w, grid, dim3(256), 0, c->stream, (const double *) s->d_y.get(), (const double *) s->d_w.get(), s->ld, s->nx,
+	                   d_curves, ldc, B, d_rows, M, d_out);
+	return launched("k_curve_rows_w");
+}
+
 bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm)
 {
 	Context *c = ctx();
@@ -136,16 +249,49 @@ bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_
 
 using namespace mdns;
 
+// what both device entry points check first; 1: refused, 0: go on, -1: nothing to score
+static int curve_batch_check(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                             const double *d_Lout, bool weighted, const char *who)
+{
+	if (!ctx()) return 1;
+	if (!s) { set_error("%s: null spectra handle", who); return 1; }
+	if (B < 0 || M < 0 || M > s->ndata || s->nx < 1 || ldc < s->nx || (!d_row_ids && M != s->ndata && M != 0)) {
+		set_error("%s: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", who, B, M, s->ndata, ldc, s->nx);
+		return 1;
+	}
+	if (weighted && !s->d_w.get()) { set_error("%s: spectra were created without variances", who); return 1; }
+	if (B == 0 || M == 0) return -1;
+	if (!d_curves || !d_Lout) { set_error("%s: null argument", who); return 1; }
+	return 0;
+}
+
 extern "C" int mdns_curve_loglike_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, double noise_level,
                                             const int *d_row_ids, int M, double *d_Lout)
 {
-	if (!ctx()) return 1;
-	if (!s) { set_error("mdns_curve_loglike_batch_dev: null spectra handle"); return 1; }
-	if (B < 0 || M < 0 || M > s->ndata || s->nx < 1 || ldc < s->nx || (!d_row_ids && M != s->ndata && M != 0)) {
-		set_error("mdns_curve_loglike_batch_dev: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", B, M, s->ndata, ldc, s->nx);
+	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, false, "mdns_curve_loglike_batch_dev");
+	if (rc != 0) return rc > 0;
+	return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (noise_level * noise_level), d_row_ids, M, d_Lout) ? 0 : 1;
+}
+
+extern "C" int mdns_curve_chi2_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                                         double *d_Lout)
+{
+	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, true, "mdns_curve_chi2_batch_dev");
+	if (rc != 0) return rc > 0;
+	return launch_curve_rows_w(s, d_curves, ldc, B, d_row_ids, M, d_Lout) ? 0 : 1;
+}
+
+extern "C" int mdns_spectra_fixed_scale(const mdns_spectra *s) { return s ? s->fixed_scale : -1; }
+
+extern "C" int mdns_spectra_set_fixed_scale(mdns_spectra *s, int on)
+{
+	if (!s) { set_error("mdns_spectra_set_fixed_scale: null spectra handle"); return 1; }
+	if (s->njoint > 0) { set_error("mdns_spectra_set_fixed_scale: a joint state exists on these spectra (set the mode first)"); return 1; }
+	if (on && !s->d_w.get()) { set_error("mdns_spectra_set_fixed_scale: spectra were created without variances"); return 1; }
+	if (on && s->continuum > 0) {
+		set_error("mdns_spectra_set_fixed_scale: a continuum of %d terms is set on these spectra (it belongs to the scale-marginalised likelihood)", s->continuum);
 		return 1;
 	}
-	if (B == 0 || M == 0) return 0;
-	if (!d_curves || !d_Lout) { set_error("mdns_curve_loglike_batch_dev: null argument"); return 1; }
-	return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (noise_level * noise_level), d_row_ids, M, d_Lout) ? 0 : 1;
+	s->fixed_scale = on ? 1 : 0;
+	return 0;
 }

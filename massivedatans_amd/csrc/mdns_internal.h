@@ -212,6 +212,10 @@ struct mdns_spectra {
 	// entries, then the RECIPROCALS of the diagonal) and beta = G^-1 sum w b y.  Fixed like the line list (njoint)
 	int continuum = 0;
 	mdns::DeviceBuffer<double> d_ct, d_cfac;
+	// fixed-scale chi^2 with the per-pixel weights d_w (mdns_curves.hip, mdns_spectra_set_fixed_scale): 1 = every curve
+	// scoring of a joint state on this handle is -0.5 sum w (c - y)^2 and the state takes curve chunks only.  Needs
+	// variances, excludes a continuum; fixed like the line list (njoint)
+	int fixed_scale = 0;
 };
 
 namespace mdns {
@@ -359,6 +363,9 @@ bool launch_pad_model(const double *d_src, int nx, int B, double *d_dst, int ldm
 bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, int B, double scale,
                        const int *d_rows, int M, double *d_out);
 bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm);
+// the same curves against the selected rows of s->d_y with the per-pixel weights s->d_w (which must be there):
+// d_out [B][M] = -0.5 sum_j w_j (c_j - y_j)^2 (k_curve_rows_w: one chain per pair, channels ascending)
+bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
 
 // launchers implemented in mdns_neighbors.hip
 // What a radius computation leaves behind: written by the LAST workgroup of the bootstrap

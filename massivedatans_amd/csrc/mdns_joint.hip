@@ -580,11 +580,21 @@ extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double
 	return joint_sync(c) ? 0 : 1;
 }
 
+// A state over fixed-scale spectra (mdns.h Part 9) has no likelihood for parameter rows or templates: K2 would fit the
+// scale.  True (and the error set) for such a state; nothing of it has been touched.
+static bool curves_only(const mdns_joint *j, const char *who)
+{
+	if (j->kind != 1 || !j->s->fixed_scale) return false;
+	set_error("%s: fixed-scale spectra take curve chunks only (mdns_joint_init_curves, mdns_backend_draw_curves)", who);
+	return true;
+}
+
 extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter)
 {
 	Context *c = ctx();
 	if (!c || !j || !params) return 1;
 	if (j->kind != 1) { set_error("mdns_joint_init_muse3: the spectra carry no variances"); return 1; }
+	if (curves_only(j, "mdns_joint_init_muse3")) return 1;
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_muse3: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
 	const size_t pbytes = (size_t) j->nlive * j->nparams * sizeof(double), n = (size_t) j->nlive * j->ndata;
 	if (!j->h_pin.fit(pbytes)) return 1;
@@ -605,11 +615,13 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 
 // curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the fixed-noise likelihood from curves
 // (kind 0) or the scale-marginalised one on the curves staged as zero-padded templates (kind 1: exactly what
-// mdns_muse_loglike_batch_dev does with templates)
+// mdns_muse_loglike_batch_dev does with templates), or -- kind 1 on a fixed-scale handle -- the weighted chi^2 at fixed
+// scale (mdns_curve_chi2_batch_dev)
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
 	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
+	if (s->fixed_scale) return launch_curve_rows_w(s, d_curves, ldc, B, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
 	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
 	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);
@@ -1299,6 +1311,7 @@ extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B,
 	mdns_joint *j = (mdns_joint *) joint;
 	if (!c || !j || !accepted) return 1;
 	*accepted = -1;
+	if (curves_only(j, "mdns_backend_draw_chunk")) return 1;
 	if (!j->sel_open) { set_error("mdns_backend_draw_chunk: no draw begun"); return 1; }
 	const int M = j->sel_M;
 	if (!check_draw(j, B, M, "mdns_backend_draw_chunk")) return 1;
@@ -1523,6 +1536,7 @@ extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B,
 	Context *c = ctx();
 	mdns_joint *j = (mdns_joint *) joint;
 	if (!c || !j || (!params && B > 0)) return 1;
+	if (curves_only(j, "mdns_backend_draw_score")) return 1;
 	if (!j->sel_open) { set_error("mdns_backend_draw_score: no draw begun"); return 1; }
 	const int M = j->sel_M;
 	if (!check_draw(j, B, M, "mdns_backend_draw_score")) return 1;
@@ -1605,6 +1619,7 @@ extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, i
 	mdns_joint *j = (mdns_joint *) joint;
 	if (!c || !j || !params || !bound) { set_error("mdns_backend_draw_band: null argument"); return 1; }
 	if (j->kind != 1) { set_error("mdns_backend_draw_band: a state of the scale-marginalised likelihood is needed"); return 1; }
+	if (curves_only(j, "mdns_backend_draw_band")) return 1;
 	if (!j->sel_open) { set_error("mdns_backend_draw_band: no draw begun"); return 1; }
 	if (j->band_pending) { set_error("mdns_backend_draw_band_begin: the last chunk was not collected"); return 1; }
 	const int M = j->sel_M;

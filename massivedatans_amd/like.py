@@ -7,8 +7,10 @@ Mirrors the problem-definition surface of the reference driver scripts:
 * :class:`MuseSpectra` -- ``multi_loglikelihood_clike`` of musefuse.py:520-535 (scale-marginalised
   chi^2 against a template; cmuselike.c), without the RNG jitter (callers add it, see
   ``jitter``).
+* :class:`WeightedSpectra` -- per-pixel variances at fixed scale, for model curves the caller makes
+  (:mod:`massivedatans_amd.problem`); no counterpart in the reference.
 
-Both keep the spectra on the device as ``[n_datasets, n_channels]`` rows and add
+All keep the spectra on the device as ``[n_datasets, n_channels]`` rows and add
 ``loglike_batch`` (B candidates per pass), which the reference does not have.
 """
 import ctypes as C
@@ -123,6 +125,49 @@ class GaussLineSpectra(_Spectra):
         A, mu, log_sig = params
         sig = 10 ** log_sig
         return self.loglike_batch(np.array([[A, mu, sig]]), data_mask)[0]
+
+
+def mask_pixels(y, v):
+    """What :class:`WeightedSpectra` uploads for ``y``, ``v`` of one shape: ``(y, v, masked)``, copies in which a pixel
+    whose ``v`` is ``inf`` or NaN, or whose ``y`` is not finite, is MASKED -- ``y = 0``, ``v = inf``, so that its weight
+    ``1 / v`` is 0 and its residual finite -- and ``masked`` says which.  Any other ``v <= 0`` raises ValueError.  Needs
+    no device."""
+    y, v = np.array(y, dtype=np.float64), np.array(v, dtype=np.float64)
+    if v.shape != y.shape:
+        raise ValueError("v and y differ in shape")
+    masked = np.isnan(v) | (v == np.inf) | ~np.isfinite(y)
+    bad = ~masked & ~(v > 0)
+    if bad.any():
+        at = tuple(int(i) for i in np.argwhere(bad)[0])
+        raise ValueError("v%s = %r: variances must be positive (inf or NaN masks a pixel)" % (list(at), float(v[at])))
+    y[masked] = 0.0
+    v[masked] = np.inf
+    return y, v, masked
+
+
+class WeightedSpectra(_Spectra):
+    """Spectra with per-pixel variances scored at FIXED scale against model curves the caller made (include/mdns.h
+    Part 9): ``L = -0.5 sum_j (curve_j - y_j)^2 / v_j``, nothing fitted per spectrum -- the model's amplitude is the
+    caller's parameter.  A pixel with ``v`` ``inf`` or NaN, or a non-finite ``y``, is masked (:func:`mask_pixels`) and
+    contributes nothing; ``n_masked`` [ndata] counts them per spectrum.  A joint state on these spectra
+    (:class:`massivedatans_amd.jointstate.CurveJointState`) scores its curve chunks the same way."""
+
+    def __init__(self, x, y, v, layout="channel_major"):
+        if v is None:
+            raise ValueError("WeightedSpectra needs the variances v")
+        y, v, masked = mask_pixels(y, v)
+        super(WeightedSpectra, self).__init__(x, y, v, layout)
+        self.n_masked = masked.sum(axis=0 if layout == "channel_major" else 1)
+        _lib.check(self._lib.mdns_spectra_set_fixed_scale(self._h, 1), "mdns_spectra_set_fixed_scale")
+
+    def loglike_batch_curves(self, curves, data_mask=None):
+        """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_chi2_batch)."""
+        curves = np.atleast_2d(_lib.as_f64(curves))
+        if curves.shape[1] != self.nx:
+            raise ValueError("curves must be [B, %d]" % self.nx)
+        return self._batch(self._lib.mdns_curve_chi2_batch, "mdns_curve_chi2_batch", curves, data_mask)
+
+    loglike_batch = loglike_batch_curves
 
 
 class MuseSpectra(_Spectra):

@@ -26,12 +26,14 @@ import numpy
 MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
 
 
-def default_backend(x, y, noise_level, v=None, continuum=0):
+def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True):
     """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood
-    (``continuum``: like.MuseSpectra)."""
-    from .like import GaussLineSpectra, MuseSpectra
+    (``continuum``: like.MuseSpectra), or -- ``marginalise_scale=False`` -- the fixed-scale one (like.WeightedSpectra)."""
+    from .like import GaussLineSpectra, MuseSpectra, WeightedSpectra
     if v is None:
         return GaussLineSpectra(x, y, noise_level=noise_level)
+    if not marginalise_scale:
+        return WeightedSpectra(x, y, v)
     return MuseSpectra(x, y, v, continuum=continuum)
 
 
@@ -54,11 +56,19 @@ class _ModelScorer(object):
 
 class CurveProblem(object):
     """``x`` f64[nx], ``y`` (and ``v``) f64[nx, ndata] in the reference's layout.  ``model(xs[B, ndim]) ->
-    curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Without ``v``
-    the likelihood is ``-0.5 sum_j ((curve_j - y_j) / noise_level)**2`` (sample.py:64-71); with per-pixel
-    variances ``v`` the scale-marginalised one of cmuselike.c:45-64 (``noise_level`` is not used), with
-    ``continuum=P`` (1..4; needs ``v``) a polynomial of P Legendre terms profiled out per spectrum as well
-    (:mod:`massivedatans_amd.continuum`).
+    curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Three
+    likelihoods:
+
+    * without ``v``: ``-0.5 sum_j ((curve_j - y_j) / noise_level)**2`` (sample.py:64-71), one noise level for every
+      pixel;
+    * with per-pixel variances ``v``: the scale-marginalised one of cmuselike.c:45-64 -- a free amplitude ``s`` per
+      spectrum is fitted, ``-0.5 sum_j (y_j - s curve_j)**2 / v_j`` (``noise_level`` is not used); with
+      ``continuum=P`` (1..4; needs ``v``) a polynomial of P Legendre terms is profiled out per spectrum as well
+      (:mod:`massivedatans_amd.continuum`).  The amplitude of the model drops out: do not make it a parameter;
+    * with ``v`` and ``marginalise_scale=False``: ``-0.5 sum_j (curve_j - y_j)**2 / v_j`` at FIXED scale, for a
+      model whose amplitude is a parameter.  A pixel with ``v = inf`` (or NaN, or a non-finite ``y``) is ignored
+      (:class:`massivedatans_amd.like.WeightedSpectra`).  Needs ``v``, excludes ``continuum``.
+
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
     L[B, M]`` (tests put a numpy scorer there; the state is then the numpy one); by default the spectra go
@@ -67,11 +77,17 @@ class CurveProblem(object):
     Gives ``sample.build_sampler`` what it reads of a problem."""
 
     def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None,
-                 continuum=0):
+                 continuum=0, marginalise_scale=True):
         from .continuum import check_terms
         self.continuum = check_terms(continuum)
+        self.marginalise_scale = bool(marginalise_scale)
         if self.continuum and v is None:
             raise ValueError("continuum = %d needs the variances v (the scale-marginalised likelihood)" % self.continuum)
+        if not self.marginalise_scale and v is None:
+            raise ValueError("marginalise_scale = False needs the variances v (without them the likelihood is the fixed-noise one)")
+        if not self.marginalise_scale and self.continuum:
+            raise ValueError("marginalise_scale = False excludes continuum = %d (the continuum is profiled out together with the scale)"
+                             % self.continuum)
         self.x = numpy.ascontiguousarray(x, dtype=float)
         self.y = numpy.ascontiguousarray(y, dtype=float)
         self.v = None if v is None else numpy.ascontiguousarray(v, dtype=float)
@@ -85,6 +101,8 @@ class CurveProblem(object):
         self.jitter_sigma = float(jitter_sigma)
         if backend is None:
             kw = dict(continuum=self.continuum) if self.continuum else {}
+            if not self.marginalise_scale:
+                kw["marginalise_scale"] = False
             backend = default_backend(self.x, self.y, self.noise_level, self.v, **kw)
         self.backend = backend
         if getattr(backend, "continuum", 0) != self.continuum:
