@@ -228,7 +228,8 @@ int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jit
 /* The same from model curves the caller made, curves f64[nlive][nx], for both kinds of spectra: without variances the
  * fixed-noise likelihood (mdns_curve_loglike_batch) at noise_level, which the curve chunks of this state then use too;
  * with variances the scale-marginalised one (mdns_muse_loglike_batch; noise_level is ignored), or -- on a fixed-scale
- * handle, Part 9 -- mdns_curve_chi2_batch.  jitter as above. */
+ * handle, Part 9 -- mdns_curve_chi2_batch.  On a counts handle (Part 10; no variances, noise_level is ignored)
+ * mdns_curve_poisson_batch.  jitter as above. */
 int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter);
 /* The same from a host matrix liveL f64[nlive, ndata] (row p = live slot p). */
 int mdns_joint_set_live(mdns_joint *j, const double *liveL);
@@ -616,8 +617,8 @@ int mdns_backend_region_radius(void *joint, void *region, double *radius);
 /* mdns_backend_draw_chunk for a model the CALLER evaluates: curves f64[B][nx], one model curve per candidate, in
  * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M], both kinds of
  * state).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
- * variances), as mdns_muse_loglike_batch (variances) or as mdns_curve_chi2_batch (variances, fixed scale: Part 9),
- * decided and committed like a draw_chunk.  A draw may mix
+ * variances), as mdns_muse_loglike_batch (variances), as mdns_curve_chi2_batch (variances, fixed scale: Part 9) or as
+ * mdns_curve_poisson_batch (counts: Part 10), decided and committed like a draw_chunk.  A draw may mix
  * parameter chunks and curve chunks.  _dev: curves (rows of ldc >= nx doubles) and jitter already in device memory,
  * read on the library stream. */
 int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
@@ -836,6 +837,56 @@ int mdns_curve_chi2_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, 
                               double *d_Lout);
 int mdns_spectra_set_fixed_scale(mdns_spectra *s, int on);
 int mdns_spectra_fixed_scale(const mdns_spectra *s);
+
+/* ------------------------------------------------------------------------------------------
+ * Part 10 -- caller-defined models against PHOTON COUNTS: the Poisson likelihood, the "C statistic" of X-ray
+ * fitting (csrc/mdns_curves.hip, k_curve_log + k_curve_rows_p).
+ *
+ * Per spectrum k and channel j: counts n >= 0 (the handle's y; finite, not necessarily integers) and an exposure
+ * e >= 0 (effective area x time, flat field ...; e = 0 masks the pixel).  A curve c >= 0 is the expected count RATE
+ * per unit exposure, the expected counts are e c.  With tiny = DBL_MIN:
+ *
+ *   L[b][k] = sum_j ( n[row_k][j] * log(max(curves[b][j], tiny)) - e[row_k][j] * curves[b][j] ) + K[row_k]
+ *   K[k]    = sum over the pixels with n > 0 and e > 0 of  n (1 + log e - log n)        (the caller's, see below)
+ *
+ * For c > 0 that is -C/2 with C = 2 sum (e c - n + n log(n / (e c))): <= 0, and 0 for a perfect model (log n! is
+ * omitted, as every constant is).  Per pair ONE chain over the channels in ascending order, from acc = +0:
+ * acc = fma(n, lc, acc), acc = fma(-e, c', acc); L = acc + K, where k_curve_log made lc = log(max(c', tiny)) and
+ * c' = c once per candidate and channel.  The bits of a pair do not depend on B, M, its place in the batch, ldc or
+ * the entry point.
+ *   zero model     c = +-0 where n = 0 contributes exactly nothing; where n > 0 it costs n log(tiny), about -708 n:
+ *                  finite and ordered.
+ *   invalid model  a negative or NaN curve value (c' = NaN) makes L NaN for EVERY spectrum, masked pixel or not;
+ *                  the accept test of a joint state rejects NaN.  +inf is not validated.
+ *   masked pixel   n = 0 and e = 0: a deleted channel, bit for bit, for every finite c >= 0.  A spectrum without a
+ *                  good pixel scores K = 0, hence +0.0.
+ *
+ * mdns_spectra_set_counts(s, exposure, offsets): puts a handle created WITHOUT variances into counts mode.
+ * exposure f64[ndata][nx] (one spectrum per row, contiguous), or NULL for all ones; offsets f64[ndata], the K[k] --
+ * computed by the caller, so that no device logarithm enters them --, or NULL for zeros.  Both go into buffers of
+ * their own on the handle, and y is zeroed where e == 0 (with what the handle keeps derived from y).  Fails -- the
+ * handle stays as it was -- on a null handle, on a handle created with variances, once a joint state exists on the
+ * handle, and when an exposure is negative or not finite (looked for in the host array before anything is
+ * uploaded).  There is no way back out of the mode.  mdns_spectra_counts: 0 or 1 (-1: null handle).
+ *
+ * mdns_curve_poisson_batch[_dev]: arguments, size checks and messages as mdns_curve_chi2_batch[_dev]; on a handle
+ * that is not in counts mode "spectra are not in counts mode (mdns_spectra_set_counts)".  B == 0 or M == 0: nothing
+ * happens.
+ *
+ * A joint state created on a counts handle takes the dense route of the scale-marginalised likelihood; every curve
+ * scoring of it -- mdns_joint_init_curves, mdns_backend_draw_curves[_dev] -- is this likelihood; jitter, accept,
+ * commit and mailbox are the same.  Such a state takes curve chunks ONLY: mdns_joint_init_gauss,
+ * mdns_joint_init_muse3, mdns_backend_draw_chunk, mdns_backend_draw_score, mdns_backend_draw_band[_begin] and
+ * mdns_joint_score_dev fail on it with "counts spectra take curve chunks only ..." (and leave it usable).
+ * mdns_spectra_set_fixed_scale and mdns_spectra_set_continuum(P > 0) fail on the handle as on any without
+ * variances.  The Gaussian batch functions (mdns_gauss_loglike_batch, mdns_curve_loglike_batch*) keep computing what
+ * their names say, from the y that is on the handle.
+ * ------------------------------------------------------------------------------------------ */
+int mdns_spectra_set_counts(mdns_spectra *s, const double *exposure, const double *offsets);
+int mdns_spectra_counts(const mdns_spectra *s);
+int mdns_curve_poisson_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout);
+int mdns_curve_poisson_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                                 double *d_Lout);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,8 @@ ABI_SYMBOLS = (
     "mdns_spectra_set_continuum", "mdns_spectra_continuum", "mdns_muse_continuum_fit_batch", "mdns_muse_continuum_fit_batch_dev",
     # Part 9: caller-made curves at fixed scale with per-pixel variances (csrc/mdns_curves.hip k_curve_rows_w)
     "mdns_curve_chi2_batch", "mdns_curve_chi2_batch_dev", "mdns_spectra_set_fixed_scale", "mdns_spectra_fixed_scale",
+    # Part 10: caller-made curves against photon counts, the Poisson likelihood (csrc/mdns_curves.hip k_curve_rows_p)
+    "mdns_spectra_set_counts", "mdns_spectra_counts", "mdns_curve_poisson_batch", "mdns_curve_poisson_batch_dev",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -220,6 +222,10 @@ def _declare(lib):
         "mdns_curve_chi2_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
         "mdns_spectra_set_fixed_scale": (i, [vp, i]),
         "mdns_spectra_fixed_scale": (i, [vp]),
+        "mdns_spectra_set_counts": (i, [vp, vp, vp]),
+        "mdns_spectra_counts": (i, [vp]),
+        "mdns_curve_poisson_batch": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_curve_poisson_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

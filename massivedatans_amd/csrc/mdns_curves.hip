@@ -38,7 +38,46 @@
 // finite y (like.WeightedSpectra sees to both) -- gives t = +-0 and fma(+-0, d, acc) = acc for every finite d, bit for
 // bit (acc = +0 stays +0: +0 + -0 = +0): the kernel does not look for masks.  As above, the bits of a pair do not
 // depend on B, M, where either sits in its batch, ldc, the grid split or the entry point.
+//
+// The same curves as expected count RATES against photon counts (include/mdns.h Part 10, mdns_curve_poisson_batch[_dev]):
+//
+//   L[b][k] = sum_j ( n[row_k][j] log(max(c[b][j], tiny)) - e[row_k][j] c[b][j] ) + K[row_k],   tiny = DBL_MIN
+//
+// n = s->d_y (counts), e = s->d_e (exposures), K = s->d_koff (the host's sum n (1 + log e - log n)): -C/2 of the C
+// statistic.  Two kernels:
+//
+// k_curve_log    curves [B][ldc] -> pairs {lc, c'} [B][ldp] (ldp = nx rounded up to a whole stage): c' = c for c >= 0
+//                (-0 included) and NaN otherwise, lc = log(fmax(c', tiny)) by the device library's fp64 log; {0, 0}
+//                behind channel nx.  One log per candidate and channel, never one per pair.
+// k_curve_rows_p k_curve_rows_w's tiling -- 128 selected spectra x 32 candidates per workgroup, two spectra per lane,
+//                eight candidates per wave, the next stage's loads in flight in registers -- in stages of SIXTEEN
+//                channels.  Sixteen lanes still read one row per stage: lanes 0-7 its eight channel pairs of n, lanes
+//                8-15 the same of e (2 x 128 contiguous bytes), into two [channel pair][spectrum] arrays of 16-byte
+//                slots, 129 slots per pair.  The bank argument above holds unchanged: a store group of ds_write_b128 is
+//                eight contiguous lanes -- the eight channel pairs of one spectrum in ONE of the two arrays --, 129
+//                slots = 516 dwords = 4 mod 32 apart: eight times four different banks.  The curve stage holds the
+//                pair {lc, c'} of a candidate and channel in one 16-byte slot, [candidate][channel]: a store group is
+//                128 contiguous bytes, a read the same address in all lanes.  LDS: 2 x 8 x 129 x 16 B + 32 x 16 x 16 B
+//                = 41 216 B, THREE workgroups per CU (123 648 of 163 840 B); registers allow the third (DESIGN section 4:
+//                the figures).  Per pair of channels a wave issues 4 + 16 16-byte LDS reads (80 LDS cycles) against 64
+//                fp64 instructions (256 cycles of its SIMD): with four SIMDs on one LDS, 320 cycles of LDS stand
+//                against 256 of arithmetic -- the curve broadcast, twice k_curve_rows_w's, is what bounds this kernel,
+//                still below that kernel's 384 cycles of arithmetic.
+//
+// Per (curve, spectrum) pair the sum is ONE chain: channels in ascending order, from acc = +0:
+//     acc = fma(n, lc, acc);  acc = fma(-e, c', acc);                          L = acc + K
+// Channels past the last one are staged as n = e = 0 and {lc, c'} = {0, 0}: fma(+-0, 0, acc) = acc.  A masked pixel
+// is n = e = 0 (mdns_spectra_set_counts zeroes n where e = 0): fma(0, lc, acc) = acc and fma(-0, c', acc) = acc for
+// every finite lc and c', bit for bit -- a deleted channel; the kernel does not look for masks.  c = +-0 gives
+// lc = log(tiny), about -708.4: nothing where n = 0, n log(tiny) where n > 0, finite and ordered.  A negative or NaN
+// curve value is c' = NaN, and fma(-e, NaN, acc) is NaN even at e = 0: NaN for every spectrum, which the accept test
+// rejects.  +inf is not validated.  The bits of a pair do not depend on B, M, where either sits in its batch, ldc,
+// the grid split or the entry point.
 #include "mdns_internal.h"
+
+#include <cfloat>
+#include <cmath>
+#include <vector>
 
 namespace mdns {
 
@@ -209,6 +248,113 @@ __global__ __launch_bounds__(256) void k_curve_rows_w(
 	}
 }
 
+// ---- counts: the Poisson likelihood (file header) ----
+static constexpr int kCountCH = 16;                       // channels per stage of k_curve_rows_p
+// row stride, in {lc, c'} pairs, of the block k_curve_log stages: whole stages, so that k_curve_rows_p tests no channel
+static inline int count_ld(int nx) { return (nx + kCountCH - 1) / kCountCH * kCountCH; }
+
+// curves [B][ldc] -> staged [B][ldp] pairs {lc, c'}: c' = c for c >= 0 (and -0), NaN otherwise; lc = log(fmax(c', tiny))
+// (fmax drops the NaN: lc is finite, the NaN travels in c'); {0, 0} behind channel nx
+__global__ __launch_bounds__(256) void k_curve_log(const double *__restrict__ curves, int ldc, int nx, double2 *__restrict__ staged, int ldp)
+{
+	const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+	if (j >= ldp) return;
+	double2 p = make_double2(0.0, 0.0);
+	if (j < nx) {
+		const double c = curves[(size_t) b * ldc + j];
+		p.y = c >= 0.0 ? c : (double) NAN;
+		p.x = log(fmax(p.y, DBL_MIN));
+	}
+	staged[(size_t) b * ldp + j] = p;
+}
+
+// L[b][k] = sum_j (n lc - e c') + K from the staged pairs P [B][ldp] (k_curve_log), the counts Y and exposures E
+// [ndata][ld] and the offsets K [ndata]: k_curve_rows_w's tiling in stages of sixteen channels (file header: layout, chain)
+__global__ __launch_bounds__(256) void k_curve_rows_p(
+    const double *__restrict__ Y, const double *__restrict__ E, const double *__restrict__ K, int ld, int nx,
+    const double2 *__restrict__ P, int ldp, int B, const int *__restrict__ rows, int M, double *__restrict__ out)
+{
+	__shared__ __attribute__((aligned(16))) double2 ne[2][kCountCH / 2][kCurveSlots];    // n, e: [channel pair][spectrum]
+	__shared__ __attribute__((aligned(16))) double2 ps[kCurveCands][kCountCH];           // {lc, c'}: [candidate][channel]
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int k0 = blockIdx.x * kCurveSpectra, b0 = blockIdx.y * kCurveCands;
+	// what this thread brings in per stage: channel pair cp of n (lanes 0-7 of sixteen) or of e (lanes 8-15) of the
+	// spectra rsub, rsub + 16, ... (sixteen lanes read 2 x 128 bytes of one row), and channel cch of the candidates
+	// crow, crow + 16
+	const int cp = lane & 7, which = (lane >> 3) & 1, rsub = wave * 4 + (lane >> 4);
+	const int cch = threadIdx.x & 15, crow = threadIdx.x >> 4;
+	const double *src[kCurveSpectra / 16];
+#pragma unroll
+	for (int i = 0; i < kCurveSpectra / 16; i++) {
+		const int k = k0 + rsub + 16 * i;
+		const int kk = k < M ? k : M - 1;                                     // (past the selection: its last row again, never stored)
+		src[i] = (which ? E : Y) + (size_t) (rows ? rows[kk] : kk) * ld + 2 * cp;
+	}
+	double2 sv[kCurveSpectra / 16], pv[kCurveCands / 16];
+	auto fetch = [&](int j0) {
+		const int j = j0 + 2 * cp;
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) {
+			// (rows are 16-byte aligned and an even number of doubles long: the pair of an even channel below nx is inside)
+			double2 v = make_double2(0.0, 0.0);
+			if (j < nx) v = *reinterpret_cast<const double2 *>(src[i] + j0);
+			if (j + 1 >= nx) v.y = 0.0;
+			sv[i] = v;
+		}
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 16; i++) {
+			const int b = b0 + crow + 16 * i;
+			pv[i] = b < B ? P[(size_t) b * ldp + j0 + cch] : make_double2(0.0, 0.0);          // (j0 + cch < ldp: whole stages)
+		}
+	};
+	double acc[kCurveNC][2];
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) acc[c][0] = acc[c][1] = 0.0;
+	const bool working = b0 + wave * kCurveNC < B;                            // wave-uniform; an idle wave still stages
+	fetch(0);
+	for (int j0 = 0; j0 < nx; j0 += kCountCH) {
+#pragma unroll
+		for (int i = 0; i < kCurveSpectra / 16; i++) ne[which][cp][rsub + 16 * i] = sv[i];
+#pragma unroll
+		for (int i = 0; i < kCurveCands / 16; i++) ps[crow + 16 * i][cch] = pv[i];
+		__syncthreads();
+		if (j0 + kCountCH < nx) fetch(j0 + kCountCH);
+		if (working) {
+#pragma unroll 4
+			for (int jp = 0; jp < kCountCH / 2; jp++) {
+				const double2 na = ne[0][jp][lane], nb = ne[0][jp][lane + 64];
+				const double2 ea = ne[1][jp][lane], eb = ne[1][jp][lane + 64];
+#pragma unroll
+				for (int c = 0; c < kCurveNC; c++) {
+					const double2 p = ps[wave * kCurveNC + c][2 * jp], q = ps[wave * kCurveNC + c][2 * jp + 1];
+					acc[c][0] = fma(na.x, p.x, acc[c][0]); acc[c][0] = fma(-ea.x, p.y, acc[c][0]);
+					acc[c][0] = fma(na.y, q.x, acc[c][0]); acc[c][0] = fma(-ea.y, q.y, acc[c][0]);
+					acc[c][1] = fma(nb.x, p.x, acc[c][1]); acc[c][1] = fma(-eb.x, p.y, acc[c][1]);
+					acc[c][1] = fma(nb.y, q.x, acc[c][1]); acc[c][1] = fma(-eb.y, q.y, acc[c][1]);
+				}
+			}
+		}
+		__syncthreads();
+	}
+	if (!working) return;
+	const int ka = k0 + lane, kb = ka + 64;
+	const double Ka = ka < M ? K[rows ? rows[ka] : ka] : 0.0, Kb = kb < M ? K[rows ? rows[kb] : kb] : 0.0;
+#pragma unroll
+	for (int c = 0; c < kCurveNC; c++) {
+		const int b = b0 + wave * kCurveNC + c;
+		if (b >= B) break;
+		if (ka < M) out[(size_t) b * M + ka] = acc[c][0] + Ka;
+		if (kb < M) out[(size_t) b * M + kb] = acc[c][1] + Kb;
+	}
+}
+
+// y[i] = 0 where e[i] == 0, over the whole [ndata][ld] block (mdns_spectra_set_counts: a masked pixel holds no counts)
+__global__ __launch_bounds__(256) void k_counts_mask(double *__restrict__ y, const double *__restrict__ e, size_t n)
+{
+	const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
+	if (i < n && e[i] == 0.0) y[i] = 0.0;
+}
+
 // curves [B][ldc] -> templates [B][ldm] as the K2 row kernels take them: zero behind channel nx
 __global__ __launch_bounds__(256) void k_curve_pad(const double *__restrict__ curves, int ldc, int nx, double *__restrict__ model, int ldm)
 {
@@ -237,6 +383,21 @@ bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc,
 	return launched("k_curve_rows_w");
 }
 
+bool launch_curve_poisson(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
+{
+	Context *c = ctx();
+	if (B <= 0 || M <= 0) return true;
+	const int ldp = count_ld(s->nx);
+	if (!ensure_model(s, (size_t) B * ldp * 2)) return false;
+	double2 *staged = reinterpret_cast<double2 *>(s->d_model.get());
+	hipLaunchKernelGGL(k_curve_log, dim3((ldp + 255) / 256, B), dim3(256), 0, c->stream, d_curves, ldc, s->nx, staged, ldp);
+	if (!launched("k_curve_log")) return false;
+	const dim3 grid((M + kCurveSpectra - 1) / kCurveSpectra, (B + kCurveCands - 1) / kCurveCands);
+	hipLaunchKernelGGL(k_curve_rows_p, grid, dim3(256), 0, c->stream, (const double *) s->d_y.get(), (const double *) s->d_e.get(),
+	                   (const double *) s->d_koff.get(), s->ld, s->nx, (const double2 *) staged, ldp, B, d_rows, M, d_out);
+	return launched("k_curve_rows_p");
+}
+
 bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm)
 {
 	Context *c = ctx();
@@ -249,9 +410,11 @@ bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_
 
 using namespace mdns;
 
-// what both device entry points check first; 1: refused, 0: go on, -1: nothing to score
+// what the device entry points check first; 1: refused, 0: go on, -1: nothing to score.  needs: what the likelihood asks
+// of the handle
+enum { kNeedsNothing = 0, kNeedsVariances = 1, kNeedsCounts = 2 };
 static int curve_batch_check(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
-                             const double *d_Lout, bool weighted, const char *who)
+                             const double *d_Lout, int needs, const char *who)
 {
 	if (!ctx()) return 1;
 	if (!s) { set_error("%s: null spectra handle", who); return 1; }
@@ -259,7 +422,8 @@ static int curve_batch_check(const mdns_spectra *s, const double *d_curves, int 
 		set_error("%s: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", who, B, M, s->ndata, ldc, s->nx);
 		return 1;
 	}
-	if (weighted && !s->d_w.get()) { set_error("%s: spectra were created without variances", who); return 1; }
+	if (needs == kNeedsVariances && !s->d_w.get()) { set_error("%s: spectra were created without variances", who); return 1; }
+	if (needs == kNeedsCounts && !s->counts) { set_error("%s: spectra are not in counts mode (mdns_spectra_set_counts)", who); return 1; }
 	if (B == 0 || M == 0) return -1;
 	if (!d_curves || !d_Lout) { set_error("%s: null argument", who); return 1; }
 	return 0;
@@ -268,7 +432,7 @@ static int curve_batch_check(const mdns_spectra *s, const double *d_curves, int 
 extern "C" int mdns_curve_loglike_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, double noise_level,
                                             const int *d_row_ids, int M, double *d_Lout)
 {
-	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, false, "mdns_curve_loglike_batch_dev");
+	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, kNeedsNothing, "mdns_curve_loglike_batch_dev");
 	if (rc != 0) return rc > 0;
 	return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (noise_level * noise_level), d_row_ids, M, d_Lout) ? 0 : 1;
 }
@@ -276,7 +440,7 @@ extern "C" int mdns_curve_loglike_batch_dev(mdns_spectra *s, const double *d_cur
 extern "C" int mdns_curve_chi2_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
                                          double *d_Lout)
 {
-	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, true, "mdns_curve_chi2_batch_dev");
+	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, kNeedsVariances, "mdns_curve_chi2_batch_dev");
 	if (rc != 0) return rc > 0;
 	return launch_curve_rows_w(s, d_curves, ldc, B, d_row_ids, M, d_Lout) ? 0 : 1;
 }
@@ -293,5 +457,65 @@ extern "C" int mdns_spectra_set_fixed_scale(mdns_spectra *s, int on)
 		return 1;
 	}
 	s->fixed_scale = on ? 1 : 0;
+	return 0;
+}
+
+extern "C" int mdns_curve_poisson_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                                            double *d_Lout)
+{
+	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, kNeedsCounts, "mdns_curve_poisson_batch_dev");
+	if (rc != 0) return rc > 0;
+	return launch_curve_poisson(s, d_curves, ldc, B, d_row_ids, M, d_Lout) ? 0 : 1;
+}
+
+extern "C" int mdns_spectra_counts(const mdns_spectra *s) { return s ? s->counts : -1; }
+
+extern "C" int mdns_spectra_set_counts(mdns_spectra *s, const double *exposure, const double *offsets)
+{
+	if (!s) { set_error("mdns_spectra_set_counts: null spectra handle"); return 1; }
+	Context *c = ctx();
+	if (!c) return 1;
+	if (s->d_w.get()) { set_error("mdns_spectra_set_counts: spectra were created with variances (counts carry none: their noise is Poisson)"); return 1; }
+	if (s->njoint > 0) { set_error("mdns_spectra_set_counts: a joint state exists on these spectra (set the mode first)"); return 1; }
+	const int ndata = s->ndata, nx = s->nx, ld = s->ld;
+	// the host copy is looked at before anything is uploaded
+	bool any_zero = false;
+	if (exposure) {
+		for (int k = 0; k < ndata; k++)
+			for (int j = 0; j < nx; j++) {
+				const double e = exposure[(size_t) k * nx + j];
+				if (!(e >= 0.0) || std::isinf(e)) {
+					set_error("mdns_spectra_set_counts: exposure[%d][%d] = %g: exposures must be finite and >= 0 (0 masks a pixel)", k, j, e);
+					return 1;
+				}
+				any_zero = any_zero || e == 0.0;
+			}
+	}
+	// rows as the kernels read them: [ndata][ld] with the slack of d_y, zero behind channel nx
+	const size_t elems = (size_t) ndata * ld + 2;
+	std::vector<double> e_rows(elems, 0.0), koff((size_t) (ndata > 0 ? ndata : 1), 0.0);
+	for (int k = 0; k < ndata; k++)
+		for (int j = 0; j < nx; j++) e_rows[(size_t) k * ld + j] = exposure ? exposure[(size_t) k * nx + j] : 1.0;
+	if (offsets) for (int k = 0; k < ndata; k++) koff[k] = offsets[k];
+	// made in locals and installed on success: the handle stays as it was when this call fails
+	DeviceBuffer<double> d_e, d_koff;
+	if (!d_e.make(elems) || !d_koff.make(koff.size())) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(d_e.get(), e_rows.data(), elems * sizeof(double), hipMemcpyHostToDevice, c->stream)) ||
+	    !MDNS_HIP(hipMemcpyAsync(d_koff.get(), koff.data(), koff.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) ||
+	    !MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
+	if (any_zero && ndata > 0 && nx > 0) {
+		// a masked pixel holds no counts; what the handle keeps derived from y follows (the Gaussian batch functions then
+		// score the y that is on the handle)
+		hipLaunchKernelGGL(k_counts_mask, dim3((unsigned) ((elems + 255) / 256)), dim3(256), 0, c->stream, s->d_y.get(), (const double *) d_e.get(), elems);
+		if (!launched("k_counts_mask")) return 1;
+		bool ok = true;
+		if (s->d_yT.get()) ok = launch_tile_columns(s->d_y.get(), ld, ndata, nx, nullptr, s->d_yT.get());
+		if (ok && s->d_ysq.get()) ok = launch_row_sumsq(s->d_y.get(), ld, nx, ndata, s->d_ysq.get());
+		if (!ok || !MDNS_HIP(hipStreamSynchronize(c->stream))) return 1;
+		s->d_yG.release();                                        // (made again from the new y on first use)
+	}
+	s->d_e = std::move(d_e);
+	s->d_koff = std::move(d_koff);
+	s->counts = 1;
 	return 0;
 }

@@ -216,6 +216,12 @@ struct mdns_spectra {
 	// scoring of a joint state on this handle is -0.5 sum w (c - y)^2 and the state takes curve chunks only.  Needs
 	// variances, excludes a continuum; fixed like the line list (njoint)
 	int fixed_scale = 0;
+	// photon counts (mdns_curves.hip, mdns_spectra_set_counts): 1 = d_y holds counts n, d_e [ndata, ld] the exposures
+	// (0 = a masked pixel, whose n is 0 too; zero behind channel nx), d_koff [ndata] the host's offsets K; every curve
+	// scoring of a joint state on this handle is the Poisson likelihood sum (n log c - e c) + K and the state takes curve
+	// chunks only.  Excludes variances (d_w means 1/v to every K2 function); fixed like the line list (njoint)
+	int counts = 0;
+	mdns::DeviceBuffer<double> d_e, d_koff;
 };
 
 namespace mdns {
@@ -366,6 +372,10 @@ bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_
 // the same curves against the selected rows of s->d_y with the per-pixel weights s->d_w (which must be there):
 // d_out [B][M] = -0.5 sum_j w_j (c_j - y_j)^2 (k_curve_rows_w: one chain per pair, channels ascending)
 bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
+// the same curves as count rates against the selected rows of a handle in counts mode (s->d_e, s->d_koff must be there):
+// d_out [B][M] = sum_j (n_j log max(c_j, DBL_MIN) - e_j c_j) + K (k_curve_log into s->d_model, then k_curve_rows_p: one
+// chain per pair, channels ascending)
+bool launch_curve_poisson(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
 
 // launchers implemented in mdns_neighbors.hip
 // What a radius computation leaves behind: written by the LAST workgroup of the bootstrap

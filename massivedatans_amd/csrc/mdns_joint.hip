@@ -496,8 +496,9 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	if (shelf_cap < 4) shelf_cap = 4;
 	mdns_joint *j = new mdns_joint();
 	j->s = s; j->nlive = nlive; j->cap = shelf_cap; j->ndata = s->ndata;
-	// spectra with variances: the scale-marginalised likelihood against the three-line template
-	j->kind = s->d_w.get() ? 1 : 0;
+	// spectra with variances: the scale-marginalised likelihood against the three-line template; counts (mdns.h Part 10)
+	// take the same dense route, through curve chunks alone (curves_only)
+	j->kind = s->d_w.get() || s->counts ? 1 : 0;
 	j->nparams = j->kind == 1 ? muse_nparams(s) : 3;
 	const size_t nd = (size_t) s->ndata;
 	const size_t res = (size_t) kFlagInts * sizeof(int) + result_bytes(s->ndata);
@@ -563,10 +564,22 @@ static int joint_reset(mdns_joint *j)
 	       MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) ? 0 : 1;
 }
 
+// A state over fixed-scale spectra (mdns.h Part 9) has no likelihood for parameter rows or templates: K2 would fit the
+// scale.  Nor has one over counts (Part 10): its handle has no weights d_w for K2, and its K1 replicas are not what the
+// Poisson likelihood means.  True (and the error set) for such a state; nothing of it has been touched or read.
+static bool curves_only(const mdns_joint *j, const char *who)
+{
+	if (j->kind != 1 || (!j->s->fixed_scale && !j->s->counts)) return false;
+	set_error("%s: %s spectra take curve chunks only (mdns_joint_init_curves, mdns_backend_draw_curves)", who,
+	          j->s->counts ? "counts" : "fixed-scale");
+	return true;
+}
+
 extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double noise_level)
 {
 	Context *c = ctx();
 	if (!c || !j || !params) return 1;
+	if (curves_only(j, "mdns_joint_init_gauss")) return 1;
 	if (j->kind != 0) { set_error("mdns_joint_init_gauss: these spectra carry variances (mdns_joint_init_muse3)"); return 1; }
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_gauss: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
 	if (!j->h_pin.fit((size_t) j->nlive * 24)) return 1;
@@ -580,14 +593,6 @@ extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double
 	return joint_sync(c) ? 0 : 1;
 }
 
-// A state over fixed-scale spectra (mdns.h Part 9) has no likelihood for parameter rows or templates: K2 would fit the
-// scale.  True (and the error set) for such a state; nothing of it has been touched.
-static bool curves_only(const mdns_joint *j, const char *who)
-{
-	if (j->kind != 1 || !j->s->fixed_scale) return false;
-	set_error("%s: fixed-scale spectra take curve chunks only (mdns_joint_init_curves, mdns_backend_draw_curves)", who);
-	return true;
-}
 
 extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter)
 {
@@ -616,11 +621,12 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 // curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the fixed-noise likelihood from curves
 // (kind 0) or the scale-marginalised one on the curves staged as zero-padded templates (kind 1: exactly what
 // mdns_muse_loglike_batch_dev does with templates), or -- kind 1 on a fixed-scale handle -- the weighted chi^2 at fixed
-// scale (mdns_curve_chi2_batch_dev)
+// scale (mdns_curve_chi2_batch_dev), or -- kind 1 on a counts handle -- the Poisson likelihood (mdns_curve_poisson_batch_dev)
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
 	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
+	if (s->counts) return launch_curve_poisson(s, d_curves, ldc, B, d_rows, M, d_out);
 	if (s->fixed_scale) return launch_curve_rows_w(s, d_curves, ldc, B, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
 	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
@@ -821,6 +827,7 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 {
 	Context *c = ctx();
 	if (!c || !check_draw(j, B, M, "mdns_joint_score_dev")) return 1;
+	if (curves_only(j, "mdns_joint_score_dev")) return 1;
 	if (j->kind != 0) { set_error("mdns_joint_score_dev: Gaussian-line states only (use the mdns_backend_* entry points)"); return 1; }
 	mdns_spectra *s = j->s;
 	j->last_B = 0;

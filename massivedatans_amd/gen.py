@@ -188,7 +188,7 @@ def load(path, ndata=None):
     """Counterpart of sample.py:28-31: ``x`` and the first ``ndata`` columns of ``y``."""
     out = read_datasets(path)
     if ndata is not None:
-        for k in ("y", "v"):
-            if k in out:
+        for k in ("y", "v", "e"):                        # (e: exposures of count spectra, sample.load_model)
+            if k in out and (k != "e" or np.ndim(out[k]) == 2):
                 out[k] = np.ascontiguousarray(out[k][:, :int(ndata)])
     return out

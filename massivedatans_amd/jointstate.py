@@ -508,7 +508,8 @@ class CurveJointState(GaussJointState):
     :class:`massivedatans_amd.like.GaussLineSpectra` the likelihood is the fixed-noise one of sample.py:64-71
     at the spectra's ``noise_level``, over a :class:`massivedatans_amd.like.MuseSpectra` the
     scale-marginalised one of cmuselike.c:45-64, over a :class:`massivedatans_amd.like.WeightedSpectra` the
-    fixed-scale one with per-pixel variances (mdns_curve_chi2_batch).  ``nparams`` is the model's ``ndim``: what the first
+    fixed-scale one with per-pixel variances (mdns_curve_chi2_batch), over a
+    :class:`massivedatans_amd.like.CountSpectra` the Poisson one (mdns_curve_poisson_batch).  ``nparams`` is the model's ``ndim``: what the first
     ``init`` is given, or ``ndim=``.
 
     A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in

@@ -9,6 +9,8 @@ Mirrors the problem-definition surface of the reference driver scripts:
   ``jitter``).
 * :class:`WeightedSpectra` -- per-pixel variances at fixed scale, for model curves the caller makes
   (:mod:`massivedatans_amd.problem`); no counterpart in the reference.
+* :class:`CountSpectra` -- photon counts with per-pixel exposures, the Poisson likelihood for the same model curves; no
+  counterpart in the reference.
 
 All keep the spectra on the device as ``[n_datasets, n_channels]`` rows and add
 ``loglike_batch`` (B candidates per pass), which the reference does not have.
@@ -166,6 +168,68 @@ class WeightedSpectra(_Spectra):
         if curves.shape[1] != self.nx:
             raise ValueError("curves must be [B, %d]" % self.nx)
         return self._batch(self._lib.mdns_curve_chi2_batch, "mdns_curve_chi2_batch", curves, data_mask)
+
+    loglike_batch = loglike_batch_curves
+
+
+def count_pixels(y, e=None, axis=0):
+    """What :class:`CountSpectra` uploads for counts ``y`` and exposures ``e`` of one shape (``e=None``: all ones):
+    ``(y, e, masked, offsets)``, copies in which a pixel whose ``e`` is 0 or NaN, or whose ``y`` is not finite, is MASKED
+    -- ``y = 0``, ``e = 0``, a deleted channel to the likelihood -- and ``masked`` says which.  On a pixel that is not
+    masked ``y < 0``, ``e < 0`` and ``e = inf`` raise ValueError.  ``offsets`` [the other axis]: per spectrum the
+    ``K = sum n (1 + log e - log n)`` over its pixels with ``n > 0`` and ``e > 0`` (``axis``: the channel axis; 0 in
+    the reference's layout ``[nx, ndata]``), summed in np.longdouble and rounded to float64 -- with it the likelihood
+    is ``-C/2`` of the C statistic, 0 for a perfect model.  Needs no device."""
+    y = np.array(y, dtype=np.float64)
+    e = np.ones_like(y) if e is None else np.array(e, dtype=np.float64)
+    if e.shape != y.shape:
+        raise ValueError("e and y differ in shape")
+    masked = (e == 0) | np.isnan(e) | ~np.isfinite(y)
+    bad = ~masked & ((e < 0) | (e == np.inf) | (y < 0))
+    if bad.any():
+        at = tuple(int(i) for i in np.argwhere(bad)[0])
+        if e[at] < 0 or e[at] == np.inf:
+            raise ValueError("e%s = %r: exposures must be finite and >= 0 (0 or NaN masks a pixel)" % (list(at), float(e[at])))
+        raise ValueError("y%s = %r: counts must be >= 0 (a non-finite one masks a pixel)" % (list(at), float(y[at])))
+    y[masked] = 0.0
+    e[masked] = 0.0
+    good = y > 0                                              # (masked pixels hold 0 counts: not among these)
+    n, ee = np.where(good, y, 1.0).astype(np.longdouble), np.where(good, e, 1.0).astype(np.longdouble)
+    terms = np.where(good, n * (1 + np.log(ee) - np.log(n)), np.longdouble(0))
+    return y, e, masked, terms.sum(axis=axis).astype(np.float64)
+
+
+class CountSpectra(_Spectra):
+    """Photon counts scored against model curves the caller made (include/mdns.h Part 10): the Poisson likelihood
+    ``L = sum_j (n_j log c_j - e_j c_j) + K``, the curve ``c >= 0`` the expected count RATE per unit ``exposure``
+    (default 1) -- ``-C/2`` of the C statistic of X-ray fitting.  A pixel with ``exposure`` 0 or NaN, or a non-finite
+    count, is masked (:func:`count_pixels`) and contributes nothing; ``n_masked`` [ndata] counts them per spectrum.  A
+    curve value of 0 where counts were seen costs ``n log(DBL_MIN)``; a negative or NaN one makes the candidate's
+    likelihood NaN for every spectrum.  A joint state on these spectra
+    (:class:`massivedatans_amd.jointstate.CurveJointState`) scores its curve chunks the same way."""
+
+    continuum = 0
+
+    def __init__(self, x, y, exposure=None, layout="channel_major"):
+        channel_major = layout == "channel_major"
+        y, e, masked, offsets = count_pixels(y, exposure, axis=0 if channel_major else 1)
+        super(CountSpectra, self).__init__(x, y, None, layout)
+        self.n_masked = masked.sum(axis=0 if channel_major else 1)
+        rows = None
+        if exposure is not None or masked.any():              # one spectrum per row, as the handle keeps them
+            rows = np.ascontiguousarray(e.T if channel_major else e)
+        offsets = np.ascontiguousarray(offsets)
+        rc = self._lib.mdns_spectra_set_counts(self._h, _lib.ptr(rows) if rows is not None else None, _lib.ptr(offsets))
+        if rc != 0:
+            self.close()
+            _lib.check(rc, "mdns_spectra_set_counts")
+
+    def loglike_batch_curves(self, curves, data_mask=None):
+        """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_poisson_batch)."""
+        curves = np.atleast_2d(_lib.as_f64(curves))
+        if curves.shape[1] != self.nx:
+            raise ValueError("curves must be [B, %d]" % self.nx)
+        return self._batch(self._lib.mdns_curve_poisson_batch, "mdns_curve_poisson_batch", curves, data_mask)
 
     loglike_batch = loglike_batch_curves
 

@@ -26,10 +26,13 @@ import numpy
 MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
 
 
-def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True):
+def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True, poisson=False, exposure=None):
     """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood
-    (``continuum``: like.MuseSpectra), or -- ``marginalise_scale=False`` -- the fixed-scale one (like.WeightedSpectra)."""
-    from .like import GaussLineSpectra, MuseSpectra, WeightedSpectra
+    (``continuum``: like.MuseSpectra), or -- ``marginalise_scale=False`` -- the fixed-scale one (like.WeightedSpectra), or
+    -- ``poisson=True``, ``y`` holding counts -- the Poisson one (``exposure``: like.CountSpectra)."""
+    from .like import CountSpectra, GaussLineSpectra, MuseSpectra, WeightedSpectra
+    if poisson:
+        return CountSpectra(x, y, exposure)
     if v is None:
         return GaussLineSpectra(x, y, noise_level=noise_level)
     if not marginalise_scale:
@@ -56,7 +59,7 @@ class _ModelScorer(object):
 
 class CurveProblem(object):
     """``x`` f64[nx], ``y`` (and ``v``) f64[nx, ndata] in the reference's layout.  ``model(xs[B, ndim]) ->
-    curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Three
+    curves[B, nx]`` and ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` are the caller's.  Four
     likelihoods:
 
     * without ``v``: ``-0.5 sum_j ((curve_j - y_j) / noise_level)**2`` (sample.py:64-71), one noise level for every
@@ -67,7 +70,14 @@ class CurveProblem(object):
       (:mod:`massivedatans_amd.continuum`).  The amplitude of the model drops out: do not make it a parameter;
     * with ``v`` and ``marginalise_scale=False``: ``-0.5 sum_j (curve_j - y_j)**2 / v_j`` at FIXED scale, for a
       model whose amplitude is a parameter.  A pixel with ``v = inf`` (or NaN, or a non-finite ``y``) is ignored
-      (:class:`massivedatans_amd.like.WeightedSpectra`).  Needs ``v``, excludes ``continuum``.
+      (:class:`massivedatans_amd.like.WeightedSpectra`).  Needs ``v``, excludes ``continuum``;
+    * with ``poisson=True``: ``y`` holds photon COUNTS, the curve is the expected count rate per unit ``exposure``
+      (f64[nx, ndata], default 1) and the likelihood the Poisson one, ``sum_j (y_j log curve_j - exposure_j curve_j)``
+      plus a constant per spectrum that makes it ``-C/2`` of the C statistic.  The curve must be ``>= 0``: 0 where counts
+      were seen costs about ``-708`` per count, a negative or NaN value makes the candidate NaN for every spectrum (it is
+      then never accepted).  A pixel with ``exposure`` 0 (or NaN, or a non-finite count) is ignored
+      (:class:`massivedatans_amd.like.CountSpectra`).  Excludes ``v``, ``continuum`` and ``marginalise_scale=False``;
+      ``noise_level`` is not used.
 
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
@@ -77,10 +87,19 @@ class CurveProblem(object):
     Gives ``sample.build_sampler`` what it reads of a problem."""
 
     def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None,
-                 continuum=0, marginalise_scale=True):
+                 continuum=0, marginalise_scale=True, poisson=False, exposure=None):
         from .continuum import check_terms
         self.continuum = check_terms(continuum)
         self.marginalise_scale = bool(marginalise_scale)
+        self.poisson = bool(poisson)
+        if self.poisson and v is not None:
+            raise ValueError("poisson = True excludes the variances v (the noise of counts is Poisson, not Gaussian)")
+        if self.poisson and self.continuum:
+            raise ValueError("poisson = True excludes continuum = %d (it belongs to the scale-marginalised likelihood)" % self.continuum)
+        if self.poisson and not self.marginalise_scale:
+            raise ValueError("poisson = True excludes marginalise_scale = False (that is the Gaussian likelihood with variances)")
+        if exposure is not None and not self.poisson:
+            raise ValueError("exposure needs poisson = True (the Gaussian likelihoods have no exposure)")
         if self.continuum and v is None:
             raise ValueError("continuum = %d needs the variances v (the scale-marginalised likelihood)" % self.continuum)
         if not self.marginalise_scale and v is None:
@@ -91,6 +110,7 @@ class CurveProblem(object):
         self.x = numpy.ascontiguousarray(x, dtype=float)
         self.y = numpy.ascontiguousarray(y, dtype=float)
         self.v = None if v is None else numpy.ascontiguousarray(v, dtype=float)
+        self.exposure = None if exposure is None else numpy.ascontiguousarray(exposure, dtype=float)
         self.nx, self.ndata = self.y.shape
         if not 1 <= int(ndim) <= MAX_DIM:
             raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
@@ -103,6 +123,10 @@ class CurveProblem(object):
             kw = dict(continuum=self.continuum) if self.continuum else {}
             if not self.marginalise_scale:
                 kw["marginalise_scale"] = False
+            if self.poisson:
+                kw["poisson"] = True
+                if self.exposure is not None:
+                    kw["exposure"] = self.exposure
             backend = default_backend(self.x, self.y, self.noise_level, self.v, **kw)
         self.backend = backend
         if getattr(backend, "continuum", 0) != self.continuum:

@@ -246,7 +246,9 @@ def load_model(path):
     """A ``MDNS_MODEL`` file: Python that defines ``model(xs[B, ndim]) -> curves[B, nx]``,
     ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` and ``ndim``, optionally ``noise_level`` and
     ``marginalise_scale`` (default True; False: the fixed-scale likelihood of problem.CurveProblem, which needs
-    variances ``v`` in the data file).  Returns them as a dict; ValueError says what is wrong with the file."""
+    variances ``v`` in the data file) and ``poisson`` (default False; True: ``y`` of the data file holds photon counts,
+    ``e`` -- if there -- their exposures, and the likelihood is the Poisson one of problem.CurveProblem; the data file
+    must not hold ``v``).  Returns them as a dict; ValueError says what is wrong with the file."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("mdns_model", path)
     if spec is None or spec.loader is None:
@@ -263,6 +265,7 @@ def load_model(path):
         out[name] = getattr(module, name)
     out["noise_level"] = float(getattr(module, "noise_level", noise_level))
     out["marginalise_scale"] = bool(getattr(module, "marginalise_scale", True))
+    out["poisson"] = bool(getattr(module, "poisson", False))
     return out
 
 
@@ -417,13 +420,17 @@ def main(argv=None):
     backend = None
     if definition is not None:
         # the caller's own model (massivedatans_amd.problem): variances `v` in the data file select the
-        # scale-marginalised likelihood, or -- `marginalise_scale = False` in the model file -- the fixed-scale one
+        # scale-marginalised likelihood, or -- `marginalise_scale = False` in the model file -- the fixed-scale one;
+        # `poisson = True` in the model file the Poisson likelihood of counts `y` with exposures `e`
         from . import problem as problem_module
+        if definition['poisson'] and data.get('v') is not None:
+            sys.exit("MDNS_MODEL: poisson = True excludes per-pixel variances `v`, which the data file %s holds (counts carry their own noise)" % argv[1])
         if not definition['marginalise_scale'] and data.get('v') is None:
             sys.exit("MDNS_MODEL: marginalise_scale = False needs per-pixel variances `v` in the data file %s" % argv[1])
         results, sampler, problem, duration = run_model(problem_module.CurveProblem(
             data['x'], data['y'], definition['model'], definition['priortransform_batch'], definition['ndim'],
-            noise_level=definition['noise_level'], v=data.get('v'), marginalise_scale=definition['marginalise_scale']), **settings)
+            noise_level=definition['noise_level'], v=data.get('v'), marginalise_scale=definition['marginalise_scale'],
+            **(dict(poisson=True, exposure=data.get('e')) if definition['poisson'] else {})), **settings)
     else:
         backend = distributed_backend(data['x'], data['y'])
         results, sampler, problem, duration = run(data['x'], data['y'], backend=backend, **settings)
