@@ -229,7 +229,8 @@ int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jit
  * fixed-noise likelihood (mdns_curve_loglike_batch) at noise_level, which the curve chunks of this state then use too;
  * with variances the scale-marginalised one (mdns_muse_loglike_batch; noise_level is ignored), or -- on a fixed-scale
  * handle, Part 9 -- mdns_curve_chi2_batch.  On a counts handle (Part 10; no variances, noise_level is ignored)
- * mdns_curve_poisson_batch.  jitter as above. */
+ * mdns_curve_poisson_batch, or -- where that handle has a background, Part 11 -- mdns_curve_wstat_batch.  jitter as
+ * above. */
 int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter);
 /* The same from a host matrix liveL f64[nlive, ndata] (row p = live slot p). */
 int mdns_joint_set_live(mdns_joint *j, const double *liveL);
@@ -618,7 +619,8 @@ int mdns_backend_region_radius(void *joint, void *region, double *radius);
  * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M], both kinds of
  * state).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
  * variances), as mdns_muse_loglike_batch (variances), as mdns_curve_chi2_batch (variances, fixed scale: Part 9) or as
- * mdns_curve_poisson_batch (counts: Part 10), decided and committed like a draw_chunk.  A draw may mix
+ * mdns_curve_poisson_batch (counts: Part 10; with a background mdns_curve_wstat_batch: Part 11), decided and committed
+ * like a draw_chunk.  A draw may mix
  * parameter chunks and curve chunks.  _dev: curves (rows of ldc >= nx doubles) and jitter already in device memory,
  * read on the library stream. */
 int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
@@ -887,6 +889,68 @@ int mdns_spectra_counts(const mdns_spectra *s);
 int mdns_curve_poisson_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout);
 int mdns_curve_poisson_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
                                  double *d_Lout);
+
+/* ------------------------------------------------------------------------------------------
+ * Part 11 -- caller-defined models against photon counts WITH A BACKGROUND SPECTRUM: the W statistic of X-ray
+ * fitting (csrc/mdns_curves.hip, k_curve_rows_b).
+ *
+ * Per spectrum k and channel j, beside the source region's counts n and exposures e of Part 10 (which hold source plus
+ * background): the background region's counts b >= 0 and its exposure g >= 0, the area ratio included, so that g f is
+ * the expected background count in the background region for a background rate f.  f is unknown, one per pixel, and
+ * profiled out of the joint Poisson likelihood of the two spectra in closed form.  The curve c >= 0 is the SOURCE count
+ * rate per unit exposure; c' = c for c >= 0 (-0 included) and NaN otherwise; tiny = DBL_MIN.  Per pixel
+ *
+ *   T = e + g;  N = n + b;  Q = 4 (T b);  T2 = 2 T (1 where T == 0);  b2 = 2 b           (each one rounded operation)
+ *
+ * and per (candidate, spectrum, channel), every operation a rounded fp64 one in this order:
+ *
+ *   a = fma(-T, c', N);  d = sqrt(fma(a, a, Q c'))
+ *   f = (a + d) / T2   where a >= 0
+ *   f = (b2 c') / (d - a)   where not           (the naive form loses every digit for T c' >> N)
+ *   s = c' + f
+ *   acc = fma(n, log(max(s, tiny)), acc);  acc = fma(b, log(max(f, tiny)), acc);  acc = fma(-e, s, acc);  acc = fma(-g, f, acc)
+ *
+ *   L[b][k] = acc over the channels in ascending order from acc = +0, + Kw[row_k]
+ *   Kw[k]   = sum over n > 0 of n (1 + log e - log n)  +  sum over b > 0 of b (1 + log g - log b)      (the caller's)
+ *
+ * That is -W/2: <= 0, and 0 where model plus fitted background reproduce both spectra.  In exact arithmetic f = b/T for
+ * n = 0, f = max(n/T - c', 0) for b = 0, f = 0 for n = b = 0; where b = 0 and c' >= n/T the term is Part 10's.  The
+ * bits of a pair do not depend on B, M, its place in the batch, ldc, the grid split or the entry point; log, sqrt and /
+ * are the device library's fp64 ones.
+ *   masked pixel   n = e = b = g = 0: T2 = 1, f = 0 / 1 = 0, a deleted channel, bit for bit, for every finite c >= 0.
+ *                  A spectrum without a good pixel scores Kw = 0, hence +0.0.
+ *   zero model     c = +-0 where n > 0, b = 0 gives f = n/T > 0: finite, no penalty.  Where n = b = 0 it contributes
+ *                  exactly nothing.
+ *   invalid model  a negative or NaN curve value makes L NaN for EVERY spectrum, masked pixels or not, and for no
+ *                  other candidate of the batch.  +inf is not validated.
+ *
+ * mdns_spectra_set_background(s, bkg_counts, bkg_exposure, offsets): gives a handle that is in counts mode its
+ * background.  bkg_counts f64[ndata][nx] (one spectrum per row, contiguous); bkg_exposure the same shape, or NULL for
+ * all ones; offsets f64[ndata], the Kw[k] -- the caller's, so that no device logarithm enters them --, or NULL for
+ * zeros.  A pixel whose g is 0 or NaN, or whose b is not finite, or which is masked on the handle already (e = 0), is
+ * masked on both sides: n, e, b and g become 0, with what the handle keeps derived from y.  Fails -- the handle stays as
+ * it was -- on a null handle, on a handle that is not in counts mode, once a joint state exists on the handle, on null
+ * counts, and when an exposure is negative or infinite or a count of an unmasked pixel negative (looked for in the host
+ * arrays before anything is uploaded; the message names the index).  There is no way back, and mdns_spectra_set_counts
+ * fails on a handle that has a background.  mdns_spectra_background: 0 or 1 (-1: null handle).
+ *
+ * mdns_curve_wstat_batch[_dev]: arguments, size checks and messages as mdns_curve_poisson_batch[_dev]; on a handle
+ * without a background "spectra have no background (mdns_spectra_set_background)".  B == 0 or M == 0: nothing happens.
+ * mdns_curve_background_batch[_dev]: the same arguments, fout f64[B][M][nx] = the f of every pixel, made by the device
+ * functions the scoring kernel uses (0 at a masked pixel; NaN along an invalid curve value).
+ *
+ * A joint state on such a handle is Part 10's with this likelihood for every curve scoring; it takes curve chunks
+ * only.  mdns_curve_poisson_batch[_dev] on such a handle keep computing what their name says: the C statistic of the n,
+ * e and K that are on it.
+ * ------------------------------------------------------------------------------------------ */
+int mdns_spectra_set_background(mdns_spectra *s, const double *bkg_counts, const double *bkg_exposure, const double *offsets);
+int mdns_spectra_background(const mdns_spectra *s);
+int mdns_curve_wstat_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout);
+int mdns_curve_wstat_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                               double *d_Lout);
+int mdns_curve_background_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *fout);
+int mdns_curve_background_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
+                                    double *d_fout);
 
 #ifdef __cplusplus
 }

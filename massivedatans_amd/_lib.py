@@ -59,6 +59,9 @@ ABI_SYMBOLS = (
     "mdns_curve_chi2_batch", "mdns_curve_chi2_batch_dev", "mdns_spectra_set_fixed_scale", "mdns_spectra_fixed_scale",
     # Part 10: caller-made curves against photon counts, the Poisson likelihood (csrc/mdns_curves.hip k_curve_rows_p)
     "mdns_spectra_set_counts", "mdns_spectra_counts", "mdns_curve_poisson_batch", "mdns_curve_poisson_batch_dev",
+    # Part 11: the same with a background spectrum per spectrum, the W statistic (csrc/mdns_curves.hip k_curve_rows_b)
+    "mdns_spectra_set_background", "mdns_spectra_background", "mdns_curve_wstat_batch", "mdns_curve_wstat_batch_dev",
+    "mdns_curve_background_batch", "mdns_curve_background_batch_dev",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -226,6 +229,12 @@ def _declare(lib):
         "mdns_spectra_counts": (i, [vp]),
         "mdns_curve_poisson_batch": (i, [vp, vp, i, vp, i, vp]),
         "mdns_curve_poisson_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
+        "mdns_spectra_set_background": (i, [vp, vp, vp, vp]),
+        "mdns_spectra_background": (i, [vp]),
+        "mdns_curve_wstat_batch": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_curve_wstat_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
+        "mdns_curve_background_batch": (i, [vp, vp, i, vp, i, vp]),
+        "mdns_curve_background_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

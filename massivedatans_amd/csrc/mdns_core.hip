@@ -596,6 +596,8 @@ static int fn_curve_chi2(mdns_spectra *s, const double *p, int B, const int *r, 
 { return mdns_curve_chi2_batch_dev(s, p, s->nx, B, r, M, o); }
 static int fn_curve_poisson(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_curve_poisson_batch_dev(s, p, s->nx, B, r, M, o); }
+static int fn_curve_wstat(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
+{ return mdns_curve_wstat_batch_dev(s, p, s->nx, B, r, M, o); }
 static int fn_lines(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_lines_loglike_batch_dev(s, p, B, r, M, o); }
 
@@ -616,6 +618,10 @@ extern "C" int mdns_curve_chi2_batch(mdns_spectra *s, const double *curves, int 
 extern "C" int mdns_curve_poisson_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout)
 {
 	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_curve_poisson, "mdns_curve_poisson_batch");
+}
+extern "C" int mdns_curve_wstat_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout)
+{
+	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_curve_wstat, "mdns_curve_wstat_batch");
 }
 extern "C" int mdns_muse_loglike_batch(mdns_spectra *s, const double *ypred, int B,
                                        const int *row_ids, int M, double *Lout)

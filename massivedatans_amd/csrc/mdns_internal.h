@@ -222,6 +222,12 @@ struct mdns_spectra {
 	// chunks only.  Excludes variances (d_w means 1/v to every K2 function); fixed like the line list (njoint)
 	int counts = 0;
 	mdns::DeviceBuffer<double> d_e, d_koff;
+	// a background spectrum per count spectrum (mdns_curves.hip, mdns_spectra_set_background; needs counts): 1 = d_b
+	// [ndata, ld] holds the background region's counts b, d_g its exposures g (area ratio included), d_kw [ndata] the
+	// host's offsets Kw; a pixel masked on either side holds n = e = b = g = 0.  Every curve scoring of a joint state on
+	// this handle is then the W statistic (k_curve_rows_b); fixed like the line list (njoint)
+	int background = 0;
+	mdns::DeviceBuffer<double> d_b, d_g, d_kw;
 };
 
 namespace mdns {
@@ -376,6 +382,11 @@ bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc,
 // d_out [B][M] = sum_j (n_j log max(c_j, DBL_MIN) - e_j c_j) + K (k_curve_log into s->d_model, then k_curve_rows_p: one
 // chain per pair, channels ascending)
 bool launch_curve_poisson(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
+// the same against a handle with a background (s->d_b, s->d_g, s->d_kw must be there): d_out [B][M] = the W statistic's
+// -W/2, the background rate of every pixel profiled out (k_curve_rows_b: one chain per pair, channels ascending)
+bool launch_curve_wstat(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
+// d_out [B][M][nx] = that profiled rate itself (k_curve_background, the device functions of k_curve_rows_b)
+bool launch_curve_background(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
 
 // launchers implemented in mdns_neighbors.hip
 // What a radius computation leaves behind: written by the LAST workgroup of the bootstrap

@@ -622,10 +622,12 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 // (kind 0) or the scale-marginalised one on the curves staged as zero-padded templates (kind 1: exactly what
 // mdns_muse_loglike_batch_dev does with templates), or -- kind 1 on a fixed-scale handle -- the weighted chi^2 at fixed
 // scale (mdns_curve_chi2_batch_dev), or -- kind 1 on a counts handle -- the Poisson likelihood (mdns_curve_poisson_batch_dev)
+// or, where the handle has a background, the W statistic (mdns_curve_wstat_batch_dev)
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
 	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
+	if (s->background) return launch_curve_wstat(s, d_curves, ldc, B, d_rows, M, d_out);
 	if (s->counts) return launch_curve_poisson(s, d_curves, ldc, B, d_rows, M, d_out);
 	if (s->fixed_scale) return launch_curve_rows_w(s, d_curves, ldc, B, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);

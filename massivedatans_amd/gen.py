@@ -188,7 +188,8 @@ def load(path, ndata=None):
     """Counterpart of sample.py:28-31: ``x`` and the first ``ndata`` columns of ``y``."""
     out = read_datasets(path)
     if ndata is not None:
-        for k in ("y", "v", "e"):                        # (e: exposures of count spectra, sample.load_model)
-            if k in out and (k != "e" or np.ndim(out[k]) == 2):
+        # (e: exposures of count spectra; b, eb: their background spectra and those exposures, sample.load_model)
+        for k in ("y", "v", "e", "b", "eb"):
+            if k in out and (k in ("y", "v") or np.ndim(out[k]) == 2):
                 out[k] = np.ascontiguousarray(out[k][:, :int(ndata)])
     return out

@@ -509,7 +509,8 @@ class CurveJointState(GaussJointState):
     at the spectra's ``noise_level``, over a :class:`massivedatans_amd.like.MuseSpectra` the
     scale-marginalised one of cmuselike.c:45-64, over a :class:`massivedatans_amd.like.WeightedSpectra` the
     fixed-scale one with per-pixel variances (mdns_curve_chi2_batch), over a
-    :class:`massivedatans_amd.like.CountSpectra` the Poisson one (mdns_curve_poisson_batch).  ``nparams`` is the model's ``ndim``: what the first
+    :class:`massivedatans_amd.like.CountSpectra` the Poisson one (mdns_curve_poisson_batch; with a background the W
+    statistic, mdns_curve_wstat_batch).  ``nparams`` is the model's ``ndim``: what the first
     ``init`` is given, or ``ndim=``.
 
     A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in

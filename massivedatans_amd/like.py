@@ -9,8 +9,8 @@ Mirrors the problem-definition surface of the reference driver scripts:
   ``jitter``).
 * :class:`WeightedSpectra` -- per-pixel variances at fixed scale, for model curves the caller makes
   (:mod:`massivedatans_amd.problem`); no counterpart in the reference.
-* :class:`CountSpectra` -- photon counts with per-pixel exposures, the Poisson likelihood for the same model curves; no
-  counterpart in the reference.
+* :class:`CountSpectra` -- photon counts with per-pixel exposures, the Poisson likelihood for the same model curves, or
+  -- with a background spectrum per spectrum -- the W statistic; no counterpart in the reference.
 
 All keep the spectra on the device as ``[n_datasets, n_channels]`` rows and add
 ``loglike_batch`` (B candidates per pass), which the reference does not have.
@@ -199,6 +199,38 @@ def count_pixels(y, e=None, axis=0):
     return y, e, masked, terms.sum(axis=axis).astype(np.float64)
 
 
+def background_pixels(y, e, b, g=None, axis=0):
+    """What :class:`CountSpectra` uploads for source-region counts ``y`` with exposures ``e`` (``None``: ones) and
+    background-region counts ``b`` with exposures ``g`` (``None``: ones; the area ratio included), all of one shape:
+    ``(y, e, b, g, masked, offsets)``.  A pixel is MASKED -- all four values 0, a deleted channel to the likelihood -- where
+    :func:`count_pixels` masks ``(y, e)`` or, by the same rule, ``(b, g)``: ``e`` or ``g`` 0 or NaN, ``y`` or ``b`` not
+    finite.  On a pixel that is not masked a negative count and a negative or infinite exposure raise ValueError.
+    ``offsets``: per spectrum ``Kw = sum n (1 + log e - log n) + sum b (1 + log g - log b)`` over its pixels with
+    ``n > 0`` and ``b > 0``, in np.longdouble, rounded to float64: with it the likelihood is ``-W/2`` of the W statistic,
+    0 where model plus fitted background reproduce both spectra.  Needs no device."""
+    y, e, m1, _ = count_pixels(y, e, axis)
+    b = np.array(b, dtype=np.float64)
+    if b.shape != y.shape:
+        raise ValueError("background and y differ in shape")
+    b[m1] = 0.0                                               # (masked already: nothing of it is looked at)
+    g = np.ones_like(b) if g is None else np.array(g, dtype=np.float64)
+    if g.shape == b.shape:
+        g[m1] = 0.0
+    try:
+        b, g, m2, _ = count_pixels(b, g, axis)
+    except ValueError as err:
+        raise ValueError("background: " + str(err).replace("e[", "g[", 1).replace("y[", "b[", 1).replace("e and y", "g and b"))
+    masked = m1 | m2
+    for a in (y, e, b, g):
+        a[masked] = 0.0
+    offsets = np.longdouble(0)
+    for n, ee in ((y, e), (b, g)):
+        good = n > 0                                          # (masked pixels hold 0 counts: not among these)
+        nn, el = np.where(good, n, 1.0).astype(np.longdouble), np.where(good, ee, 1.0).astype(np.longdouble)
+        offsets = offsets + np.where(good, nn * (1 + np.log(el) - np.log(nn)), np.longdouble(0)).sum(axis=axis)
+    return y, e, b, g, masked, np.asarray(offsets).astype(np.float64)
+
+
 class CountSpectra(_Spectra):
     """Photon counts scored against model curves the caller made (include/mdns.h Part 10): the Poisson likelihood
     ``L = sum_j (n_j log c_j - e_j c_j) + K``, the curve ``c >= 0`` the expected count RATE per unit ``exposure``
@@ -206,13 +238,28 @@ class CountSpectra(_Spectra):
     count, is masked (:func:`count_pixels`) and contributes nothing; ``n_masked`` [ndata] counts them per spectrum.  A
     curve value of 0 where counts were seen costs ``n log(DBL_MIN)``; a negative or NaN one makes the candidate's
     likelihood NaN for every spectrum.  A joint state on these spectra
-    (:class:`massivedatans_amd.jointstate.CurveJointState`) scores its curve chunks the same way."""
+    (:class:`massivedatans_amd.jointstate.CurveJointState`) scores its curve chunks the same way.
+
+    With ``background`` -- the counts of a background region per spectrum, of ``y``'s shape, and ``background_exposure``
+    (default 1; the area ratio included) -- ``y`` holds source PLUS background, the curve is the SOURCE rate, and the
+    likelihood is the W statistic (include/mdns.h Part 11, mdns_curve_wstat_batch): an unknown background rate per pixel,
+    profiled out of the joint Poisson likelihood of the two spectra.  A pixel masked on either side
+    (:func:`background_pixels`) is masked; :meth:`background_fit` gives the fitted rates.  A curve value of 0 is then
+    no penalty where the background can carry the counts."""
 
     continuum = 0
 
-    def __init__(self, x, y, exposure=None, layout="channel_major"):
+    def __init__(self, x, y, exposure=None, background=None, background_exposure=None, layout="channel_major"):
         channel_major = layout == "channel_major"
-        y, e, masked, offsets = count_pixels(y, exposure, axis=0 if channel_major else 1)
+        axis = 0 if channel_major else 1
+        if background is None and background_exposure is not None:
+            raise ValueError("background_exposure needs background")
+        self.has_background = background is not None
+        if self.has_background:
+            y, e, b, g, masked, kw = background_pixels(y, exposure, background, background_exposure, axis=axis)
+            offsets = count_pixels(y, e, axis=axis)[3]           # (the C statistic's K of what is left: Part 10 on this handle)
+        else:
+            y, e, masked, offsets = count_pixels(y, exposure, axis=axis)
         super(CountSpectra, self).__init__(x, y, None, layout)
         self.n_masked = masked.sum(axis=0 if channel_major else 1)
         rows = None
@@ -223,13 +270,41 @@ class CountSpectra(_Spectra):
         if rc != 0:
             self.close()
             _lib.check(rc, "mdns_spectra_set_counts")
+        if self.has_background:
+            b_rows = np.ascontiguousarray(b.T if channel_major else b)
+            g_rows = np.ascontiguousarray(g.T if channel_major else g)
+            kw = np.ascontiguousarray(kw)
+            rc = self._lib.mdns_spectra_set_background(self._h, _lib.ptr(b_rows), _lib.ptr(g_rows), _lib.ptr(kw))
+            if rc != 0:
+                self.close()
+                _lib.check(rc, "mdns_spectra_set_background")
 
     def loglike_batch_curves(self, curves, data_mask=None):
-        """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_poisson_batch)."""
+        """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_poisson_batch; with a background
+        mdns_curve_wstat_batch)."""
         curves = np.atleast_2d(_lib.as_f64(curves))
         if curves.shape[1] != self.nx:
             raise ValueError("curves must be [B, %d]" % self.nx)
+        if self.has_background:
+            return self._batch(self._lib.mdns_curve_wstat_batch, "mdns_curve_wstat_batch", curves, data_mask)
         return self._batch(self._lib.mdns_curve_poisson_batch, "mdns_curve_poisson_batch", curves, data_mask)
+
+    def background_fit(self, curves, data_mask=None):
+        """``curves[B, nx]`` -> ``f[B, M, nx]``: the background rate the W statistic fitted to every pixel of every pair,
+        by the device functions its scoring kernel uses (mdns_curve_background_batch) -- ``curves + f`` is the "model +
+        background" a caller plots against ``y / exposure``.  0 at a masked pixel."""
+        if not self.has_background:
+            raise ValueError("these spectra were made without a background")
+        curves = np.atleast_2d(_lib.as_f64(curves))
+        if curves.shape[1] != self.nx:
+            raise ValueError("curves must be [B, %d]" % self.nx)
+        rows, M = _rows_from_mask(data_mask, self.ndata)
+        B = len(curves)
+        f = np.empty((B, M, self.nx))
+        if B and M:
+            _lib.check(self._lib.mdns_curve_background_batch(self._h, _lib.ptr(curves), B, _lib.ptr(rows) if rows is not None else None,
+                                                             M, _lib.ptr(f)), "mdns_curve_background_batch")
+        return f
 
     loglike_batch = loglike_batch_curves
 

@@ -26,13 +26,15 @@ import numpy
 MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
 
 
-def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True, poisson=False, exposure=None):
+def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True, poisson=False, exposure=None,
+                    background=None, background_exposure=None):
     """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood
     (``continuum``: like.MuseSpectra), or -- ``marginalise_scale=False`` -- the fixed-scale one (like.WeightedSpectra), or
-    -- ``poisson=True``, ``y`` holding counts -- the Poisson one (``exposure``: like.CountSpectra)."""
+    -- ``poisson=True``, ``y`` holding counts -- the Poisson one (``exposure``: like.CountSpectra), with ``background``
+    (and ``background_exposure``) the W statistic."""
     from .like import CountSpectra, GaussLineSpectra, MuseSpectra, WeightedSpectra
     if poisson:
-        return CountSpectra(x, y, exposure)
+        return CountSpectra(x, y, exposure, background, background_exposure)
     if v is None:
         return GaussLineSpectra(x, y, noise_level=noise_level)
     if not marginalise_scale:
@@ -77,7 +79,12 @@ class CurveProblem(object):
       were seen costs about ``-708`` per count, a negative or NaN value makes the candidate NaN for every spectrum (it is
       then never accepted).  A pixel with ``exposure`` 0 (or NaN, or a non-finite count) is ignored
       (:class:`massivedatans_amd.like.CountSpectra`).  Excludes ``v``, ``continuum`` and ``marginalise_scale=False``;
-      ``noise_level`` is not used.
+      ``noise_level`` is not used;
+    * with ``poisson=True`` and ``background`` (f64[nx, ndata], the counts of a background region per spectrum;
+      ``background_exposure`` the same shape, default 1, the area ratio included): ``y`` holds source plus background,
+      the curve is the SOURCE rate, and the likelihood is the W statistic -- an unknown background rate per pixel,
+      profiled out in closed form of the joint Poisson likelihood of the two spectra (include/mdns.h Part 11).  A pixel
+      masked on either side is ignored; ``backend.background_fit`` gives the fitted rates.
 
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
@@ -87,7 +94,7 @@ class CurveProblem(object):
     Gives ``sample.build_sampler`` what it reads of a problem."""
 
     def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None,
-                 continuum=0, marginalise_scale=True, poisson=False, exposure=None):
+                 continuum=0, marginalise_scale=True, poisson=False, exposure=None, background=None, background_exposure=None):
         from .continuum import check_terms
         self.continuum = check_terms(continuum)
         self.marginalise_scale = bool(marginalise_scale)
@@ -100,6 +107,10 @@ class CurveProblem(object):
             raise ValueError("poisson = True excludes marginalise_scale = False (that is the Gaussian likelihood with variances)")
         if exposure is not None and not self.poisson:
             raise ValueError("exposure needs poisson = True (the Gaussian likelihoods have no exposure)")
+        if background is not None and not self.poisson:
+            raise ValueError("background needs poisson = True (the W statistic is a likelihood of counts)")
+        if background_exposure is not None and background is None:
+            raise ValueError("background_exposure needs background")
         if self.continuum and v is None:
             raise ValueError("continuum = %d needs the variances v (the scale-marginalised likelihood)" % self.continuum)
         if not self.marginalise_scale and v is None:
@@ -111,6 +122,12 @@ class CurveProblem(object):
         self.y = numpy.ascontiguousarray(y, dtype=float)
         self.v = None if v is None else numpy.ascontiguousarray(v, dtype=float)
         self.exposure = None if exposure is None else numpy.ascontiguousarray(exposure, dtype=float)
+        self.background = None if background is None else numpy.ascontiguousarray(background, dtype=float)
+        self.background_exposure = None if background_exposure is None else numpy.ascontiguousarray(background_exposure, dtype=float)
+        for name in ("background", "background_exposure"):
+            a = getattr(self, name)
+            if a is not None and a.shape != self.y.shape:
+                raise ValueError("%s has shape %s, y has %s" % (name, a.shape, self.y.shape))
         self.nx, self.ndata = self.y.shape
         if not 1 <= int(ndim) <= MAX_DIM:
             raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
@@ -127,6 +144,10 @@ class CurveProblem(object):
                 kw["poisson"] = True
                 if self.exposure is not None:
                     kw["exposure"] = self.exposure
+                if self.background is not None:
+                    kw["background"] = self.background
+                if self.background_exposure is not None:
+                    kw["background_exposure"] = self.background_exposure
             backend = default_backend(self.x, self.y, self.noise_level, self.v, **kw)
         self.backend = backend
         if getattr(backend, "continuum", 0) != self.continuum:

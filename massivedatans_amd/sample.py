@@ -248,7 +248,8 @@ def load_model(path):
     ``marginalise_scale`` (default True; False: the fixed-scale likelihood of problem.CurveProblem, which needs
     variances ``v`` in the data file) and ``poisson`` (default False; True: ``y`` of the data file holds photon counts,
     ``e`` -- if there -- their exposures, and the likelihood is the Poisson one of problem.CurveProblem; the data file
-    must not hold ``v``).  Returns them as a dict; ValueError says what is wrong with the file."""
+    must not hold ``v``; if it holds ``b``, the counts of a background region per spectrum -- and ``eb``, their exposures
+    --, the likelihood is the W statistic).  Returns them as a dict; ValueError says what is wrong with the file."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("mdns_model", path)
     if spec is None or spec.loader is None:
@@ -421,16 +422,20 @@ def main(argv=None):
     if definition is not None:
         # the caller's own model (massivedatans_amd.problem): variances `v` in the data file select the
         # scale-marginalised likelihood, or -- `marginalise_scale = False` in the model file -- the fixed-scale one;
-        # `poisson = True` in the model file the Poisson likelihood of counts `y` with exposures `e`
+        # `poisson = True` in the model file the Poisson likelihood of counts `y` with exposures `e`, or -- where the data
+        # file holds background counts `b` (and exposures `eb`) -- the W statistic
         from . import problem as problem_module
         if definition['poisson'] and data.get('v') is not None:
             sys.exit("MDNS_MODEL: poisson = True excludes per-pixel variances `v`, which the data file %s holds (counts carry their own noise)" % argv[1])
+        if data.get('eb') is not None and data.get('b') is None:
+            sys.exit("MDNS_MODEL: the data file %s holds background exposures `eb` but no background counts `b`" % argv[1])
         if not definition['marginalise_scale'] and data.get('v') is None:
             sys.exit("MDNS_MODEL: marginalise_scale = False needs per-pixel variances `v` in the data file %s" % argv[1])
         results, sampler, problem, duration = run_model(problem_module.CurveProblem(
             data['x'], data['y'], definition['model'], definition['priortransform_batch'], definition['ndim'],
             noise_level=definition['noise_level'], v=data.get('v'), marginalise_scale=definition['marginalise_scale'],
-            **(dict(poisson=True, exposure=data.get('e')) if definition['poisson'] else {})), **settings)
+            **(dict(poisson=True, exposure=data.get('e'), background=data.get('b'), background_exposure=data.get('eb'))
+               if definition['poisson'] else {})), **settings)
     else:
         backend = distributed_backend(data['x'], data['y'])
         results, sampler, problem, duration = run(data['x'], data['y'], backend=backend, **settings)
