@@ -369,23 +369,23 @@ bool launch_tile_columns(const double *d_y, int ld, int ndata, int nx, const int
 bool launch_copy_rows(const double *d_src, int nx, int ndata, double *d_dst, int ld,
                       bool invert);
 bool launch_pad_model(const double *d_src, int nx, int B, double *d_dst, int ldm);
-// caller-made model curves (mdns_curves.hip): d_curves [B][ldc] against the selected rows of s->d_y at fixed noise,
-// d_out [B][M] = scale * sum_j (c_j - y_j)^2 (one chain per pair, channels ascending); and the curves as the K2 row
-// kernels take templates, [B][ldm] zero padded
-bool launch_curve_rows(const mdns_spectra *s, const double *d_curves, int ldc, int B, double scale,
-                       const int *d_rows, int M, double *d_out);
+// caller-made model curves (mdns_curves.hip): d_curves [B][ldc] against the selected rows of s, d_out [B][M], one chain
+// per pair with the channels ascending.  The statistic:
+//   kCurveNoise    -0.5 sum_j ((c_j - y_j) / noise_level)^2                                       (k_curve_rows)
+//   kCurveChi2     -0.5 sum_j w_j (c_j - y_j)^2 with the per-pixel weights s->d_w, which must be there (k_curve_rows_w)
+//   kCurvePoisson  sum_j (n_j log max(c_j, DBL_MIN) - e_j c_j) + K of a handle in counts mode: s->d_e, s->d_koff must be
+//                  there                                                (k_curve_log into s->d_model, then k_curve_rows_p)
+//   kCurveWstat    the W statistic's -W/2 of a handle with a background (s->d_b, s->d_g, s->d_kw must be there), the
+//                  background rate of every pixel profiled out                                    (k_curve_rows_b)
+//   kCurveMarginal no curve kernel: spectra with variances whose scale is marginalised (launch_curve_pad, then K2)
+// curve_stat: what every curve scoring of a joint state on the handle is (fixed_scale, counts, background: mdns_spectra)
+enum CurveStat { kCurveNoise, kCurveChi2, kCurvePoisson, kCurveWstat, kCurveMarginal };
+CurveStat curve_stat(const mdns_spectra *s);
+bool launch_curve(CurveStat stat, mdns_spectra *s, const double *d_curves, int ldc, int B, double noise_level,
+                  const int *d_rows, int M, double *d_out);
+// the curves as the K2 row kernels take templates, [B][ldm] zero padded
 bool launch_curve_pad(const double *d_curves, int ldc, int nx, int B, double *d_model, int ldm);
-// the same curves against the selected rows of s->d_y with the per-pixel weights s->d_w (which must be there):
-// d_out [B][M] = -0.5 sum_j w_j (c_j - y_j)^2 (k_curve_rows_w: one chain per pair, channels ascending)
-bool launch_curve_rows_w(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
-// the same curves as count rates against the selected rows of a handle in counts mode (s->d_e, s->d_koff must be there):
-// d_out [B][M] = sum_j (n_j log max(c_j, DBL_MIN) - e_j c_j) + K (k_curve_log into s->d_model, then k_curve_rows_p: one
-// chain per pair, channels ascending)
-bool launch_curve_poisson(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
-// the same against a handle with a background (s->d_b, s->d_g, s->d_kw must be there): d_out [B][M] = the W statistic's
-// -W/2, the background rate of every pixel profiled out (k_curve_rows_b: one chain per pair, channels ascending)
-bool launch_curve_wstat(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
-// d_out [B][M][nx] = that profiled rate itself (k_curve_background, the device functions of k_curve_rows_b)
+// d_out [B][M][nx] = the W statistic's profiled rate itself (k_curve_background, the device functions of k_curve_rows_b)
 bool launch_curve_background(const mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out);
 
 // launchers implemented in mdns_neighbors.hip

@@ -569,9 +569,10 @@ static int joint_reset(mdns_joint *j)
 // Poisson likelihood means.  True (and the error set) for such a state; nothing of it has been touched or read.
 static bool curves_only(const mdns_joint *j, const char *who)
 {
-	if (j->kind != 1 || (!j->s->fixed_scale && !j->s->counts)) return false;
+	const CurveStat stat = curve_stat(j->s);
+	if (stat == kCurveNoise || stat == kCurveMarginal) return false;
 	set_error("%s: %s spectra take curve chunks only (mdns_joint_init_curves, mdns_backend_draw_curves)", who,
-	          j->s->counts ? "counts" : "fixed-scale");
+	          stat == kCurveChi2 ? "fixed-scale" : "counts");
 	return true;
 }
 
@@ -618,18 +619,15 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 	return joint_sync(c) ? 0 : 1;
 }
 
-// curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the fixed-noise likelihood from curves
-// (kind 0) or the scale-marginalised one on the curves staged as zero-padded templates (kind 1: exactly what
-// mdns_muse_loglike_batch_dev does with templates), or -- kind 1 on a fixed-scale handle -- the weighted chi^2 at fixed
-// scale (mdns_curve_chi2_batch_dev), or -- kind 1 on a counts handle -- the Poisson likelihood (mdns_curve_poisson_batch_dev)
-// or, where the handle has a background, the W statistic (mdns_curve_wstat_batch_dev)
+// curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the handle's curve statistic (curve_stat: what
+// the mdns_curve_*_batch_dev entry of that statistic computes; kind 0 is the fixed-noise one), or -- kind 1 with the
+// scale marginalised -- the curves staged as zero-padded templates: exactly what mdns_muse_loglike_batch_dev does with
+// templates
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
-	if (j->kind == 0) return launch_curve_rows(s, d_curves, ldc, B, -0.5 / (j->noise_level * j->noise_level), d_rows, M, d_out);
-	if (s->background) return launch_curve_wstat(s, d_curves, ldc, B, d_rows, M, d_out);
-	if (s->counts) return launch_curve_poisson(s, d_curves, ldc, B, d_rows, M, d_out);
-	if (s->fixed_scale) return launch_curve_rows_w(s, d_curves, ldc, B, d_rows, M, d_out);
+	const CurveStat stat = curve_stat(s);
+	if (stat != kCurveMarginal) return launch_curve(stat, s, d_curves, ldc, B, j->noise_level, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
 	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
 	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);

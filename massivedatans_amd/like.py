@@ -95,6 +95,13 @@ class _Spectra(object):
             _lib.check(fn(*args), name)
         return out
 
+    def _curves_batch(self, name, curves, data_mask, *extra):
+        """``curves[B, nx]`` (one curve: ``[nx]``) through the library's batch function ``name`` -> ``L[B, mask.sum()]``."""
+        curves = np.atleast_2d(_lib.as_f64(curves))
+        if curves.shape[1] != self.nx:
+            raise ValueError("curves must be [B, %d]" % self.nx)
+        return self._batch(getattr(self._lib, name), name, curves, data_mask, *extra)
+
 
 class GaussLineSpectra(_Spectra):
     """The toy problem of sample.py: ``ypred = A exp(-0.5 ((mu - x)/sig)^2)``,
@@ -115,11 +122,7 @@ class GaussLineSpectra(_Spectra):
     def loglike_batch_curves(self, curves, data_mask=None):
         """``curves[B, nx]`` model curves the caller made, one per candidate (any model) ->
         ``L[B, mask.sum()]``, ``L = -0.5 sum_j ((curve_j - y_j) / noise_level)^2`` (sample.py:64-71)."""
-        curves = np.atleast_2d(_lib.as_f64(curves))
-        if curves.shape[1] != self.nx:
-            raise ValueError("curves must be [B, %d]" % self.nx)
-        return self._batch(self._lib.mdns_curve_loglike_batch, "mdns_curve_loglike_batch",
-                           curves, data_mask, self.noise_level)
+        return self._curves_batch("mdns_curve_loglike_batch", curves, data_mask, self.noise_level)
 
     def multi_loglikelihood(self, params, data_mask):
         """Same call as sample.py:101-108: ``params = (A, mu, log10 sig)`` after
@@ -164,10 +167,7 @@ class WeightedSpectra(_Spectra):
 
     def loglike_batch_curves(self, curves, data_mask=None):
         """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_chi2_batch)."""
-        curves = np.atleast_2d(_lib.as_f64(curves))
-        if curves.shape[1] != self.nx:
-            raise ValueError("curves must be [B, %d]" % self.nx)
-        return self._batch(self._lib.mdns_curve_chi2_batch, "mdns_curve_chi2_batch", curves, data_mask)
+        return self._curves_batch("mdns_curve_chi2_batch", curves, data_mask)
 
     loglike_batch = loglike_batch_curves
 
@@ -282,12 +282,7 @@ class CountSpectra(_Spectra):
     def loglike_batch_curves(self, curves, data_mask=None):
         """``curves[B, nx]`` -> ``L[B, mask.sum()]`` (mdns_curve_poisson_batch; with a background
         mdns_curve_wstat_batch)."""
-        curves = np.atleast_2d(_lib.as_f64(curves))
-        if curves.shape[1] != self.nx:
-            raise ValueError("curves must be [B, %d]" % self.nx)
-        if self.has_background:
-            return self._batch(self._lib.mdns_curve_wstat_batch, "mdns_curve_wstat_batch", curves, data_mask)
-        return self._batch(self._lib.mdns_curve_poisson_batch, "mdns_curve_poisson_batch", curves, data_mask)
+        return self._curves_batch("mdns_curve_wstat_batch" if self.has_background else "mdns_curve_poisson_batch", curves, data_mask)
 
     def background_fit(self, curves, data_mask=None):
         """``curves[B, nx]`` -> ``f[B, M, nx]``: the background rate the W statistic fitted to every pixel of every pair,

@@ -10,57 +10,19 @@ import pytest
 from massivedatans_amd import _lib, jointstate, problem, sample
 from massivedatans_amd.like import GaussLineSpectra, MuseSpectra, WeightedSpectra
 from chi2_support import DeviceScorer, NumpyWeightedChi2, chain, rel_bound, weighted_data
-from curves_support import gauss_prior, line_model
+from curves_support import (STAGE_EDGE_BS, STAGE_EDGE_CASES, STAGE_EDGE_NDATA, STAGE_EDGE_NX, Chunks, StatementProblem, dev_batch,
+                            gauss_prior, line_model, refused, selections)
 from filter_support import _drive
-from test_curves import _Chunks, _StatementProblem
 
 pytestmark = pytest.mark.gpu
 
-NX = (1, 2, 31, 32, 33, 63, 64, 65, 200, 513)
-NDATA = (1, 63, 64, 65, 127, 128, 129, 300)
-BS = (1, 7, 8, 9, 31, 32, 33, 70)
-# 30 cases: every nx three times, every ndata and every B at least three times, paired (no product)
-CASES = [(NX[i % 10], NDATA[(3 * i + i // 8) % 8], BS[(5 * i + 2 * (i // 8)) % 8]) for i in range(30)]
+NX, NDATA, BS = STAGE_EDGE_NX, STAGE_EDGE_NDATA, STAGE_EDGE_BS
+CASES = STAGE_EDGE_CASES
 
 
 def test_the_cases_cover_every_size():
     assert {c[0] for c in CASES} == set(NX) and {c[1] for c in CASES} == set(NDATA) and {c[2] for c in CASES} == set(BS)
     assert len(set(CASES)) == 30
-
-
-def _dev_batch(lib, spectra, curves, pad, rows):
-    """mdns_curve_chi2_batch_dev on rows of nx + pad doubles (NaN behind the curves)."""
-    B, nx = curves.shape
-    ldc = nx + pad
-    wide = np.full((B, ldc), np.nan)
-    wide[:, :nx] = curves
-    M = spectra.ndata if rows is None else len(rows)
-    out = np.empty((B, M))
-    d_c, d_o = lib.mdns_dev_alloc(wide.nbytes), lib.mdns_dev_alloc(out.nbytes)
-    d_r = None
-    try:
-        assert d_c and d_o
-        _lib.check(lib.mdns_h2d(d_c, _lib.ptr(wide), wide.nbytes), "h2d")
-        if rows is not None:
-            r32 = np.ascontiguousarray(rows, dtype=np.int32)
-            d_r = lib.mdns_dev_alloc(r32.nbytes)
-            _lib.check(lib.mdns_h2d(d_r, _lib.ptr(r32), r32.nbytes), "h2d")
-        _lib.check(lib.mdns_curve_chi2_batch_dev(spectra.handle, d_c, ldc, B, d_r, M, d_o), "mdns_curve_chi2_batch_dev")
-        _lib.check(lib.mdns_d2h(_lib.ptr(out), d_o, out.nbytes), "d2h")
-    finally:
-        for p in (d_c, d_o, d_r):
-            if p:
-                lib.mdns_dev_free(p)
-    return out
-
-
-def _selections(ndata, rng):
-    sel = [("all", None), ("one", np.array([ndata // 3]))]
-    if ndata >= 3:
-        sel.append(("third", np.arange(rng.randint(0, 3), ndata, 3)))
-    if ndata > 1:
-        sel.append(("ragged", np.sort(rng.choice(ndata, size=ndata - 1, replace=False))))      # 127 of 128, 128 of 129 ...
-    return sel
 
 
 @pytest.mark.parametrize("nx,ndata,B", CASES)
@@ -78,7 +40,7 @@ def test_kernel_against_the_statement(nx, ndata, B, hip):
     curves = rng.uniform(-0.1, 0.3, size=(B, nx))
     want = st.loglike_batch_long(curves)
     worst = 0.0
-    for name, rows in _selections(ndata, rng):
+    for name, rows in selections(ndata, rng):
         ref = want if rows is None else want[:, rows]
         got = spectra.loglike_batch_curves(curves, rows)
         assert got.shape == ref.shape
@@ -87,7 +49,7 @@ def test_kernel_against_the_statement(nx, ndata, B, hip):
         err = np.abs(got.astype(np.longdouble) - ref)[~zero] / np.abs(ref[~zero])
         worst = max(worst, float(err.max()) if err.size else 0.0)
         assert (err <= rel_bound(nx)).all(), (name, float(err.max()), rel_bound(nx))
-        assert np.array_equal(_dev_batch(hip, spectra, curves, 3, rows), got), name
+        assert np.array_equal(dev_batch(hip, spectra, curves, 3, rows, "mdns_curve_chi2_batch_dev"), got), name
         assert np.array_equal(spectra.loglike_batch(curves, rows), got), name
     print("nx=%d ndata=%d B=%d masked=%s: max rel err %.3g (bound %.3g)" % (nx, ndata, B, masked, worst, rel_bound(nx)))
     whole = spectra.loglike_batch_curves(curves)
@@ -113,7 +75,7 @@ def test_a_pair_has_one_value(hip):
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm], sel), whole[perm][:, sel])
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm[:5]], sel[3:4]), whole[perm[:5]][:, sel[3:4]])
     for pad in (0, 1, 56):
-        assert np.array_equal(_dev_batch(hip, spectra, curves[perm], pad, sel), whole[perm][:, sel]), pad
+        assert np.array_equal(dev_batch(hip, spectra, curves[perm], pad, sel, "mdns_curve_chi2_batch_dev"), whole[perm][:, sel]), pad
     nlive = 40
     js = jointstate.CurveJointState(spectra, nlive, lambda xs: curves[xs[:, 0].astype(int)])
     js.init(np.arange(20, 20 + nlive, dtype=float)[:, None])
@@ -191,7 +153,7 @@ def test_joint_state_equals_its_numpy_statement(ndata, nlive, nx, noisy):
     assert dev.nparams == 3 and np.array_equal(dev.live_matrix(), host.live_matrix())
     want = NumpyWeightedChi2(d["y"], d["v"]).loglike_batch_long(model(xs0)).astype(float) + (noise0 if noisy else 0)
     assert np.allclose(dev.live_matrix(), want, rtol=1e-12, atol=0)
-    assert _drive(_Chunks(dev, lambda xs: xs, noisy), _Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
+    assert _drive(Chunks(dev, lambda xs: xs, noisy), Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
     dev.close()
     spectra.close()
 
@@ -202,7 +164,7 @@ def test_whole_run_equals_the_statement(use_graph):
     x, y, v = d["x"][96:160], np.ascontiguousarray(d["y"][96:160]), np.ascontiguousarray(d["v"][96:160])
     model = line_model(x)
     runs = []
-    for cls in (problem.CurveProblem, _StatementProblem):
+    for cls in (problem.CurveProblem, StatementProblem):
         p = cls(x, y, model, gauss_prior, 3, v=v, marginalise_scale=False)
         assert isinstance(p.backend, WeightedSpectra)
         with np.errstate(all="ignore"):
@@ -215,19 +177,14 @@ def test_whole_run_equals_the_statement(use_graph):
         assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
-def _refused(rc, *words):
-    msg = _lib.last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
 def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     d = weighted_data(20, 64, seed=10)
     plain = GaussLineSpectra(d["x"], d["y"], noise_level=0.01)
-    _refused(hip.mdns_spectra_set_fixed_scale(plain.handle, 1), "mdns_spectra_set_fixed_scale", "without variances")
+    refused(hip.mdns_spectra_set_fixed_scale(plain.handle, 1), "mdns_spectra_set_fixed_scale", "without variances")
     assert hip.mdns_spectra_fixed_scale(plain.handle) == 0 and hip.mdns_spectra_fixed_scale(None) == -1
     curves = np.zeros((2, 64))
     out = np.zeros((2, 20))
-    _refused(hip.mdns_curve_chi2_batch(plain.handle, _lib.ptr(curves), 2, None, 20, _lib.ptr(out)), "spectra were created without variances")
+    refused(hip.mdns_curve_chi2_batch(plain.handle, _lib.ptr(curves), 2, None, 20, _lib.ptr(out)), "spectra were created without variances")
     plain.close()
     # a handle in either mode scores the same through the pure batch call
     muse = MuseSpectra(d["x"], d["y"], d["v"])
@@ -243,24 +200,24 @@ def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     assert np.array_equal(marg, muse.loglike_batch(curves))
     # a continuum excludes the mode, and the mode a continuum
     assert hip.mdns_spectra_set_continuum(muse.handle, 2) == 0
-    _refused(hip.mdns_spectra_set_fixed_scale(muse.handle, 1), "mdns_spectra_set_fixed_scale", "continuum")
+    refused(hip.mdns_spectra_set_fixed_scale(muse.handle, 1), "mdns_spectra_set_fixed_scale", "continuum")
     assert hip.mdns_spectra_fixed_scale(muse.handle) == 0 and hip.mdns_spectra_continuum(muse.handle) == 2
     assert hip.mdns_spectra_set_continuum(muse.handle, 0) == 0
-    _refused(hip.mdns_spectra_set_continuum(weighted.handle, 2), "mdns_spectra_set_continuum", "fixed-scale")
+    refused(hip.mdns_spectra_set_continuum(weighted.handle, 2), "mdns_spectra_set_continuum", "fixed-scale")
     assert hip.mdns_spectra_continuum(weighted.handle) == 0 and hip.mdns_spectra_fixed_scale(weighted.handle) == 1
     # fixed while a joint state lives on the handle, in both directions
     for sp, now in ((muse, 0), (weighted, 1)):
         js = jointstate.CurveJointState(sp, 8, line_model(d["x"]))
-        _refused(hip.mdns_spectra_set_fixed_scale(sp.handle, 1 - now), "mdns_spectra_set_fixed_scale", "a joint state exists")
+        refused(hip.mdns_spectra_set_fixed_scale(sp.handle, 1 - now), "mdns_spectra_set_fixed_scale", "a joint state exists")
         assert hip.mdns_spectra_fixed_scale(sp.handle) == now
         js.close()
     assert hip.mdns_spectra_set_fixed_scale(muse.handle, 1) == 0 and hip.mdns_spectra_fixed_scale(muse.handle) == 1
     assert hip.mdns_spectra_set_fixed_scale(muse.handle, 0) == 0 and hip.mdns_spectra_fixed_scale(muse.handle) == 0
     # sizes
-    _refused(hip.mdns_curve_chi2_batch(weighted.handle, _lib.ptr(curves), 5, None, 21, _lib.ptr(got)), "mdns_curve_chi2_batch", "M=21")
+    refused(hip.mdns_curve_chi2_batch(weighted.handle, _lib.ptr(curves), 5, None, 21, _lib.ptr(got)), "mdns_curve_chi2_batch", "M=21")
     d_c = hip.mdns_dev_alloc(curves.nbytes)
     d_o = hip.mdns_dev_alloc(got.nbytes)
-    _refused(hip.mdns_curve_chi2_batch_dev(weighted.handle, d_c, 63, 5, None, 20, d_o), "mdns_curve_chi2_batch_dev", "ldc=63", "nx=64")
+    refused(hip.mdns_curve_chi2_batch_dev(weighted.handle, d_c, 63, 5, None, 20, d_o), "mdns_curve_chi2_batch_dev", "ldc=63", "nx=64")
     assert hip.mdns_curve_chi2_batch_dev(weighted.handle, d_c, 64, 0, None, 20, d_o) == 0
     assert hip.mdns_curve_chi2_batch_dev(weighted.handle, d_c, 64, 5, None, 0, d_o) == 0
     hip.mdns_dev_free(d_c)
@@ -278,7 +235,7 @@ def test_a_fixed_scale_state_takes_curve_chunks_only(hip):
     host = jointstate.HostJointState(DeviceScorer(spectra), nlive, ndata, model)
     rng = np.random.RandomState(3)
     rows5 = np.ones((nlive, 5))
-    _refused(hip.mdns_joint_init_muse3(dev._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", "curve chunks only")
+    refused(hip.mdns_joint_init_muse3(dev._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", "curve chunks only")
     xs0 = gauss_prior(rng.uniform(size=(nlive, 3)))
     dev.init(xs0)
     host.init(xs0)
@@ -287,15 +244,15 @@ def test_a_fixed_scale_state_takes_curve_chunks_only(hip):
     accepted, nscored, npairs = C.c_int(7), C.c_int(0), C.c_int(0)
     bits = np.zeros(1, dtype=np.uint64)
     assert hip.mdns_backend_draw_begin(dev._h, None, ndata) == 0
-    _refused(hip.mdns_backend_draw_chunk(dev._h, _lib.ptr(rows5), 4, None, C.addressof(accepted), _lib.ptr(bits), C.addressof(nscored)),
+    refused(hip.mdns_backend_draw_chunk(dev._h, _lib.ptr(rows5), 4, None, C.addressof(accepted), _lib.ptr(bits), C.addressof(nscored)),
              "mdns_backend_draw_chunk", "curve chunks only")
     assert accepted.value == -1
-    _refused(hip.mdns_backend_draw_score(dev._h, _lib.ptr(rows5), 4, None), "mdns_backend_draw_score", "curve chunks only")
+    refused(hip.mdns_backend_draw_score(dev._h, _lib.ptr(rows5), 4, None), "mdns_backend_draw_score", "curve chunks only")
     bound = np.zeros(4)
     status, pb, pk = (np.zeros(64, dtype=np.int32) for _ in range(3))
     pL, pt = np.zeros(64), np.zeros(64)
-    _refused(hip.mdns_backend_draw_band_begin(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound)), "mdns_backend_draw_band", "curve chunks only")
-    _refused(hip.mdns_backend_draw_band(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound), _lib.ptr(status), C.addressof(npairs), _lib.ptr(pb),
+    refused(hip.mdns_backend_draw_band_begin(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound)), "mdns_backend_draw_band", "curve chunks only")
+    refused(hip.mdns_backend_draw_band(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound), _lib.ptr(status), C.addressof(npairs), _lib.ptr(pb),
                                         _lib.ptr(pk), _lib.ptr(pL), _lib.ptr(pt), 64), "mdns_backend_draw_band", "curve chunks only")
     # ... and the state goes on as if nothing had happened: curve chunks decide as the statement does
     for attempt in range(6):

@@ -13,7 +13,9 @@ import pytest
 
 from massivedatans_amd import _lib, gen, jointstate, problem, sample
 from massivedatans_amd.like import GaussLineSpectra, MuseSpectra
-from curves_support import gauss_prior, line_model, muse_cut
+from chi2_support import _fma
+from curves_support import (STAGE_EDGE_CASES, Chunks, StatementProblem, dev_batch, gauss_prior, line_model, muse_cut, selections,
+                            selections_by_size)
 from test_joint import _drive
 
 pytestmark = pytest.mark.gpu
@@ -42,42 +44,6 @@ class CurveScorer(object):
         return self.spectra.loglike_batch_curves(curves, data_mask)
 
 
-def _selections(ndata, rng):
-    sel = [("all", None), ("one", np.array([ndata // 2]))]
-    for n in (63, 64, 65):
-        if ndata > n:
-            sel.append((str(n), np.sort(rng.choice(ndata, size=n, replace=False))))
-    if ndata >= 3:
-        sel.append(("third", np.arange(rng.randint(0, 3), ndata, 3)))
-    return sel
-
-
-def _dev_batch(lib, spectra, curves, pad, rows):
-    """mdns_curve_loglike_batch_dev on rows of nx + pad doubles."""
-    B, nx = curves.shape
-    ldc = nx + pad
-    wide = np.full((B, ldc), np.nan)
-    wide[:, :nx] = curves
-    M = spectra.ndata if rows is None else len(rows)
-    out = np.empty((B, M))
-    d_c, d_o = lib.mdns_dev_alloc(wide.nbytes), lib.mdns_dev_alloc(out.nbytes)
-    d_r = None
-    try:
-        assert d_c and d_o
-        _lib.check(lib.mdns_h2d(d_c, _lib.ptr(wide), wide.nbytes), "h2d")
-        if rows is not None:
-            r32 = np.ascontiguousarray(rows, dtype=np.int32)
-            d_r = lib.mdns_dev_alloc(r32.nbytes)
-            _lib.check(lib.mdns_h2d(d_r, _lib.ptr(r32), r32.nbytes), "h2d")
-        _lib.check(lib.mdns_curve_loglike_batch_dev(spectra.handle, d_c, ldc, B, NOISE, d_r, M, d_o), "mdns_curve_loglike_batch_dev")
-        _lib.check(lib.mdns_d2h(_lib.ptr(out), d_o, out.nbytes), "d2h")
-    finally:
-        for p in (d_c, d_o, d_r):
-            if p:
-                lib.mdns_dev_free(p)
-    return out
-
-
 # every nx of {1, 7, 33, 64, 200, 201, 513}, every B of {1, 3, 17, 64, 257, 1024}, every ndata of {1, 7, 100, 1000}
 @pytest.mark.parametrize("nx,B,ndata", [(1, 1, 1), (7, 3, 7), (33, 17, 100), (64, 64, 1000), (200, 257, 100), (201, 1024, 7),
                                         (513, 64, 100), (200, 3, 1000)])
@@ -88,7 +54,7 @@ def test_kernel_against_the_numpy_statement(nx, B, ndata, hip):
     curves = rng.uniform(-0.1, 0.3, size=(B, nx))
     spectra = GaussLineSpectra(x, y, noise_level=NOISE)
     want = _statement(curves, y)
-    for name, rows in _selections(ndata, rng):
+    for name, rows in selections_by_size(ndata, rng):
         ref = want if rows is None else want[:, rows]
         got = spectra.loglike_batch_curves(curves, rows)
         assert got.shape == ref.shape
@@ -96,7 +62,38 @@ def test_kernel_against_the_numpy_statement(nx, B, ndata, hip):
         print("nx=%d B=%d ndata=%d %s: max rel err %.3g" % (nx, B, ndata, name, err))
         assert err < RTOL_L, (name, err)
         # rows longer than the curves, device pointers: the same bits
-        assert np.array_equal(_dev_batch(hip, spectra, curves, 3, rows), got), name
+        assert np.array_equal(dev_batch(hip, spectra, curves, 3, rows, "mdns_curve_loglike_batch_dev", (NOISE,)), got), name
+    spectra.close()
+
+
+def _chain(curve, y, noise=NOISE):
+    """The kernel's chain for one pair in float64, operation by operation: d = c - y, acc = fma(d, d, acc) from +0 with
+    the channels ascending, L = acc * scale with scale = -0.5 / (noise * noise)."""
+    acc = 0.0
+    for c, yy in zip(np.asarray(curve, dtype=float).tolist(), np.asarray(y, dtype=float).tolist()):
+        d = c - yy
+        acc = _fma(d, d, acc)
+    return acc * (-0.5 / (noise * noise))
+
+
+@pytest.mark.parametrize("nx,ndata,B", STAGE_EDGE_CASES)
+def test_kernel_against_the_emulated_chain(nx, ndata, B):
+    """mdns_curve_loglike_batch bit for bit with the chain of the file header, at the first, the last and the middle pair
+    of the whole batch and of a ragged selection, over nx across the 32-channel stage edges, ndata across the tile's 64
+    and 128 spectra and B across a wave's 8 and the tile's 32 candidates."""
+    rng = np.random.RandomState(nx * 1000 + B)
+    y = rng.normal(0, 0.05, size=(nx, ndata))
+    curves = rng.uniform(-0.1, 0.3, size=(B, nx))
+    spectra = GaussLineSpectra(np.linspace(400, 800, nx), y, noise_level=NOISE)
+    for name, rows in selections(ndata, rng):
+        if name not in ("all", "ragged"):
+            continue
+        got = spectra.loglike_batch_curves(curves, rows)
+        ks = np.arange(ndata) if rows is None else rows
+        M = len(ks)
+        assert got.shape == (B, M)
+        for b, m in {(0, 0), (B - 1, M - 1), (B // 2, M // 2)}:
+            assert got[b, m] == _chain(curves[b], y[:, ks[m]]), (name, b, m)
     spectra.close()
 
 
@@ -189,28 +186,6 @@ class SameShapeScorer(object):
         return self.spectra.loglike_batch(curves, data_mask)
 
 
-class _Chunks(object):
-    """A joint state whose ``draw`` takes model parameters, goes through ``draw_params`` and -- ``noisy`` -- adds
-    a noise block [B, M], the same one for the same call number."""
-
-    def __init__(self, state, to_params, noisy, scorer=None):
-        self.__dict__.update(_s=state, _p=to_params, _noisy=noisy, _scorer=scorer, _calls=0)
-
-    def __getattr__(self, name):
-        return getattr(self._s, name)
-
-    def draw(self, xs, rows):
-        self.__dict__["_calls"] += 1
-        M = self._s.ndata if rows is None else len(rows)
-        noise = np.random.RandomState(self._calls).normal(0, 1e-5, size=(len(xs), M)) if self._noisy else None
-        params = self._p(xs)
-        if self._scorer is not None:
-            mask = np.zeros(self._s.ndata, dtype=bool)
-            mask[np.arange(self._s.ndata) if rows is None else rows] = True
-            self._scorer.begin(params, mask)
-        return self._s.draw_params(params, rows, jitter=noise)
-
-
 @pytest.mark.parametrize("noisy", [False, True])
 def test_scale_marginalised_joint_state_equals_its_numpy_statement(noisy):
     ndata, nlive, nx = 60, 12, 96
@@ -234,7 +209,7 @@ def test_scale_marginalised_joint_state_equals_its_numpy_statement(noisy):
     dev.init(xs0, jitter=noise0)
     host.init(xs0, jitter=noise0)
     assert np.array_equal(dev.live_matrix(), host.live_matrix())
-    assert _drive(_Chunks(dev, lambda xs: xs, noisy), _Chunks(host, model, noisy, scorer), ndata, rng, iterations=8, exact=True) > 0
+    assert _drive(Chunks(dev, lambda xs: xs, noisy), Chunks(host, model, noisy, scorer), ndata, rng, iterations=8, exact=True) > 0
     dev.close()
     spectra.close()
 
@@ -372,20 +347,13 @@ def test_a_device_tensor_is_read_where_it_lies(tmp_path):
     assert out.returncode == 0 and "TENSOR OK" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
 
 
-class _StatementProblem(problem.CurveProblem):
-    """The same problem with the numpy statement of the joint state over the device's curve kernel."""
-
-    def _on_device(self):
-        return False
-
-
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_whole_run_equals_the_statement(use_graph):
     d = gen.horns(40)
     x, y = d["x"][96:160], np.ascontiguousarray(d["y"][96:160])
     model = line_model(x)
     runs = []
-    for cls in (problem.CurveProblem, _StatementProblem):
+    for cls in (problem.CurveProblem, StatementProblem):
         p = cls(x, y, model, gauss_prior, 3, noise_level=NOISE)
         with np.errstate(all="ignore"):
             results, sampler, _, _ = sample.run_model(p, nlive_points=30, max_samples=60, use_graph=use_graph, seed=1)

@@ -10,10 +10,9 @@ import pytest
 
 from massivedatans_amd import _lib, jointstate, problem, sample
 from massivedatans_amd.like import CountSpectra, GaussLineSpectra, MuseSpectra, _Spectra
-from curves_support import gauss_prior, line_model
+from curves_support import Chunks, StatementProblem, dev_batch, gauss_prior, line_model, refused, selections
 from filter_support import _drive
 from poisson_support import LOG_ULPS, TINY, DeviceScorer, NumpyPoisson, chain, count_data, count_model, within_bound
-from test_curves import _Chunks, _StatementProblem
 
 pytestmark = pytest.mark.gpu
 
@@ -41,32 +40,6 @@ def _curves(B, nx, seed):
     curves[rng.uniform(size=curves.shape) < 0.02] = 0.0
     curves[rng.uniform(size=curves.shape) < 0.01] = -0.0
     return curves
-
-
-def _dev_batch(lib, spectra, curves, pad, rows):
-    """mdns_curve_poisson_batch_dev on rows of nx + pad doubles (NaN behind the curves)."""
-    B, nx = curves.shape
-    ldc = nx + pad
-    wide = np.full((B, ldc), np.nan)
-    wide[:, :nx] = curves
-    M = spectra.ndata if rows is None else len(rows)
-    out = np.empty((B, M))
-    d_c, d_o = lib.mdns_dev_alloc(wide.nbytes), lib.mdns_dev_alloc(out.nbytes)
-    d_r = None
-    try:
-        assert d_c and d_o
-        _lib.check(lib.mdns_h2d(d_c, _lib.ptr(wide), wide.nbytes), "h2d")
-        if rows is not None:
-            r32 = np.ascontiguousarray(rows, dtype=np.int32)
-            d_r = lib.mdns_dev_alloc(r32.nbytes)
-            _lib.check(lib.mdns_h2d(d_r, _lib.ptr(r32), r32.nbytes), "h2d")
-        _lib.check(lib.mdns_curve_poisson_batch_dev(spectra.handle, d_c, ldc, B, d_r, M, d_o), "mdns_curve_poisson_batch_dev")
-        _lib.check(lib.mdns_d2h(_lib.ptr(out), d_o, out.nbytes), "d2h")
-    finally:
-        for p in (d_c, d_o, d_r):
-            if p:
-                lib.mdns_dev_free(p)
-    return out
 
 
 class _RawCounts(_Spectra):
@@ -97,18 +70,6 @@ def device_log(curves):
     return lc
 
 
-def _selections(ndata, rng):
-    sel = [("all", None), ("one", np.array([ndata // 3]))]
-    if ndata >= 3:
-        sel.append(("third", np.arange(rng.randint(0, 3), ndata, 3)))
-    if ndata > 1:
-        sel.append(("ragged", np.sort(rng.choice(ndata, size=ndata - 1, replace=False))))
-    for m in MS:
-        if ndata > m + 1:
-            sel.append(("sparse %d" % m, np.sort(rng.choice(ndata, size=m, replace=False))))
-    return sel
-
-
 @pytest.mark.parametrize("nx,ndata,B,exposure", CASES)
 def test_kernel_against_the_statement(nx, ndata, B, exposure, hip):
     """Every L within ``bound`` of the longdouble statement (poisson_support derives it), over the whole set and over
@@ -122,13 +83,13 @@ def test_kernel_against_the_statement(nx, ndata, B, exposure, hip):
     curves = _curves(B, nx, nx + B)
     want = (st.loglike_batch_long(curves),) + st.sums_long(curves)        # once, for every selection
     worst = 0.0
-    for name, rows in _selections(ndata, rng):
+    for name, rows in selections(ndata, rng, MS):
         got = spectra.loglike_batch_curves(curves, rows)
         assert got.shape == (B, ndata if rows is None else len(rows))
         ok, frac = within_bound(got, st, nx, curves, rows, want)
         worst = max(worst, frac)
         assert ok, (name, frac)
-        assert np.array_equal(_dev_batch(hip, spectra, curves, 3, rows), got), name
+        assert np.array_equal(dev_batch(hip, spectra, curves, 3, rows, "mdns_curve_poisson_batch_dev"), got), name
         assert np.array_equal(spectra.loglike_batch(curves, rows), got), name
     lc = device_log(curves)
     exact = np.log(np.fmax(np.abs(curves), TINY).astype(np.longdouble))
@@ -159,7 +120,7 @@ def test_a_pair_has_one_value(hip):
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm], sel), whole[perm][:, sel])
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm[:5]], sel[3:4]), whole[perm[:5]][:, sel[3:4]])
     for pad in (0, 1, 56):
-        assert np.array_equal(_dev_batch(hip, spectra, curves[perm], pad, sel), whole[perm][:, sel]), pad
+        assert np.array_equal(dev_batch(hip, spectra, curves[perm], pad, sel, "mdns_curve_poisson_batch_dev"), whole[perm][:, sel]), pad
     nlive = 40
     js = jointstate.CurveJointState(spectra, nlive, lambda xs: curves[xs[:, 0].astype(int)])
     js.init(np.arange(20, 20 + nlive, dtype=float)[:, None])
@@ -282,7 +243,7 @@ def test_joint_state_equals_its_numpy_statement(ndata, nlive, nx, noisy):
     assert dev.nparams == 3 and np.array_equal(dev.live_matrix(), host.live_matrix())
     want = NumpyPoisson(d["y"], d["e"]).loglike_batch_long(model(xs0)).astype(float) + (noise0 if noisy else 0)
     assert np.allclose(dev.live_matrix(), want, rtol=1e-11, atol=1e-9)
-    assert _drive(_Chunks(dev, lambda xs: xs, noisy), _Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
+    assert _drive(Chunks(dev, lambda xs: xs, noisy), Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
     dev.close()
     spectra.close()
 
@@ -292,7 +253,7 @@ def test_whole_run_equals_the_statement():
     x, y, e = d["x"], d["y"], d["e"]
     model = count_model(x)
     runs = []
-    for cls in (problem.CurveProblem, _StatementProblem):
+    for cls in (problem.CurveProblem, StatementProblem):
         p = cls(x, y, model, gauss_prior, 3, poisson=True, exposure=e)
         assert isinstance(p.backend, CountSpectra)
         with np.errstate(all="ignore"):
@@ -305,11 +266,6 @@ def test_whole_run_equals_the_statement():
         assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
-def _refused(rc, *words):
-    msg = _lib.last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
 def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     nx, ndata = 64, 20
     d = count_data(ndata, nx, seed=10, edges=False)
@@ -318,12 +274,12 @@ def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     curves = _curves(5, nx, 10)
     got = np.empty((5, ndata))
     assert hip.mdns_spectra_counts(None) == -1
-    _refused(hip.mdns_spectra_set_counts(None, None, None), "mdns_spectra_set_counts", "null")
+    refused(hip.mdns_spectra_set_counts(None, None, None), "mdns_spectra_set_counts", "null")
     # a handle created with variances
     muse = MuseSpectra(d["x"], st.y, np.ones_like(st.y))
-    _refused(hip.mdns_spectra_set_counts(muse.handle, _lib.ptr(rows), None), "mdns_spectra_set_counts", "with variances")
+    refused(hip.mdns_spectra_set_counts(muse.handle, _lib.ptr(rows), None), "mdns_spectra_set_counts", "with variances")
     assert hip.mdns_spectra_counts(muse.handle) == 0
-    _refused(hip.mdns_curve_poisson_batch(muse.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)),
+    refused(hip.mdns_curve_poisson_batch(muse.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)),
              "mdns_curve_poisson_batch", "spectra are not in counts mode (mdns_spectra_set_counts)")
     muse.close()
     # a bad exposure is found in the host array, named, and nothing is uploaded: the handle scores as before
@@ -332,23 +288,23 @@ def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     for bad in (-1.0, np.nan, np.inf):
         wrong = rows.copy()
         wrong[7, 5] = bad
-        _refused(hip.mdns_spectra_set_counts(plain.handle, _lib.ptr(wrong), None), "mdns_spectra_set_counts", "exposure[7][5]")
+        refused(hip.mdns_spectra_set_counts(plain.handle, _lib.ptr(wrong), None), "mdns_spectra_set_counts", "exposure[7][5]")
         assert hip.mdns_spectra_counts(plain.handle) == 0
-    _refused(hip.mdns_curve_poisson_batch(plain.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)), "not in counts mode")
+    refused(hip.mdns_curve_poisson_batch(plain.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)), "not in counts mode")
     d_c, d_o = hip.mdns_dev_alloc(curves.nbytes), hip.mdns_dev_alloc(got.nbytes)
-    _refused(hip.mdns_curve_poisson_batch_dev(plain.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "not in counts mode")
+    refused(hip.mdns_curve_poisson_batch_dev(plain.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "not in counts mode")
     assert np.array_equal(plain.loglike_batch_curves(curves), before)
     # once a joint state exists on the handle
     js = jointstate.CurveJointState(plain, 8, line_model(d["x"]))
-    _refused(hip.mdns_spectra_set_counts(plain.handle, _lib.ptr(rows), None), "mdns_spectra_set_counts", "a joint state exists")
+    refused(hip.mdns_spectra_set_counts(plain.handle, _lib.ptr(rows), None), "mdns_spectra_set_counts", "a joint state exists")
     assert hip.mdns_spectra_counts(plain.handle) == 0
     js.close()
     assert np.array_equal(plain.loglike_batch_curves(curves), before)
     # now it goes through; the other setters refuse as on any handle without variances, and the mode stays
     K = np.ascontiguousarray(st.K)
     assert hip.mdns_spectra_set_counts(plain.handle, _lib.ptr(rows), _lib.ptr(K)) == 0 and hip.mdns_spectra_counts(plain.handle) == 1
-    _refused(hip.mdns_spectra_set_fixed_scale(plain.handle, 1), "mdns_spectra_set_fixed_scale", "without variances")
-    _refused(hip.mdns_spectra_set_continuum(plain.handle, 2), "mdns_spectra_set_continuum", "variances")
+    refused(hip.mdns_spectra_set_fixed_scale(plain.handle, 1), "mdns_spectra_set_fixed_scale", "without variances")
+    refused(hip.mdns_spectra_set_continuum(plain.handle, 2), "mdns_spectra_set_continuum", "variances")
     assert hip.mdns_spectra_counts(plain.handle) == 1 and hip.mdns_spectra_fixed_scale(plain.handle) == 0
     assert hip.mdns_curve_poisson_batch(plain.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)) == 0
     counts = CountSpectra(d["x"], d["y"], d["e"])
@@ -356,12 +312,12 @@ def test_the_mode_is_set_only_where_it_has_a_meaning(hip):
     # the Gaussian batch functions keep computing what their names say (the y on the handle: st.y, masked already)
     assert np.array_equal(plain.loglike_batch_curves(curves), before)
     js = jointstate.CurveJointState(counts, 8, count_model(d["x"]))
-    _refused(hip.mdns_spectra_set_counts(counts.handle, None, None), "mdns_spectra_set_counts", "a joint state exists")
+    refused(hip.mdns_spectra_set_counts(counts.handle, None, None), "mdns_spectra_set_counts", "a joint state exists")
     js.close()
     # sizes, as mdns_curve_chi2_batch[_dev]
-    _refused(hip.mdns_curve_poisson_batch(counts.handle, _lib.ptr(curves), 5, None, ndata + 1, _lib.ptr(got)), "mdns_curve_poisson_batch", "M=%d" % (ndata + 1))
-    _refused(hip.mdns_curve_poisson_batch_dev(counts.handle, d_c, nx - 1, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "ldc=%d" % (nx - 1), "nx=%d" % nx)
-    _refused(hip.mdns_curve_poisson_batch_dev(counts.handle, None, nx, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "null argument")
+    refused(hip.mdns_curve_poisson_batch(counts.handle, _lib.ptr(curves), 5, None, ndata + 1, _lib.ptr(got)), "mdns_curve_poisson_batch", "M=%d" % (ndata + 1))
+    refused(hip.mdns_curve_poisson_batch_dev(counts.handle, d_c, nx - 1, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "ldc=%d" % (nx - 1), "nx=%d" % nx)
+    refused(hip.mdns_curve_poisson_batch_dev(counts.handle, None, nx, 5, None, ndata, d_o), "mdns_curve_poisson_batch_dev", "null argument")
     assert hip.mdns_curve_poisson_batch_dev(counts.handle, d_c, nx, 0, None, ndata, d_o) == 0
     assert hip.mdns_curve_poisson_batch_dev(counts.handle, d_c, nx, 5, None, 0, d_o) == 0
     assert np.array_equal(got, counts.loglike_batch_curves(curves))
@@ -384,8 +340,8 @@ def test_a_counts_state_takes_curve_chunks_only(hip):
     rng = np.random.RandomState(3)
     rows5 = np.ones((nlive, 5))
     only = "counts spectra take curve chunks only"
-    _refused(hip.mdns_joint_init_muse3(dev._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", only)
-    _refused(hip.mdns_joint_init_gauss(dev._h, _lib.ptr(rows5), 1.0), "mdns_joint_init_gauss", only)
+    refused(hip.mdns_joint_init_muse3(dev._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", only)
+    refused(hip.mdns_joint_init_gauss(dev._h, _lib.ptr(rows5), 1.0), "mdns_joint_init_gauss", only)
     xs0 = gauss_prior(rng.uniform(size=(nlive, 3)))
     dev.init(xs0)
     host.init(xs0)
@@ -394,18 +350,18 @@ def test_a_counts_state_takes_curve_chunks_only(hip):
     accepted, nscored, npairs = C.c_int(7), C.c_int(0), C.c_int(0)
     bits = np.zeros(1, dtype=np.uint64)
     assert hip.mdns_backend_draw_begin(dev._h, None, ndata) == 0
-    _refused(hip.mdns_backend_draw_chunk(dev._h, _lib.ptr(rows5), 4, None, C.addressof(accepted), _lib.ptr(bits), C.addressof(nscored)),
+    refused(hip.mdns_backend_draw_chunk(dev._h, _lib.ptr(rows5), 4, None, C.addressof(accepted), _lib.ptr(bits), C.addressof(nscored)),
              "mdns_backend_draw_chunk", only)
     assert accepted.value == -1
-    _refused(hip.mdns_backend_draw_score(dev._h, _lib.ptr(rows5), 4, None), "mdns_backend_draw_score", only)
+    refused(hip.mdns_backend_draw_score(dev._h, _lib.ptr(rows5), 4, None), "mdns_backend_draw_score", only)
     bound = np.zeros(4)
     status, pb, pk = (np.zeros(64, dtype=np.int32) for _ in range(3))
     pL, pt = np.zeros(64), np.zeros(64)
-    _refused(hip.mdns_backend_draw_band_begin(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound)), "mdns_backend_draw_band", only)
-    _refused(hip.mdns_backend_draw_band(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound), _lib.ptr(status), C.addressof(npairs), _lib.ptr(pb),
+    refused(hip.mdns_backend_draw_band_begin(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound)), "mdns_backend_draw_band", only)
+    refused(hip.mdns_backend_draw_band(dev._h, _lib.ptr(rows5), 4, _lib.ptr(bound), _lib.ptr(status), C.addressof(npairs), _lib.ptr(pb),
                                         _lib.ptr(pk), _lib.ptr(pL), _lib.ptr(pt), 64), "mdns_backend_draw_band", only)
     d_p = hip.mdns_dev_alloc(rows5.nbytes)
-    _refused(hip.mdns_joint_score_dev(dev._h, d_p, 4, 1.0, None, ndata), "mdns_joint_score_dev", only)
+    refused(hip.mdns_joint_score_dev(dev._h, d_p, 4, 1.0, None, ndata), "mdns_joint_score_dev", only)
     hip.mdns_dev_free(d_p)
     # ... and the state goes on as if nothing had happened: curve chunks decide as the statement does
     for attempt in range(6):

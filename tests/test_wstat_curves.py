@@ -8,11 +8,10 @@ import pytest
 
 from massivedatans_amd import _lib, jointstate, problem, sample
 from massivedatans_amd.like import CountSpectra, GaussLineSpectra, _Spectra
-from curves_support import gauss_prior
+from curves_support import Chunks, StatementProblem, dev_batch, gauss_prior, refused, selections
 from filter_support import _drive
 from poisson_support import NumpyPoisson
 from wstat_support import DeviceScorer, NumpyWstat, rate, rate_within_bound, source_model, within_bound, wstat_data
-from test_curves import _Chunks, _StatementProblem
 
 pytestmark = pytest.mark.gpu
 
@@ -47,32 +46,6 @@ def _curves(B, nx, seed, st=None):
     return curves
 
 
-def _dev_batch(lib, spectra, curves, pad, rows, fn="mdns_curve_wstat_batch_dev", per=1):
-    """``fn`` on rows of nx + pad doubles (NaN behind the curves); ``per``: outputs per pair."""
-    B, nx = curves.shape
-    ldc = nx + pad
-    wide = np.full((B, ldc), np.nan)
-    wide[:, :nx] = curves
-    M = spectra.ndata if rows is None else len(rows)
-    out = np.empty((B, M, per)) if per > 1 else np.empty((B, M))
-    d_c, d_o = lib.mdns_dev_alloc(wide.nbytes), lib.mdns_dev_alloc(out.nbytes)
-    d_r = None
-    try:
-        assert d_c and d_o
-        _lib.check(lib.mdns_h2d(d_c, _lib.ptr(wide), wide.nbytes), "h2d")
-        if rows is not None:
-            r32 = np.ascontiguousarray(rows, dtype=np.int32)
-            d_r = lib.mdns_dev_alloc(r32.nbytes)
-            _lib.check(lib.mdns_h2d(d_r, _lib.ptr(r32), r32.nbytes), "h2d")
-        _lib.check(getattr(lib, fn)(spectra.handle, d_c, ldc, B, d_r, M, d_o), fn)
-        _lib.check(lib.mdns_d2h(_lib.ptr(out), d_o, out.nbytes), "d2h")
-    finally:
-        for p in (d_c, d_o, d_r):
-            if p:
-                lib.mdns_dev_free(p)
-    return out
-
-
 def _t(a):
     return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=float).T)
 
@@ -96,18 +69,6 @@ class _RawBackground(_Spectra):
         return self._batch(self._lib.mdns_curve_poisson_batch, "mdns_curve_poisson_batch", np.atleast_2d(_lib.as_f64(curves)), rows)
 
 
-def _selections(ndata, rng):
-    sel = [("all", None), ("one", np.array([ndata // 3]))]
-    if ndata >= 3:
-        sel.append(("third", np.arange(rng.randint(0, 3), ndata, 3)))
-    if ndata > 1:
-        sel.append(("ragged", np.sort(rng.choice(ndata, size=ndata - 1, replace=False))))
-    for m in MS:
-        if ndata > m + 1:
-            sel.append(("sparse %d" % m, np.sort(rng.choice(ndata, size=m, replace=False))))
-    return sel
-
-
 @pytest.mark.parametrize("nx,ndata,B,exposure", CASES)
 def test_kernel_against_the_statement(nx, ndata, B, exposure, hip):
     """Every L within ``bound`` of the longdouble statement (wstat_support derives it), over the whole set and over
@@ -126,13 +87,13 @@ def test_kernel_against_the_statement(nx, ndata, B, exposure, hip):
         assert up > 0.02 and down > 0.02 and near > 0, (up, down, near)
     want = (st.loglike_batch_long(curves),) + st.sums_long(curves)        # once, for every selection
     worst = 0.0
-    for name, rows in _selections(ndata, rng):
+    for name, rows in selections(ndata, rng, MS):
         got = spectra.loglike_batch_curves(curves, rows)
         assert got.shape == (B, ndata if rows is None else len(rows))
         ok, frac = within_bound(got, st, nx, curves, rows, want)
         worst = max(worst, frac)
         assert ok, (name, frac)
-        assert np.array_equal(_dev_batch(hip, spectra, curves, 3, rows), got), name
+        assert np.array_equal(dev_batch(hip, spectra, curves, 3, rows, "mdns_curve_wstat_batch_dev"), got), name
         assert np.array_equal(spectra.loglike_batch(curves, rows), got), name
     print("nx=%d ndata=%d B=%d exposure=%s: worst error %.3g of the bound; a >= 0 in %.2f, a < 0 in %.2f, %d near" %
           (nx, ndata, B, exposure, worst, up, down, near))
@@ -155,13 +116,13 @@ def test_background_fit_against_the_statement(nx, ndata, B, exposure, hip):
     spectra = CountSpectra(d["x"], d["y"], d["e"], d["b"], d["g"])
     curves = _curves(B, nx, nx + B, st)
     worst = 0.0
-    for name, rows in _selections(ndata, rng):
+    for name, rows in selections(ndata, rng, MS):
         f = spectra.background_fit(curves, rows)
         assert f.shape == (B, ndata if rows is None else len(rows), nx)
         ok, frac = rate_within_bound(f, st, curves, rows)
         worst = max(worst, frac)
         assert ok, (name, frac)
-        assert np.array_equal(_dev_batch(hip, spectra, curves, 5, rows, "mdns_curve_background_batch_dev", per=nx), f), name
+        assert np.array_equal(dev_batch(hip, spectra, curves, 5, rows, "mdns_curve_background_batch_dev", per=nx), f), name
     f = spectra.background_fit(curves)
     assert (f[:, st.masked.T] == 0).all() and (f >= 0).all()
     pick = [(rng.randint(B), rng.randint(ndata), rng.randint(nx)) for _ in range(2000)]
@@ -212,7 +173,7 @@ def test_a_pair_has_one_value(hip):
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm], sel), whole[perm][:, sel])
     assert np.array_equal(spectra.loglike_batch_curves(curves[perm[:5]], sel[3:4]), whole[perm[:5]][:, sel[3:4]])
     for pad in (0, 1, 56):
-        assert np.array_equal(_dev_batch(hip, spectra, curves[perm[:70]], pad, sel), whole[perm[:70]][:, sel]), pad
+        assert np.array_equal(dev_batch(hip, spectra, curves[perm[:70]], pad, sel, "mdns_curve_wstat_batch_dev"), whole[perm[:70]][:, sel]), pad
     nlive = 40
     js = jointstate.CurveJointState(spectra, nlive, lambda xs: curves[xs[:, 0].astype(int)])
     js.init(np.arange(20, 20 + nlive, dtype=float)[:, None])
@@ -345,7 +306,7 @@ def test_joint_state_equals_its_numpy_statement(ndata, nlive, nx, noisy):
     assert dev.nparams == 3 and np.array_equal(dev.live_matrix(), host.live_matrix())
     want = NumpyWstat(d["y"], d["e"], d["b"], d["g"]).loglike_batch_long(model(xs0)).astype(float) + (noise0 if noisy else 0)
     assert np.allclose(dev.live_matrix(), want, rtol=1e-11, atol=1e-9)
-    assert _drive(_Chunks(dev, lambda xs: xs, noisy), _Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
+    assert _drive(Chunks(dev, lambda xs: xs, noisy), Chunks(host, model, noisy), ndata, rng, iterations=8, exact=True) > 0
     dev.close()
     spectra.close()
 
@@ -354,7 +315,7 @@ def test_whole_run_equals_the_statement():
     d = wstat_data(12, 64, seed=9, edges=False)
     model = source_model(d["x"])
     runs = []
-    for cls in (problem.CurveProblem, _StatementProblem):
+    for cls in (problem.CurveProblem, StatementProblem):
         p = cls(d["x"], d["y"], model, gauss_prior, 3, poisson=True, exposure=d["e"], background=d["b"], background_exposure=d["g"])
         assert isinstance(p.backend, CountSpectra) and p.backend.has_background
         with np.errstate(all="ignore"):
@@ -367,11 +328,6 @@ def test_whole_run_equals_the_statement():
         assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
-def _refused(rc, *words):
-    msg = _lib.last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
 def test_the_background_is_set_only_where_it_has_a_meaning(hip):
     """Every refusal of include/mdns.h Part 11 names its function and reason and leaves the handle as it was."""
     nx, ndata = 64, 20
@@ -382,11 +338,11 @@ def test_the_background_is_set_only_where_it_has_a_meaning(hip):
     got = np.empty((5, ndata))
     fout = np.empty((5, ndata, nx))
     assert hip.mdns_spectra_background(None) == -1
-    _refused(hip.mdns_spectra_set_background(None, _lib.ptr(b_rows), None, None), "mdns_spectra_set_background", "null")
+    refused(hip.mdns_spectra_set_background(None, _lib.ptr(b_rows), None, None), "mdns_spectra_set_background", "null")
     # a handle that is not in counts mode
     plain = GaussLineSpectra(d["x"], st.y, noise_level=1.0)
     before = plain.loglike_batch_curves(curves)
-    _refused(hip.mdns_spectra_set_background(plain.handle, _lib.ptr(b_rows), _lib.ptr(g_rows), None), "mdns_spectra_set_background", "not in counts mode")
+    refused(hip.mdns_spectra_set_background(plain.handle, _lib.ptr(b_rows), _lib.ptr(g_rows), None), "mdns_spectra_set_background", "not in counts mode")
     assert hip.mdns_spectra_background(plain.handle) == 0 and np.array_equal(plain.loglike_batch_curves(curves), before)
     plain.close()
     # a counts handle without a background: the new batch functions refuse, the Poisson one goes on
@@ -395,26 +351,26 @@ def test_the_background_is_set_only_where_it_has_a_meaning(hip):
     c_before = counts.loglike_batch_curves(curves)
     d_c, d_o = hip.mdns_dev_alloc(curves.nbytes), hip.mdns_dev_alloc(fout.nbytes)
     no = "spectra have no background (mdns_spectra_set_background)"
-    _refused(hip.mdns_curve_wstat_batch(counts.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)), "mdns_curve_wstat_batch", no)
-    _refused(hip.mdns_curve_wstat_batch_dev(counts.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", no)
-    _refused(hip.mdns_curve_background_batch(counts.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(fout)), "mdns_curve_background_batch", no)
-    _refused(hip.mdns_curve_background_batch_dev(counts.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_background_batch_dev", no)
+    refused(hip.mdns_curve_wstat_batch(counts.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)), "mdns_curve_wstat_batch", no)
+    refused(hip.mdns_curve_wstat_batch_dev(counts.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", no)
+    refused(hip.mdns_curve_background_batch(counts.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(fout)), "mdns_curve_background_batch", no)
+    refused(hip.mdns_curve_background_batch_dev(counts.handle, d_c, nx, 5, None, ndata, d_o), "mdns_curve_background_batch_dev", no)
     with pytest.raises(ValueError):
         counts.background_fit(curves)
     # null counts; a bad exposure or count is found in the host arrays, named, and nothing is uploaded
-    _refused(hip.mdns_spectra_set_background(counts.handle, None, _lib.ptr(g_rows), None), "mdns_spectra_set_background", "null background counts")
+    refused(hip.mdns_spectra_set_background(counts.handle, None, _lib.ptr(g_rows), None), "mdns_spectra_set_background", "null background counts")
     for bad in (-1.0, np.inf, -np.inf):
         wrong = g_rows.copy()
         wrong[7, 5] = bad
-        _refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(b_rows), _lib.ptr(wrong), None), "mdns_spectra_set_background", "bkg_exposure[7][5]")
+        refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(b_rows), _lib.ptr(wrong), None), "mdns_spectra_set_background", "bkg_exposure[7][5]")
     wrong = b_rows.copy()
     wrong[3, 9], g_ok = -2.0, g_rows.copy()
     g_ok[3, 9] = 1.0
-    _refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(wrong), _lib.ptr(g_ok), None), "mdns_spectra_set_background", "bkg_counts[3][9]")
+    refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(wrong), _lib.ptr(g_ok), None), "mdns_spectra_set_background", "bkg_counts[3][9]")
     assert hip.mdns_spectra_background(counts.handle) == 0 and np.array_equal(counts.loglike_batch_curves(curves), c_before)
     # once a joint state exists on the handle
     js = jointstate.CurveJointState(counts, 8, source_model(d["x"], floor=0.05))
-    _refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(b_rows), _lib.ptr(g_rows), None), "mdns_spectra_set_background", "a joint state exists")
+    refused(hip.mdns_spectra_set_background(counts.handle, _lib.ptr(b_rows), _lib.ptr(g_rows), None), "mdns_spectra_set_background", "a joint state exists")
     js.close()
     assert hip.mdns_spectra_background(counts.handle) == 0 and np.array_equal(counts.loglike_batch_curves(curves), c_before)
     # now it goes through (a NaN exposure masks); set_counts is refused from here on, and the state stays
@@ -426,7 +382,7 @@ def test_the_background_is_set_only_where_it_has_a_meaning(hip):
     both = CountSpectra(d["x"], d["y"], d["e"], d["b"], d["g"])
     assert hip.mdns_curve_wstat_batch(counts.handle, _lib.ptr(curves), 5, None, ndata, _lib.ptr(got)) == 0
     assert np.array_equal(got, both.loglike_batch_curves(curves))
-    _refused(hip.mdns_spectra_set_counts(counts.handle, None, None), "mdns_spectra_set_counts", "have a background")
+    refused(hip.mdns_spectra_set_counts(counts.handle, None, None), "mdns_spectra_set_counts", "have a background")
     assert np.array_equal(got, both.loglike_batch_curves(curves))
     # mdns_curve_poisson_batch on such a handle: the C statistic of the n, e and K that are on it -- n and e masked
     # under the new rule, K the one given to set_counts
@@ -437,19 +393,19 @@ def test_the_background_is_set_only_where_it_has_a_meaning(hip):
     assert np.allclose(pois - K0[None, :], masked_counts.loglike_batch_curves(curves) - k_now[None, :], rtol=1e-13, atol=1e-10)
     assert np.array_equal(both._batch(hip.mdns_curve_poisson_batch, "mdns_curve_poisson_batch", curves, None), masked_counts.loglike_batch_curves(curves))
     # sizes and null arguments, as mdns_curve_poisson_batch[_dev]
-    _refused(hip.mdns_curve_wstat_batch(both.handle, _lib.ptr(curves), 5, None, ndata + 1, _lib.ptr(got)), "mdns_curve_wstat_batch", "M=%d" % (ndata + 1))
-    _refused(hip.mdns_curve_wstat_batch_dev(both.handle, d_c, nx - 1, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", "ldc=%d" % (nx - 1), "nx=%d" % nx)
-    _refused(hip.mdns_curve_wstat_batch_dev(both.handle, None, nx, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", "null argument")
-    _refused(hip.mdns_curve_background_batch_dev(both.handle, d_c, nx, 5, None, ndata, None), "mdns_curve_background_batch_dev", "null argument")
+    refused(hip.mdns_curve_wstat_batch(both.handle, _lib.ptr(curves), 5, None, ndata + 1, _lib.ptr(got)), "mdns_curve_wstat_batch", "M=%d" % (ndata + 1))
+    refused(hip.mdns_curve_wstat_batch_dev(both.handle, d_c, nx - 1, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", "ldc=%d" % (nx - 1), "nx=%d" % nx)
+    refused(hip.mdns_curve_wstat_batch_dev(both.handle, None, nx, 5, None, ndata, d_o), "mdns_curve_wstat_batch_dev", "null argument")
+    refused(hip.mdns_curve_background_batch_dev(both.handle, d_c, nx, 5, None, ndata, None), "mdns_curve_background_batch_dev", "null argument")
     assert hip.mdns_curve_wstat_batch_dev(both.handle, d_c, nx, 0, None, ndata, d_o) == 0
     assert hip.mdns_curve_background_batch_dev(both.handle, d_c, nx, 5, None, 0, d_o) == 0
     bad_rows = np.array([0, ndata], dtype=np.int32)
-    _refused(hip.mdns_curve_background_batch(both.handle, _lib.ptr(curves), 5, _lib.ptr(bad_rows), 2, _lib.ptr(fout)), "mdns_curve_background_batch", "row_ids[1]")
+    refused(hip.mdns_curve_background_batch(both.handle, _lib.ptr(curves), 5, _lib.ptr(bad_rows), 2, _lib.ptr(fout)), "mdns_curve_background_batch", "row_ids[1]")
     # a state on a handle with a background refuses set_background too, and takes curve chunks only
     js = jointstate.CurveJointState(both, 8, source_model(d["x"]))
-    _refused(hip.mdns_spectra_set_background(both.handle, _lib.ptr(b_rows), None, None), "mdns_spectra_set_background", "a joint state exists")
+    refused(hip.mdns_spectra_set_background(both.handle, _lib.ptr(b_rows), None, None), "mdns_spectra_set_background", "a joint state exists")
     rows5 = np.ones((8, 5))
-    _refused(hip.mdns_joint_init_muse3(js._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", "counts spectra take curve chunks only")
+    refused(hip.mdns_joint_init_muse3(js._h, _lib.ptr(rows5), None), "mdns_joint_init_muse3", "counts spectra take curve chunks only")
     js.close()
     assert np.array_equal(got, both.loglike_batch_curves(curves))
     hip.mdns_dev_free(d_c)
