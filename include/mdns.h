@@ -952,6 +952,72 @@ int mdns_curve_background_batch(mdns_spectra *s, const double *curves, int B, co
 int mdns_curve_background_batch_dev(mdns_spectra *s, const double *d_curves, int ldc, int B, const int *d_row_ids, int M,
                                     double *d_fout);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 12 -- a MODEL on the device: a tabulated template grid (csrc/mdns_table.hip, k_table_curves).
+ *
+ * The model of the reference's real workload (musefuse.py:222-284) and of X-ray table models: templates tabulated over
+ * a few parameters, interpolated multilinearly, resampled at x / (1 + z) with numpy.interp's end rules, times an
+ * amplitude.  The caller hands the table over once; the curves of a chunk are made on the device from the candidates'
+ * parameters and never leave it on their way to the curve scoring of Parts 2, 9, 10 and 11.
+ *
+ * All float64.  axes: d arrays (1 <= d <= MDNS_TABLE_MAX_AXES), axis a of n_a >= 2 knots, finite, strictly increasing,
+ * one after the other; grid f64[nw], nw >= 2, finite, strictly increasing: the templates' own abscissa; table
+ * f64[n_1] .. [n_d][nw], C order, finite, any sign; x f64[nx], finite: the abscissa of the data.  A candidate is the
+ * row (p_1 .. p_d [, z] [, A]): z with MDNS_TABLE_REDSHIFT, A with MDNS_TABLE_AMPLITUDE, ndim = d + the flags set.
+ *
+ * Per candidate, every step ONE rounded fp64 operation, in this order, nothing contracted into an FMA:
+ *
+ *   cell      v_a = p_a clamped to [axis_a[0], axis_a[n_a - 1]]   (v < lo ? lo : v > hi ? hi : v: +-inf clamp)
+ *             i_a = the last knot <= v_a, at most n_a - 2;   f_a = (v_a - axis_a[i_a]) / (axis_a[i_a + 1] - axis_a[i_a])
+ *   weights   for corner c = 0 .. 2^d - 1 (bit a of c set: knot i_a + 1):  w_c = 1, then for a ascending
+ *             w_c = w_c * (bit a set ? f_a : 1 - f_a)
+ *   abscissa  u_j = x_j / (1 + z) (without the flag u_j = x_j), clamped to [grid[0], grid[nw - 1]] in the same way;
+ *             k_j = the last knot <= u_j, at most nw - 2;   t_j = (u_j - grid[k_j]) / (grid[k_j + 1] - grid[k_j])
+ *   value     acc = 0, then for c ascending  acc = acc + w_c * (T_c[k_j] + t_j * (T_c[k_j + 1] - T_c[k_j]))
+ *             with T_c the table row of corner c;   curve[b][j] = A * acc (without the flag acc)
+ *
+ * A NaN in ANY parameter of a candidate makes its whole row NaN (and no other row): under every curve statistic such
+ * a candidate is never accepted.  z = -1 gives u = +-inf, which clamps (where x_j = 0 as well, u_j = 0 / 0 and that
+ * channel is NaN).  A value does not depend on B, on the candidate's place in the batch, on ldc or on the entry point;
+ * / is the device's correctly rounded fp64 division.  The numpy statement of the same chain is
+ * massivedatans_amd/tablemodel.py, TableModel.statement: the two agree bit for bit.
+ *
+ * mdns_table_create: copies everything to the device; the handle owns its blocks.  All or none: NULL (mdns_last_error
+ * says why) and nothing left allocated when an argument is null, a size is outside its cap below, a knot, x or table
+ * value is not finite, an axis or the grid is not strictly increasing (the message names the array and the index),
+ * flags holds an unknown bit, or the device refuses.  Every rule is looked for in the host arrays before the device is
+ * asked for anything.  mdns_table_nparams: ndim; mdns_table_nx: nx (-1: null handle).
+ *
+ * mdns_table_curves_batch: params host f64[B][ndim] -> out host f64[B][nx] (synchronous).  _dev: device pointers,
+ * rows of ldc >= nx doubles whose padding is not touched, asynchronous on the library stream.  B == 0: nothing happens.
+ *
+ * mdns_backend_draw_table: mdns_backend_draw_curves (Part 5) with the curves of params host f64[B][ndim] made by the
+ * table on the library's stream into a buffer of the joint state's: the same checks, then exactly the path of
+ * mdns_backend_draw_curves_dev -- whichever curve statistic the state's spectra select.  Refuses a null table and one
+ * whose nx is not the spectra's.  mdns_joint_init_table: mdns_joint_init_curves with the live points' curves made from
+ * params f64[nlive][ndim] in the same way.
+ *
+ * Not covered: more than MDNS_TABLE_MAX_AXES axes, interpolation other than linear, line-of-sight broadening or
+ * extinction (fold them into the table, or use a model of your own), sharded runs, the chained first batch.
+ * ------------------------------------------------------------------------------------------ */
+#define MDNS_TABLE_MAX_AXES 4
+#define MDNS_TABLE_MAX_NX (1 << 20)            /* channels of x at most                                  */
+#define MDNS_TABLE_MAX_ELEMS 2147483647LL      /* table values at most (and knots of all axes together)   */
+#define MDNS_TABLE_TILE 256                    /* channels per workgroup of k_table_curves                */
+#define MDNS_TABLE_REDSHIFT 1
+#define MDNS_TABLE_AMPLITUDE 2
+typedef struct mdns_table mdns_table;
+mdns_table *mdns_table_create(const double *x, int nx, int d, const int *n, const double *axes, int nw, const double *grid,
+                              const double *table, int flags);
+void mdns_table_destroy(mdns_table *t);
+int mdns_table_nparams(const mdns_table *t);
+int mdns_table_nx(const mdns_table *t);
+int mdns_table_curves_batch(mdns_table *t, const double *params, int B, double *out);
+int mdns_table_curves_batch_dev(mdns_table *t, const double *d_params, int B, double *d_out, int ldc);
+int mdns_backend_draw_table(void *joint, mdns_table *table, const double *params, int B, const double *jitter, int *accepted,
+                            unsigned long long *fillbits, int *nscored);
+int mdns_joint_init_table(mdns_joint *j, mdns_table *table, const double *params, double noise_level, const double *jitter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ ABI_SYMBOLS = (
     # Part 11: the same with a background spectrum per spectrum, the W statistic (csrc/mdns_curves.hip k_curve_rows_b)
     "mdns_spectra_set_background", "mdns_spectra_background", "mdns_curve_wstat_batch", "mdns_curve_wstat_batch_dev",
     "mdns_curve_background_batch", "mdns_curve_background_batch_dev",
+    # Part 12: a tabulated template grid as the model, evaluated on the device (csrc/mdns_table.hip k_table_curves)
+    "mdns_table_create", "mdns_table_destroy", "mdns_table_nparams", "mdns_table_nx", "mdns_table_curves_batch",
+    "mdns_table_curves_batch_dev", "mdns_backend_draw_table", "mdns_joint_init_table",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -79,6 +82,11 @@ HOST_ABI_SYMBOLS = (
 
 #: mdns.h MDNS_JOINT_MAX_BATCH
 JOINT_MAX_BATCH = 1024
+#: mdns.h Part 12: MDNS_TABLE_MAX_AXES, MDNS_TABLE_TILE, MDNS_TABLE_REDSHIFT, MDNS_TABLE_AMPLITUDE
+TABLE_MAX_AXES = 4
+TABLE_TILE = 256
+TABLE_REDSHIFT = 1
+TABLE_AMPLITUDE = 2
 
 
 class MdnsError(RuntimeError):
@@ -235,6 +243,14 @@ def _declare(lib):
         "mdns_curve_wstat_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
         "mdns_curve_background_batch": (i, [vp, vp, i, vp, i, vp]),
         "mdns_curve_background_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
+        "mdns_table_create": (vp, [vp, i, i, vp, vp, i, vp, vp, i]),
+        "mdns_table_destroy": (None, [vp]),
+        "mdns_table_nparams": (i, [vp]),
+        "mdns_table_nx": (i, [vp]),
+        "mdns_table_curves_batch": (i, [vp, vp, i, vp]),
+        "mdns_table_curves_batch_dev": (i, [vp, vp, i, vp, i]),
+        "mdns_backend_draw_table": (i, [vp, vp, vp, i, vp, vp, vp, vp]),
+        "mdns_joint_init_table": (i, [vp, vp, vp, d, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -429,7 +429,8 @@ struct mdns_joint {
 	DeviceBuffer<int> d_filter_scratch;                     // matrix-core filter: ambiguous marks (zero when made)
 	DeviceBuffer<double> d_dense;                           // L[B, M] of a chunk (kind 1)
 	DeviceBuffer<double> d_jitter;
-	DeviceBuffer<double> d_curves;                          // model curves of a chunk that came as a host array
+	DeviceBuffer<double> d_curves;                          // model curves of a chunk that came as a host array, or that a table model made
+	DeviceBuffer<double> d_tparams;                         // candidates of a table model's chunk [B][ndim]
 	// the draw in progress through the mdns_backend_* entry points: its selection, uploaded once
 	DeviceBuffer<int> d_sel_rows;
 	bool sel_rows = false;
@@ -633,17 +634,12 @@ static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, 
 	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);
 }
 
-extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter)
+// the live points' likelihoods from their curves in j->d_curves [nlive][nx], plus the jitter (host [nlive][ndata] or
+// nullptr); the state is reset and the stream drained
+static int init_from_curves(mdns_joint *j, Context *c, const double *jitter)
 {
-	Context *c = ctx();
-	if (!c || !j || !curves) return 1;
-	const int nx = j->s->nx;
-	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
 	const size_t n = (size_t) j->nlive * j->ndata;
-	if (j->kind == 0) j->noise_level = noise_level;
-	if (!j->d_curves.fit((size_t) j->nlive * nx)) return 1;
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (!curves_score(j, j->d_curves.get(), nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
+	if (!curves_score(j, j->d_curves.get(), j->s->nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
 	if (jitter) {
 		if (!j->d_jitter.fit(n)) return 1;
 		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
@@ -652,6 +648,50 @@ extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, doubl
 	}
 	if (joint_reset(j) != 0) return 1;
 	return joint_sync(c) ? 0 : 1;
+}
+
+extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter)
+{
+	Context *c = ctx();
+	if (!c || !j || !curves) return 1;
+	const int nx = j->s->nx;
+	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
+	if (j->kind == 0) j->noise_level = noise_level;
+	if (!j->d_curves.fit((size_t) j->nlive * nx)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	return init_from_curves(j, c, jitter);
+}
+
+// what a table model's entry points refuse before anything is touched: no table, or curves of another length
+static bool table_fits(const mdns_joint *j, const mdns_table *table, const char *who)
+{
+	if (!table) { set_error("%s: null table handle", who); return false; }
+	if (table->nx != j->s->nx) {
+		set_error("%s: the table model makes curves of %d channels, the spectra have %d", who, table->nx, j->s->nx);
+		return false;
+	}
+	return true;
+}
+
+// params host [B][table->ndim] -> j->d_curves [B][nx], made by the table model on the library's stream
+static bool table_curves(mdns_joint *j, Context *c, mdns_table *table, const double *params, int B)
+{
+	const size_t np = (size_t) B * table->ndim;
+	// (a pageable source: the runtime stages it and returns when the caller's buffer is free)
+	return j->d_tparams.fit(np) && j->d_curves.fit((size_t) B * table->nx) &&
+	       MDNS_HIP(hipMemcpyAsync(j->d_tparams.get(), params, np * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	       launch_table_curves(table, j->d_tparams.get(), B, j->d_curves.get(), table->nx);
+}
+
+extern "C" int mdns_joint_init_table(mdns_joint *j, mdns_table *table, const double *params, double noise_level, const double *jitter)
+{
+	Context *c = ctx();
+	if (!c || !j || !params) return 1;
+	if (j->s->nx < 1) { set_error("mdns_joint_init_table: spectra without channels"); return 1; }
+	if (!table_fits(j, table, "mdns_joint_init_table")) return 1;
+	if (j->kind == 0) j->noise_level = noise_level;
+	if (!table_curves(j, c, table, params, j->nlive)) return 1;
+	return init_from_curves(j, c, jitter);
 }
 
 extern "C" int mdns_joint_restore_live_dev(mdns_joint *j, const double *d_liveL)
@@ -1390,6 +1430,26 @@ extern "C" int mdns_backend_draw_curves(void *joint, const double *curves, int B
 	if (jitter && (!j->d_jitter.fit(n) ||
 	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
 	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, jitter ? j->d_jitter.get() : nullptr, accepted, fillbits, "mdns_backend_draw_curves");
+}
+
+// the same chunk with the curves made on the device by a table model (mdns.h Part 12): no scoring code of its own
+extern "C" int mdns_backend_draw_table(void *joint, mdns_table *table, const double *params, int B, const double *jitter, int *accepted,
+                                       unsigned long long *fillbits, int *nscored)
+{
+	Context *c = ctx();
+	mdns_joint *j = (mdns_joint *) joint;
+	const int nx = j ? j->s->nx : 0;
+	if (c && j && accepted) {
+		*accepted = -1;
+		if (!table_fits(j, table, "mdns_backend_draw_table")) return 1;
+	}
+	const int rc = draw_curves_check(j, c, params, nx, B, accepted, nscored, "mdns_backend_draw_table");
+	if (rc != 0) return rc > 0;
+	const size_t n = (size_t) B * j->sel_M;
+	if (!table_curves(j, c, table, params, B)) return 1;
+	if (jitter && (!j->d_jitter.fit(n) ||
+	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
+	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, jitter ? j->d_jitter.get() : nullptr, accepted, fillbits, "mdns_backend_draw_table");
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,

@@ -1,0 +1,240 @@
+// A tabulated template grid as the model of a run (mdns.h Part 12): the caller hands over the table once, the device
+// interpolates it per candidate -- multilinear in the grid's parameters, linear along the templates' own abscissa at
+// x / (1 + z), times an amplitude -- and the curves stay in device memory for the curve scoring kernels
+// (mdns_curves.hip).
+//
+// Every value is the chain of single rounded fp64 operations that mdns.h Part 12 writes out; this file is compiled with
+// -ffp-contract=off so that no multiply meets an add in an FMA, and the numpy statement
+// (massivedatans_amd/tablemodel.py, TableModel.statement) reproduces the kernel bit for bit.  The kernel is a gather: the
+// FMAs it gives up cost nothing.
+#include "mdns_internal.h"
+#include <cmath>
+#include <vector>
+
+namespace mdns {
+
+// what the kernel takes by value (80-odd bytes of kernel arguments: scalar loads, no lane touches memory for them)
+struct TableView {
+	const double *x, *axes, *grid, *table;
+	int nx, d, nw, ndim, flags;
+	int n[MDNS_TABLE_MAX_AXES];                // knots per axis
+	int axis_at[MDNS_TABLE_MAX_AXES];          // where axis a begins in `axes`
+	long long stride[MDNS_TABLE_MAX_AXES];     // doubles between neighbouring knots of axis a in `table`
+};
+
+// channels per workgroup, one per thread
+static constexpr int kTableTile = MDNS_TABLE_TILE;
+
+// the last knot <= v of knots[0 .. n-1] (ascending, n >= 2), capped at n - 2, for knots[0] <= v; 0 for a NaN
+__device__ __forceinline__ int last_knot(const double *__restrict__ knots, int n, double v)
+{
+	int lo = 0, hi = n - 1;
+	while (hi - lo > 1) {
+		const int mid = (lo + hi) >> 1;
+		if (knots[mid] <= v) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+// the clamp of the statement, as comparisons: +-inf clamp, a NaN stays
+__device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// grid (B, ceil(nx / kTableTile)): workgroup (b, tile) writes channels tile * kTableTile ... of candidate b.  The
+// candidate's cell, fractions, 2^d corner weights and row offsets are made once per workgroup (threads 0 .. d-1 an axis
+// each, then threads 0 .. 2^d - 1 a corner each) and read from LDS as broadcasts.  Thread t takes channel j: one binary
+// search in the templates' abscissa, then per corner the pair T_c[k], T_c[k+1]; neighbouring threads have neighbouring
+// (or equal) k, so a wave reads one contiguous window of every corner row.  Nothing a value is made of depends on B, on
+// the candidate's place in the batch or on ldc.
+__global__ __launch_bounds__(kTableTile) void k_table_curves(const TableView tv, const double *__restrict__ params, int B,
+                                                              double *__restrict__ out, int ldc)
+{
+	__shared__ double s_f[MDNS_TABLE_MAX_AXES];
+	__shared__ int s_i[MDNS_TABLE_MAX_AXES];
+	__shared__ double s_w[1 << MDNS_TABLE_MAX_AXES];
+	__shared__ long long s_off[1 << MDNS_TABLE_MAX_AXES];
+	__shared__ int s_nan;
+	const int b = blockIdx.x, tid = threadIdx.x, d = tv.d;
+	if (b >= B) return;                                                   // (uniform over the workgroup)
+	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	if (tid < d) {
+		const double *__restrict__ axis = tv.axes + tv.axis_at[tid];
+		const int n = tv.n[tid];
+		const double v = clamp_to(p[tid], axis[0], axis[n - 1]);
+		const int i = last_knot(axis, n, v);
+		s_i[tid] = i;
+		s_f[tid] = (v - axis[i]) / (axis[i + 1] - axis[i]);
+	} else if (tid == d) {
+		int any = 0;
+		for (int a = 0; a < tv.ndim; a++) any |= p[a] != p[a];
+		s_nan = any;
+	}
+	__syncthreads();
+	if (tid < (1 << d)) {
+		double w = 1.0;
+		long long off = 0;
+		for (int a = 0; a < d; a++) {
+			const int bit = (tid >> a) & 1;
+			const double f = s_f[a];
+			w = w * (bit ? f : 1.0 - f);
+			off += (long long) (s_i[a] + bit) * tv.stride[a];
+		}
+		s_w[tid] = w;
+		s_off[tid] = off;
+	}
+	__syncthreads();
+	const int j = blockIdx.y * kTableTile + tid;
+	if (j >= tv.nx) return;
+	double *__restrict__ o = out + (size_t) b * ldc + j;
+	if (s_nan) { *o = __builtin_nan(""); return; }
+	double u = tv.x[j];
+	if (tv.flags & MDNS_TABLE_REDSHIFT) u = u / (1.0 + p[d]);
+	const int nw = tv.nw;
+	u = clamp_to(u, tv.grid[0], tv.grid[nw - 1]);
+	const int k = last_knot(tv.grid, nw, u);
+	const double g0 = tv.grid[k];
+	const double t = (u - g0) / (tv.grid[k + 1] - g0);
+	double acc = 0.0;
+	const int corners = 1 << d;
+	for (int c = 0; c < corners; c++) {
+		const double *__restrict__ T = tv.table + s_off[c] + k;
+		const double lo = T[0], hi = T[1];
+		acc = acc + s_w[c] * (lo + t * (hi - lo));
+	}
+	if (tv.flags & MDNS_TABLE_AMPLITUDE) acc = p[tv.ndim - 1] * acc;
+	*o = acc;
+}
+
+static TableView table_view(const mdns_table *t)
+{
+	TableView tv = {};
+	tv.x = t->d_x.get(); tv.axes = t->d_axes.get(); tv.grid = t->d_grid.get(); tv.table = t->d_table.get();
+	tv.nx = t->nx; tv.d = t->d; tv.nw = t->nw; tv.ndim = t->ndim; tv.flags = t->flags;
+	int at = 0;
+	for (int a = 0; a < t->d; a++) { tv.n[a] = t->n[a]; tv.axis_at[a] = at; at += t->n[a]; }
+	long long stride = t->nw;
+	for (int a = t->d - 1; a >= 0; a--) { tv.stride[a] = stride; stride *= t->n[a]; }
+	return tv;
+}
+
+bool launch_table_curves(const mdns_table *t, const double *d_params, int B, double *d_out, int ldc)
+{
+	Context *c = ctx();
+	if (!c) return false;
+	if (B <= 0) return true;
+	const dim3 grid((unsigned) B, (unsigned) ((t->nx + kTableTile - 1) / kTableTile));
+	hipLaunchKernelGGL(k_table_curves, grid, dim3(kTableTile), 0, c->stream, table_view(t), d_params, B, d_out, ldc);
+	return launched("k_table_curves");
+}
+
+}  // namespace mdns
+
+using namespace mdns;
+
+// knots[0 .. n-1] finite and strictly increasing; else the error names `what` and the index
+static bool knots_ok(const double *knots, int n, const char *what, int axis)
+{
+	for (int i = 0; i < n; i++) {
+		if (!std::isfinite(knots[i])) {
+			if (axis >= 0) set_error("mdns_table_create: axis %d: knot %d = %g is not finite", axis, i, knots[i]);
+			else set_error("mdns_table_create: %s[%d] = %g is not finite", what, i, knots[i]);
+			return false;
+		}
+		if (i > 0 && !(knots[i] > knots[i - 1])) {
+			if (axis >= 0) set_error("mdns_table_create: axis %d is not strictly increasing at knot %d", axis, i);
+			else set_error("mdns_table_create: %s is not strictly increasing at [%d]", what, i);
+			return false;
+		}
+	}
+	return true;
+}
+
+extern "C" mdns_table *mdns_table_create(const double *x, int nx, int d, const int *n, const double *axes, int nw, const double *grid,
+                                         const double *table, int flags)
+{
+	// every rule of the statement, on the host copies, before the device is asked for anything
+	if (!x || !n || !axes || !grid || !table) { set_error("mdns_table_create: null argument"); return nullptr; }
+	if (nx < 1 || nx > MDNS_TABLE_MAX_NX) { set_error("mdns_table_create: nx=%d: 1 to %d channels", nx, MDNS_TABLE_MAX_NX); return nullptr; }
+	if (d < 1 || d > MDNS_TABLE_MAX_AXES) { set_error("mdns_table_create: d=%d: 1 to %d axes", d, MDNS_TABLE_MAX_AXES); return nullptr; }
+	if (flags & ~(MDNS_TABLE_REDSHIFT | MDNS_TABLE_AMPLITUDE)) { set_error("mdns_table_create: flags=%d: unknown bits", flags); return nullptr; }
+	const int ndim = d + ((flags & MDNS_TABLE_REDSHIFT) ? 1 : 0) + ((flags & MDNS_TABLE_AMPLITUDE) ? 1 : 0);
+	if (ndim > MDNS_MAX_DIM) { set_error("mdns_table_create: %d parameters > %d", ndim, MDNS_MAX_DIM); return nullptr; }
+	if (nw < 2) { set_error("mdns_table_create: nw=%d: the templates need 2 knots at least", nw); return nullptr; }
+	long long elems = nw, knots = 0;
+	for (int a = 0; a < d; a++) {
+		if (n[a] < 2) { set_error("mdns_table_create: axis %d has %d knots: 2 at least", a, n[a]); return nullptr; }
+		knots += n[a];
+		elems *= n[a];                                                // (<= 2^31 * 2^31 before the test: no overflow)
+		if (elems > MDNS_TABLE_MAX_ELEMS || knots > MDNS_TABLE_MAX_ELEMS) {
+			set_error("mdns_table_create: the table is too large: more than %lld values up to axis %d", (long long) MDNS_TABLE_MAX_ELEMS, a);
+			return nullptr;
+		}
+	}
+	for (int j = 0; j < nx; j++)
+		if (!std::isfinite(x[j])) { set_error("mdns_table_create: x[%d] = %g is not finite", j, x[j]); return nullptr; }
+	const double *axis = axes;
+	for (int a = 0; a < d; a++) {
+		if (!knots_ok(axis, n[a], "axis", a)) return nullptr;
+		axis += n[a];
+	}
+	if (!knots_ok(grid, nw, "grid", -1)) return nullptr;
+	for (long long i = 0; i < elems; i++)
+		if (!std::isfinite(table[i])) { set_error("mdns_table_create: table[%lld] = %g is not finite", i, table[i]); return nullptr; }
+	Context *c = ctx();
+	if (!c) return nullptr;
+	mdns_table *t = new mdns_table();
+	t->nx = nx; t->d = d; t->nw = nw; t->ndim = ndim; t->flags = flags;
+	for (int a = 0; a < d; a++) t->n[a] = n[a];
+	// (pageable sources; the synchronise below lets the caller's arrays go)
+	const bool ok =
+	    t->d_x.make((size_t) nx) && t->d_axes.make((size_t) knots) && t->d_grid.make((size_t) nw) && t->d_table.make((size_t) elems) &&
+	    MDNS_HIP(hipMemcpyAsync(t->d_x.get(), x, (size_t) nx * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipMemcpyAsync(t->d_axes.get(), axes, (size_t) knots * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipMemcpyAsync(t->d_grid.get(), grid, (size_t) nw * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipMemcpyAsync(t->d_table.get(), table, (size_t) elems * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	    MDNS_HIP(hipStreamSynchronize(c->stream));
+	if (!ok) { mdns_table_destroy(t); return nullptr; }               // (the owners free what was made)
+	return t;
+}
+
+extern "C" void mdns_table_destroy(mdns_table *t)
+{
+	if (!t) return;
+	Context *c = ctx();
+	if (c) (void) hipStreamSynchronize(c->stream);
+	delete t;
+}
+
+extern "C" int mdns_table_nparams(const mdns_table *t) { return t ? t->ndim : -1; }
+extern "C" int mdns_table_nx(const mdns_table *t) { return t ? t->nx : -1; }
+
+// what both forms check first; 1: refused, 0: go on, -1: nothing to do
+static int table_batch_check(const mdns_table *t, const void *params, int B, const void *out, int ldc, const char *who)
+{
+	if (!ctx()) return 1;
+	if (!t) { set_error("%s: null table handle", who); return 1; }
+	if (B < 0 || ldc < t->nx) { set_error("%s: bad sizes B=%d ldc=%d (nx=%d)", who, B, ldc, t->nx); return 1; }
+	if (B == 0) return -1;
+	if (!params || !out) { set_error("%s: null argument", who); return 1; }
+	return 0;
+}
+
+extern "C" int mdns_table_curves_batch_dev(mdns_table *t, const double *d_params, int B, double *d_out, int ldc)
+{
+	const int rc = table_batch_check(t, d_params, B, d_out, ldc, "mdns_table_curves_batch_dev");
+	if (rc != 0) return rc > 0;
+	return launch_table_curves(t, d_params, B, d_out, ldc) ? 0 : 1;
+}
+
+extern "C" int mdns_table_curves_batch(mdns_table *t, const double *params, int B, double *out)
+{
+	Context *c = ctx();
+	const int rc = table_batch_check(t, params, B, out, t ? t->nx : 0, "mdns_table_curves_batch");
+	if (rc != 0) return rc > 0;
+	const size_t np = (size_t) B * t->ndim, no = (size_t) B * t->nx;
+	if (!t->d_params.fit(np) || !t->d_out.fit(no)) return 1;
+	// (pageable memory: the runtime stages it; the call ends in a synchronise)
+	if (!MDNS_HIP(hipMemcpyAsync(t->d_params.get(), params, np * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!launch_table_curves(t, t->d_params.get(), B, t->d_out.get(), t->nx)) return 1;
+	if (!MDNS_HIP(hipMemcpyAsync(out, t->d_out.get(), no * sizeof(double), hipMemcpyDeviceToHost, c->stream))) return 1;
+	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
+}

@@ -511,18 +511,26 @@ class CurveJointState(GaussJointState):
     fixed-scale one with per-pixel variances (mdns_curve_chi2_batch), over a
     :class:`massivedatans_amd.like.CountSpectra` the Poisson one (mdns_curve_poisson_batch; with a background the W
     statistic, mdns_curve_wstat_batch).  ``nparams`` is the model's ``ndim``: what the first
-    ``init`` is given, or ``ndim=``.
+    ``init`` is given, or ``ndim=``.  With ``table=`` (a :class:`massivedatans_amd.tablemodel.DeviceTable`) the curves
+    are made on the device from the parameters and ``model`` is not called.
 
     A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in
     :meth:`draw_params`.  Whoever drives the draws -- the sampler, the native core, a test -- may or may not
     count accepted points into ``shelf_n`` itself, so :meth:`prepare` reads the shelf sizes back from the
     device instead of trusting the mirror."""
 
-    def __init__(self, spectra, nlive, model, shelf_cap=64, ndim=None):
+    def __init__(self, spectra, nlive, model, shelf_cap=64, ndim=None, table=None):
         super(CurveJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
         self.model = model
         self.nx = int(spectra.nx)
         self.nparams = int(ndim) if ndim is not None else None
+        # a table model on the device (tablemodel.DeviceTable): init and draw_params hand it the parameters and
+        # ``model`` is never called (mdns_joint_init_table, mdns_backend_draw_table)
+        self.table = table
+        if table is not None:
+            if self.nparams is not None and self.nparams != table.ndim:
+                raise ValueError("ndim = %d, the table model takes %d parameters" % (self.nparams, table.ndim))
+            self.nparams = int(table.ndim)
         self._d_jitter, self._d_jitter_bytes = None, 0
         self._n32 = numpy.zeros(self.ndata, dtype=numpy.int32)
 
@@ -558,16 +566,21 @@ class CurveJointState(GaussJointState):
         if xs.ndim != 2 or len(xs) != self.nlive or (self.nparams is not None and xs.shape[1] != self.nparams):
             raise ValueError("initial points must be [nlive, ndim]")
         self.nparams = int(xs.shape[1])
-        address, ld, on_device, keep = self._curves(xs)
-        if on_device:                                     # (once per run: through the host)
-            keep = _lib.as_f64(keep.cpu().numpy())
-            address = _lib.ptr(keep)
         if jitter is not None:
             jitter = _lib.as_f64(jitter)
             if jitter.shape != (self.nlive, self.ndata):
                 raise ValueError("jitter must be [nlive, ndata]")
-        self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.ptr(jitter) if jitter is not None else None),
-                    "mdns_joint_init_curves")
+        if self.table is not None:
+            xs = _lib.as_f64(xs)
+            self._check(self._lib.mdns_joint_init_table(self._h, self.table.handle, _lib.ptr(xs), self.noise_level,
+                                                        _lib.ptr(jitter) if jitter is not None else None), "mdns_joint_init_table")
+        else:
+            address, ld, on_device, keep = self._curves(xs)
+            if on_device:                                     # (once per run: through the host)
+                keep = _lib.as_f64(keep.cpu().numpy())
+                address = _lib.ptr(keep)
+            self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.ptr(jitter) if jitter is not None else None),
+                        "mdns_joint_init_curves")
         self.shelf_n[:] = 0
         self.nevals_scored += self.nlive * self.ndata
         self.ncalls += 1
@@ -594,7 +607,13 @@ class CurveJointState(GaussJointState):
         if B == 0 or M == 0:
             return -1, None, None, B
         params = numpy.asarray(params, dtype=float)[:B]
-        address, ld, on_device, keep = self._curves(params)
+        if self.table is not None:
+            params = _lib.as_f64(params)
+            if params.ndim != 2 or params.shape[1] != self.table.ndim:
+                raise ValueError("params must be [B, %d], got %s" % (self.table.ndim, params.shape))
+            address, ld, on_device, keep = None, self.nx, False, params
+        else:
+            address, ld, on_device, keep = self._curves(params)
         if rows is not None:
             rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
         if jitter is not None:
@@ -604,7 +623,11 @@ class CurveJointState(GaussJointState):
         self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.ptr(rows) if rows is not None else None, M),
                     "mdns_backend_draw_begin")
         out = (C.addressof(self._accepted), _lib.ptr(self._bits), C.addressof(self._nscored))
-        if on_device:
+        if self.table is not None:
+            self._check(self._lib.mdns_backend_draw_table(self._h, self.table.handle, _lib.ptr(params), B,
+                                                          _lib.ptr(jitter) if jitter is not None else None, *out),
+                        "mdns_backend_draw_table")
+        elif on_device:
             self._check(self._lib.mdns_backend_draw_curves_dev(self._h, address, ld, B, self._jitter_to_device(jitter), *out),
                         "mdns_backend_draw_curves_dev")
         else:

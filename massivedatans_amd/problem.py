@@ -86,6 +86,12 @@ class CurveProblem(object):
       profiled out in closed form of the joint Poisson likelihood of the two spectra (include/mdns.h Part 11).  A pixel
       masked on either side is ignored; ``backend.background_fit`` gives the fitted rates.
 
+    ``model`` may also be a :class:`massivedatans_amd.tablemodel.TableModel` (``ndim`` must be its ``ndim``), with every
+    likelihood above: the device then interpolates the table per candidate and scores the curves where they lie --
+    draws and the initial points hand over parameters (``mdns_backend_draw_table``, ``mdns_joint_init_table``) and no
+    curve is made in Python; ``multi_loglikelihood[_batch]`` fetch the device's curves and score them like any other.
+    Over a ``backend`` that is not on the device the model is ``TableModel.statement``.
+
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
     L[B, M]`` (tests put a numpy scorer there; the state is then the numpy one); by default the spectra go
@@ -132,6 +138,11 @@ class CurveProblem(object):
         if not 1 <= int(ndim) <= MAX_DIM:
             raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
         self.nparams = int(ndim)
+        from .tablemodel import TableModel
+        table_model = model if isinstance(model, TableModel) else None
+        if table_model is not None and table_model.ndim != self.nparams:
+            raise ValueError("ndim = %d, the table model takes %d parameters" % (self.nparams, table_model.ndim))
+        self.table = None                            # a table model on the device (tablemodel.DeviceTable)
         self.model = model
         self.priortransform_batch = priortransform_batch
         self.noise_level = float(noise_level)
@@ -153,6 +164,14 @@ class CurveProblem(object):
         if getattr(backend, "continuum", 0) != self.continuum:
             raise ValueError("the backend was made with continuum = %r, the problem with %d"
                              % (getattr(backend, "continuum", 0), self.continuum))
+        if table_model is not None:
+            # on the device the joint state hands parameters to the table (no curves are made in Python); what scores
+            # outside a draw fetches the device's curves.  Over any other backend the model is its numpy statement
+            if self._on_device():
+                self.table = table_model.bind(self.x)
+                self.model = self.table.curves
+            else:
+                self.model = lambda xs, _tm=table_model, _x=self.x: _tm.statement(_x, xs)
         if jitter_sigma > 0:
             self.multi_loglikelihood_batch = None         # (every evaluation draws its noise: one candidate at a time)
         self.ncalls = 0
@@ -194,7 +213,7 @@ class CurveProblem(object):
     def joint_state(self, nlive_points):
         from . import jointstate
         if self._on_device():
-            js = jointstate.CurveJointState(self.backend, nlive_points, self.model, ndim=self.nparams)
+            js = jointstate.CurveJointState(self.backend, nlive_points, self.model, ndim=self.nparams, table=self.table)
         else:
             js = jointstate.HostJointState(_ModelScorer(self._score, self.model), nlive_points, self.ndata,
                                            lambda xs: xs, nparams=self.nparams)
