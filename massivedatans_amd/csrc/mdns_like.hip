@@ -907,7 +907,9 @@ __device__ __forceinline__ void block_sums(double (&v)[N], double *slot)
 	for (int i = 0; i < N; i++) v[i] = (slot[i] + slot[N + i]) + (slot[2 * N + i] + slot[3 * N + i]);
 }
 
-// NP = channel pairs per thread (nx <= 512*NP); CB = candidates per barrier pair; W holds 1/v.
+// NP = channel pairs per thread, ceil(nx / 512) exactly (launch_muse_rows): the template loads below are not tested,
+// they read 512 NP doubles of a row and a row owns model_ld(nx) = 512 NP of them.  With a larger NP they would run into
+// the next row, or past the last.  CB = candidates per barrier pair; W holds 1/v.
 // Per candidate and channel: s1 += (y w) m, s2 += (m m) w, then chi += (y - s m)^2 w -- six
 // VALU operations, with y, w and y w resident in registers for all candidates of the row.
 template <int NP, int CB>
@@ -1467,21 +1469,31 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
 	if (gy < 1) gy = 1;
 	const int bchunk = 2 * (((B + gy - 1) / gy + 1) / 2);         // even: k_muse_rows<NP, 2> walks pairs
 	gy = (B + bchunk - 1) / bchunk;
-	note_kernel(1, two_rows ? "k_muse_rows2<%d>" : (variant == 1 ? "k_muse_rows<%d, 2>" : "k_muse_rows<%d, 1>"),
-	            nx <= 512 ? 1 : nx <= 1024 ? 2 : nx <= 2048 ? 4 : 8);
+	// NP = ceil(nx / 512) exactly: a row kernel then reads 512 NP <= model_ld(nx) <= ldm doubles of a template row
+	// -- its own row and nothing behind it -- with no test on the load (what lies in [nx, 512 NP) is the zero pad)
+	const int np = nx <= 512 ? 1 : (nx + 511) / 512;
+	if (nx <= 4096) note_kernel(1, two_rows ? "k_muse_rows2<%d>" : (variant == 1 ? "k_muse_rows<%d, 2>" : "k_muse_rows<%d, 1>"), np);
+	else note_kernel(1, "k_muse_rows_generic");
 #define MUSE_LAUNCH(NP) do { if (two_rows) hipLaunchKernelGGL((k_muse_rows2<NP>), dim3((blocks + 1) / 2), dim3(kBlock), 0, c->stream, \
 		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out); \
 	else if (variant == 1) hipLaunchKernelGGL((k_muse_rows<NP, 2>), dim3(blocks, gy), dim3(kBlock), 0, c->stream, \
 		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out, bchunk, fused); \
 	else hipLaunchKernelGGL((k_muse_rows<NP, 1>), dim3(blocks), dim3(kBlock), 0, c->stream, \
 		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out, B, none); } while (0)
-	if (nx <= 512) MUSE_LAUNCH(1);
-	else if (nx <= 1024) MUSE_LAUNCH(2);
-	else if (nx <= 2048) MUSE_LAUNCH(4);
-	else if (nx <= 4096) MUSE_LAUNCH(8);
-	else
+	if (ldm < model_ld(nx)) { set_error("launch_muse_rows: template rows %d apart, nx=%d needs %d", ldm, nx, model_ld(nx)); return false; }
+	switch (nx <= 4096 ? np : 0) {
+	case 1: MUSE_LAUNCH(1); break;
+	case 2: MUSE_LAUNCH(2); break;
+	case 3: MUSE_LAUNCH(3); break;
+	case 4: MUSE_LAUNCH(4); break;
+	case 5: MUSE_LAUNCH(5); break;
+	case 6: MUSE_LAUNCH(6); break;
+	case 7: MUSE_LAUNCH(7); break;
+	case 8: MUSE_LAUNCH(8); break;
+	default:
 		hipLaunchKernelGGL(k_muse_rows_generic, dim3(blocks), dim3(kBlock), 0, c->stream,
 		                   s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out);
+	}
 #undef MUSE_LAUNCH
 	return launched("k_muse_rows");
 }
