@@ -616,8 +616,8 @@ int mdns_backend_chunk_size(void *joint, int offered, int M, int hint);
 void *mdns_backend_region_begin(void *joint, const double *members, int K, int ndim, const unsigned *packed, int nbootstraps);
 int mdns_backend_region_radius(void *joint, void *region, double *radius);
 /* mdns_backend_draw_chunk for a model the CALLER evaluates: curves f64[B][nx], one model curve per candidate, in
- * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M], both kinds of
- * state).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
+ * place of the parameter rows (after mdns_backend_draw_begin; same outputs; jitter NULL or f64[B][M]; a state
+ * of any statistic).  Scored as mdns_curve_loglike_batch at the noise level of mdns_joint_init_curves / _init_gauss (no
  * variances), as mdns_muse_loglike_batch (variances), as mdns_curve_chi2_batch (variances, fixed scale: Part 9) or as
  * mdns_curve_poisson_batch (counts: Part 10; with a background mdns_curve_wstat_batch: Part 11), decided and committed
  * like a draw_chunk.  A draw may mix
@@ -632,8 +632,8 @@ int mdns_backend_draw_curves_dev(void *joint, const double *d_curves, int ldc, i
  * stages and scores the chunk like draw_chunk and leaves one int32 0 / 1 vote per candidate in device
  * memory (mdns_joint_votes_dev: int32[MDNS_JOINT_MAX_BATCH], asynchronous on the library stream);
  * `commit` takes the first candidate that has a vote THEN as the accepted one and finishes like
- * draw_chunk (shelves, thresholds, *accepted, fill bits of this handle's selected data sets).  Both
- * kinds of joint state (Gaussian line; scale-marginalised likelihood with jitter f64[B, M]). */
+ * draw_chunk (shelves, thresholds, *accepted, fill bits of this handle's selected data sets).  The two
+ * statistics with a parameter model (Gaussian line; scale-marginalised likelihood with jitter f64[B, M]). */
 int mdns_backend_draw_score(void *joint, const double *params, int B, const double *jitter);
 int *mdns_joint_votes_dev(mdns_joint *j);
 int mdns_backend_draw_commit(void *joint, int *accepted, unsigned long long *fillbits);

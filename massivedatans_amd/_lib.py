@@ -296,5 +296,10 @@ def ptr(a):
     return a.ctypes.data
 
 
+def opt(a):
+    """:func:`ptr` of an optional array: None (a NULL argument) for None."""
+    return None if a is None else a.ctypes.data
+
+
 def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)

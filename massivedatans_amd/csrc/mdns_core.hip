@@ -1044,6 +1044,17 @@ Wait mdns::wait_seq(const volatile unsigned long long *at, unsigned long long wa
 	return Wait::ok;
 }
 
+bool mdns::wait_ok(Wait w, hipError_t err, const char *who)
+{
+	switch (w) {
+	case Wait::ok: return true;
+	case Wait::timeout: set_error("%s: no result within MDNS_POLL_TIMEOUT_S", who); break;
+	case Wait::failed: set_error("%s failed: %s", who, hipGetErrorString(err)); break;
+	case Wait::empty: set_error("%s finished without a result", who); break;
+	}
+	return false;
+}
+
 // A radius computation on r's members into r's result slot: `launch` is launch_bootstrap (choice matrix) or
 // launch_bootstrap_packed (bit masks).  Once it is in the stream the membership kernel takes its threshold from
 // d_res, and the host copies are to be fetched under the new `seq`.
@@ -1181,12 +1192,7 @@ static bool region_fetch(mdns_region *r)
 {
 	if (!r->pending) return true;
 	hipError_t e = hipSuccess;
-	switch (wait_seq(&r->h_res->seq, r->seq, &e)) {
-	case Wait::ok: break;
-	case Wait::timeout: set_error("radius computation: no result within MDNS_POLL_TIMEOUT_S"); return false;
-	case Wait::failed: set_error("radius computation failed: %s", hipGetErrorString(e)); return false;
-	case Wait::empty: set_error("radius computation finished without a result"); return false;
-	}
+	if (!wait_ok(wait_seq(&r->h_res->seq, r->seq, &e), e, "radius computation")) return false;
 	r->radius = r->h_res->radius;
 	r->thresh_sq = sqrt_threshold(r->radius);     // the device derived the same number (tested)
 	r->pending = false;
@@ -1292,17 +1298,10 @@ extern "C" int mdns_region_count_polled(mdns_region *r, const double *points, in
 	if (!launch_count_within(r->d_members, r->K, r->ndim, r->thresh_sq, r->on_device ? r->d_res : nullptr,
 	                         (const double *) (stage_dev + off_points), M, (int *) (stage_dev + off_counts), &mail)) return 1;
 	hipError_t e = hipSuccess;
-	switch (wait_seq((const volatile unsigned long long *) stage, seq, &e)) {
-	case Wait::ok: break;
-	case Wait::timeout: set_error("membership count: no result within MDNS_POLL_TIMEOUT_S"); return 1;
-	case Wait::failed: set_error("membership count failed: %s", hipGetErrorString(e)); return 1;
-	case Wait::empty:
-		// (the stream drained and the number is not there: the launch failed; the ticket counter
-		// may be anywhere)
-		(void) hipMemsetAsync(ticket, 0, sizeof(int), c->stream);
-		set_error("membership count finished without a result");
-		return 1;
-	}
+	const Wait w = wait_seq((const volatile unsigned long long *) stage, seq, &e);
+	// (the stream drained and the number is not there: the launch failed; the ticket counter may be anywhere)
+	if (w == Wait::empty) (void) hipMemsetAsync(ticket, 0, sizeof(int), c->stream);
+	if (!wait_ok(w, e, "membership count")) return 1;
 	memcpy(counts, stage + off_counts, (size_t) M * sizeof(int));
 	return 0;
 }

@@ -486,12 +486,7 @@ extern "C" int mdns_groups_components(mdns_groups *g, const int32_t *rows, int M
 		// counts, flags and the list arrive in mapped host memory: poll for `seq` (looking at the
 		// stream now and then: a failed launch shows up as an error instead of a hang)
 		hipError_t e = hipSuccess;
-		switch (wait_seq(&g->h_box->seq, g->box_seq, &e)) {
-		case Wait::ok: break;
-		case Wait::timeout: set_error("mdns_groups_components: no result within MDNS_POLL_TIMEOUT_S"); return 1;
-		case Wait::failed: set_error("mdns_groups_components: %s", hipGetErrorString(e)); return 1;
-		case Wait::empty: set_error("mdns_groups_components: finished without a result"); return 1;
-		}
+		if (!wait_ok(wait_seq(&g->h_box->seq, g->box_seq, &e), e, "mdns_groups_components")) return 1;
 		if (h->status) {
 			const int status = h->status;
 			(void) hipMemsetAsync(&hdr_of(g)->status, 0, sizeof(int), c->stream);

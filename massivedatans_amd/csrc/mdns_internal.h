@@ -22,9 +22,13 @@ bool launched(const char *name);
 // wait_seq polls *at (mapped host memory a kernel on the context's stream raises last) until it holds `want`, looking
 // at the stream now and then: a failed launch shows up as an error instead of a hang.  ok: everything the kernel
 // stored before `want` can be read; timeout: the limit passed (the kernel may still be running); failed: the stream
-// reports *err; empty: the stream drained and the number is not there.  The error text is the caller's.
+// reports *err; empty: the stream drained and the number is not there.
 enum class Wait { ok, timeout, failed, empty };
 Wait wait_seq(const volatile unsigned long long *at, unsigned long long want, hipError_t *err = nullptr);
+// What a wait that did not succeed becomes under the caller's name for what it waited for: "<who>: no result within
+// MDNS_POLL_TIMEOUT_S", "<who> failed: <the stream's error>", "<who> finished without a result".  True: the number is
+// there and no text was set.  (A caller that has something to put right after Wait::empty still holds the value.)
+bool wait_ok(Wait w, hipError_t err, const char *who);
 
 // ---- owned memory: grow-only scratch and exact-size blocks ------------------------------------
 // Two owners, DeviceBuffer<T> and PinnedBuffer, and two ways to fill one:

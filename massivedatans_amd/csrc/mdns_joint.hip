@@ -369,7 +369,7 @@ __global__ void k_joint_fill(double *__restrict__ p, size_t n, double value)
 using namespace mdns;
 
 // what the accept pass of a backend chunk leaves for its commit.  path 0: none (-1: nothing of this handle's was
-// selected); 1: dense block (kind 1); 2: two launches; 3: lane kernels.  flag: what the pass wrote into d_flags for
+// selected); 1: dense block (K2 chunks, curve chunks); 2: two launches; 3: lane kernels.  flag: what the pass wrote into d_flags for
 // a candidate that beats a threshold.
 struct ChunkScore { int path, B, flag; };
 
@@ -405,7 +405,7 @@ struct mdns_joint {
 	DeviceBuffer<char> d_params;
 	double *params() const { return (double *) d_params.get(); }
 	int *d_rows = nullptr;             // inside d_params' block, behind the candidates
-	PinnedBuffer h_pin;
+	PinnedBuffer h_pin;                // host values on their way to the device, and a result's way back (stage_h2d has the rule)
 	// what the last score launched with (commit uses the same spectra replica and templates)
 	const double *last_yT = nullptr;
 	const int *last_gather = nullptr;
@@ -419,15 +419,17 @@ struct mdns_joint {
 	int staged_M = 0;
 	size_t staged_in_bytes = 0;
 	double noise_level = 0;            // of mdns_joint_init_gauss (the backend entry points score with it)
-	// which likelihood: 0 = the Gaussian line (clike.c; lane kernels, trail), 1 = the three-line
-	// template scored with the scale-marginalised chi^2 (cmuselike.c; dense L[B, M] block)
-	int kind = 0;
-	int nparams = 3;                   // kind 1: of the spectra's template model (5, or its line list's G + 2)
+	// which likelihood: curve_stat of the spectra, read once (their mode is fixed while a joint state exists on them).
+	// kCurveNoise: the Gaussian line (clike.c) -- parameter rows through the lane kernels and the trail; kCurveMarginal:
+	// the template with the scale marginalised (cmuselike.c) -- parameter rows through K2 into the dense L[B, M] block,
+	// and the band; any other: curve chunks only (wrong_stat).  A curve chunk takes the dense block whatever the statistic.
+	CurveStat stat = kCurveNoise;
+	int nparams = 3;                   // kCurveMarginal: of the spectra's template model (5, or its line list's G + 2)
 	bool counted = false;              // this state is in the spectra's njoint (the model is fixed while it lives)
 	// made on first use, each by itself
-	DeviceBuffer<double> d_msq;                             // templates' sums of squares (guarded accept filter, kind 0)
+	DeviceBuffer<double> d_msq;                             // templates' sums of squares (guarded accept filter, kCurveNoise)
 	DeviceBuffer<int> d_filter_scratch;                     // matrix-core filter: ambiguous marks (zero when made)
-	DeviceBuffer<double> d_dense;                           // L[B, M] of a chunk (kind 1)
+	DeviceBuffer<double> d_dense;                           // L[B, M] of a K2 parameter chunk or a curve chunk
 	DeviceBuffer<double> d_jitter;
 	DeviceBuffer<double> d_curves;                          // model curves of a chunk that came as a host array, or that a table model made
 	DeviceBuffer<double> d_tparams;                         // candidates of a table model's chunk [B][ndim]
@@ -497,10 +499,8 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	if (shelf_cap < 4) shelf_cap = 4;
 	mdns_joint *j = new mdns_joint();
 	j->s = s; j->nlive = nlive; j->cap = shelf_cap; j->ndata = s->ndata;
-	// spectra with variances: the scale-marginalised likelihood against the three-line template; counts (mdns.h Part 10)
-	// take the same dense route, through curve chunks alone (curves_only)
-	j->kind = s->d_w.get() || s->counts ? 1 : 0;
-	j->nparams = j->kind == 1 ? muse_nparams(s) : 3;
+	j->stat = curve_stat(s);
+	j->nparams = j->stat == kCurveMarginal ? muse_nparams(s) : 3;
 	const size_t nd = (size_t) s->ndata;
 	const size_t res = (size_t) kFlagInts * sizeof(int) + result_bytes(s->ndata);
 	static_assert(sizeof(JointHeader) % sizeof(int) == 0, "d_flags is counted in ints");
@@ -508,7 +508,7 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	    j->live.make((size_t) nlive * nd) && j->shelfL.make((size_t) shelf_cap * nd) && j->shelfn.make(nd) && j->higher.make(nd) &&
 	    j->d_running.make(nd) && j->d_Lmin.make(nd) && j->d_argmin_run.make(nd) && j->d_argmin.make(nd) && j->d_status.make(1) &&
 	    j->d_flags.make(res / sizeof(int)) &&
-	    // candidates [B, 3] followed by the selection's row ids: one staging block (kind 1: candidates [B, nparams] alone)
+	    // candidates [B, 3] followed by the selection's row ids: one staging block (kCurveMarginal: candidates [B, nparams] alone)
 	    j->d_params.make((size_t) MDNS_JOINT_MAX_BATCH * kJointParamsMost * sizeof(double) + nd * sizeof(int) + 16) &&
 	    j->box.make(sizeof(JointMailbox) + ((nd + 63) / 64) * 8);
 	if (ok) {
@@ -565,70 +565,102 @@ static int joint_reset(mdns_joint *j)
 	       MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) ? 0 : 1;
 }
 
-// A state over fixed-scale spectra (mdns.h Part 9) has no likelihood for parameter rows or templates: K2 would fit the
-// scale.  Nor has one over counts (Part 10): its handle has no weights d_w for K2, and its K1 replicas are not what the
-// Poisson likelihood means.  True (and the error set) for such a state; nothing of it has been touched or read.
-static bool curves_only(const mdns_joint *j, const char *who)
+// The refusal of a parameter-taking entry for a state of the wrong statistic: true, and the error set, when `who` does
+// not serve j's; nothing of the state has been touched or read.  Fixed-scale spectra (mdns.h Part 9) have no likelihood
+// for parameter rows or templates: K2 would fit the scale.  Nor have counts (Part 10): no weights d_w for K2, and their
+// K1 replicas are not what the Poisson likelihood means.  Of the two statistics with a parameter model an entry takes
+// one or both (`takes`); `other` is what it tells a state of the one it does not take.
+enum : unsigned { kTakesLine = 1, kTakesTemplate = 2, kNamesNull = 4, kBandIdle = 8 };     // (the last two: draw_entry)
+static bool wrong_stat(const mdns_joint *j, unsigned takes, const char *who, const char *other)
 {
-	const CurveStat stat = curve_stat(j->s);
-	if (stat == kCurveNoise || stat == kCurveMarginal) return false;
+	if (j->stat == kCurveNoise || j->stat == kCurveMarginal) {
+		if (takes & (j->stat == kCurveNoise ? kTakesLine : kTakesTemplate)) return false;
+		set_error("%s: %s", who, other);
+		return true;
+	}
 	set_error("%s: %s spectra take curve chunks only (mdns_joint_init_curves, mdns_backend_draw_curves)", who,
-	          stat == kCurveChi2 ? "fixed-scale" : "counts");
+	          j->stat == kCurveChi2 ? "fixed-scale" : "counts");
 	return true;
+}
+
+// Host values to the device through the pinned block: `bytes` of src, and `bytes2` of src2 right behind them, are in
+// h_pin and ONE copy of them to dst is in the stream when this returns true (`room`: what the block holds at least --
+// joint_stage_and_score keeps the outcome's way back behind the staged bytes).
+// THE RULE every caller relies on to reuse the one block: whatever was last copied out of h_pin has been consumed.  An
+// entry that stages ends with the host waiting behind its copy -- a joint_sync (init, a commit with a likelihood row) or
+// a mailbox that a later kernel raises (every chunk, the band's _end and _commit).  Where that wait is a second call's
+// (mdns_joint_score, mdns_backend_draw_score, mdns_backend_draw_band_begin) the rule holds for a caller that makes the
+// call before staging again; a score repeated without its commit rewrites the block under a copy it supersedes.
+static bool stage_h2d(mdns_joint *j, Context *c, void *dst, const void *src, size_t bytes, const void *src2 = nullptr, size_t bytes2 = 0,
+                      size_t room = 0)
+{
+	const size_t all = bytes + bytes2;
+	if (!j->h_pin.fit(room > all ? room : all)) return false;
+	if (all == 0) return true;
+	char *pin = j->h_pin.get();
+	if (bytes) memcpy(pin, src, bytes);
+	if (bytes2) memcpy(pin + bytes, src2, bytes2);
+	return MDNS_HIP(hipMemcpyAsync(dst, pin, all, hipMemcpyHostToDevice, c->stream));
+}
+
+// The noise of a chunk or of the initial points, `n` doubles of host memory: where the kernels read it once its copy
+// into d_jitter is in the stream.  nullptr: `jitter` is, or the copy could not be made (the error set).
+// (A pageable source: the runtime stages it and returns when the caller's buffer is free.)
+static const double *chunk_noise(mdns_joint *j, Context *c, const double *jitter, size_t n)
+{
+	if (!jitter || !j->d_jitter.fit(n) ||
+	    !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return nullptr;
+	return j->d_jitter.get();
+}
+
+// the noise [nlive][ndata], if any, added to the live points' likelihoods (as musefuse.py:535 does for its initial points)
+static bool add_noise_to_live(mdns_joint *j, Context *c, const double *jitter)
+{
+	const size_t n = (size_t) j->nlive * j->ndata;
+	const double *d_noise = chunk_noise(j, c, jitter, n);
+	if (!d_noise) return !jitter;
+	hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, d_noise, n);
+	return MDNS_HIP(hipGetLastError());
+}
+
+// the tail of every init entry, behind the scoring into st.live: the noise added, shelves and status cleared and the
+// stream drained -- the state holds the initial points when this returns 0
+static int init_finish(mdns_joint *j, Context *c, const double *jitter)
+{
+	return add_noise_to_live(j, c, jitter) && joint_reset(j) == 0 && joint_sync(c) ? 0 : 1;
 }
 
 extern "C" int mdns_joint_init_gauss(mdns_joint *j, const double *params, double noise_level)
 {
 	Context *c = ctx();
 	if (!c || !j || !params) return 1;
-	if (curves_only(j, "mdns_joint_init_gauss")) return 1;
-	if (j->kind != 0) { set_error("mdns_joint_init_gauss: these spectra carry variances (mdns_joint_init_muse3)"); return 1; }
+	if (wrong_stat(j, kTakesLine, "mdns_joint_init_gauss", "these spectra carry variances (mdns_joint_init_muse3)")) return 1;
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_gauss: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
-	if (!j->h_pin.fit((size_t) j->nlive * 24)) return 1;
-	char *pin = j->h_pin.get();
 	j->noise_level = noise_level;
-	memcpy(pin, params, (size_t) j->nlive * 24);
-	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, (size_t) j->nlive * 24, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!stage_h2d(j, c, j->params(), params, (size_t) j->nlive * 24)) return 1;
 	// always the lane kernel: every likelihood of a run is then the same chain of operations
 	if (gauss_loglike_cols_dev(j->s, j->params(), j->nlive, noise_level, nullptr, j->ndata, j->st.live) != 0) return 1;
-	if (joint_reset(j) != 0) return 1;
-	return joint_sync(c) ? 0 : 1;
+	return init_finish(j, c, nullptr);
 }
-
 
 extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const double *jitter)
 {
 	Context *c = ctx();
 	if (!c || !j || !params) return 1;
-	if (j->kind != 1) { set_error("mdns_joint_init_muse3: the spectra carry no variances"); return 1; }
-	if (curves_only(j, "mdns_joint_init_muse3")) return 1;
+	if (wrong_stat(j, kTakesTemplate, "mdns_joint_init_muse3", "the spectra carry no variances")) return 1;
 	if (j->nlive > MDNS_JOINT_MAX_BATCH) { set_error("mdns_joint_init_muse3: nlive=%d > %d", j->nlive, MDNS_JOINT_MAX_BATCH); return 1; }
-	const size_t pbytes = (size_t) j->nlive * j->nparams * sizeof(double), n = (size_t) j->nlive * j->ndata;
-	if (!j->h_pin.fit(pbytes)) return 1;
-	char *pin = j->h_pin.get();
-	memcpy(pin, params, pbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!stage_h2d(j, c, j->params(), params, (size_t) j->nlive * j->nparams * sizeof(double))) return 1;
 	if (mdns_lines_loglike_batch_dev(j->s, j->params(), j->nlive, nullptr, j->ndata, j->st.live) != 0) return 1;
-	if (jitter) {
-		// (musefuse.py:535 adds its noise to the initial points' likelihoods too)
-		if (!j->d_jitter.fit(n)) return 1;
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter.get(), n);
-		if (!MDNS_HIP(hipGetLastError())) return 1;
-	}
-	if (joint_reset(j) != 0) return 1;
-	return joint_sync(c) ? 0 : 1;
+	return init_finish(j, c, jitter);
 }
 
-// curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the handle's curve statistic (curve_stat: what
-// the mdns_curve_*_batch_dev entry of that statistic computes; kind 0 is the fixed-noise one), or -- kind 1 with the
-// scale marginalised -- the curves staged as zero-padded templates: exactly what mdns_muse_loglike_batch_dev does with
-// templates
+// curves [B][ldc] on the device against the selected rows -> d_out [B][M]: the state's statistic (what the
+// mdns_curve_*_batch_dev entry of that statistic computes; kCurveNoise at the state's noise level), or -- kCurveMarginal
+// -- the curves staged as zero-padded templates: exactly what mdns_muse_loglike_batch_dev does with templates
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
-	const CurveStat stat = curve_stat(s);
-	if (stat != kCurveMarginal) return launch_curve(stat, s, d_curves, ldc, B, j->noise_level, d_rows, M, d_out);
+	if (j->stat != kCurveMarginal) return launch_curve(j->stat, s, d_curves, ldc, B, j->noise_level, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
 	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
 	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);
@@ -638,16 +670,8 @@ static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, 
 // nullptr); the state is reset and the stream drained
 static int init_from_curves(mdns_joint *j, Context *c, const double *jitter)
 {
-	const size_t n = (size_t) j->nlive * j->ndata;
 	if (!curves_score(j, j->d_curves.get(), j->s->nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
-	if (jitter) {
-		if (!j->d_jitter.fit(n)) return 1;
-		if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		hipLaunchKernelGGL(k_joint_add, dim3(1024), dim3(kBlock), 0, c->stream, j->st.live, (const double *) j->d_jitter.get(), n);
-		if (!MDNS_HIP(hipGetLastError())) return 1;
-	}
-	if (joint_reset(j) != 0) return 1;
-	return joint_sync(c) ? 0 : 1;
+	return init_finish(j, c, jitter);
 }
 
 extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, double noise_level, const double *jitter)
@@ -656,7 +680,7 @@ extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, doubl
 	if (!c || !j || !curves) return 1;
 	const int nx = j->s->nx;
 	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
-	if (j->kind == 0) j->noise_level = noise_level;
+	if (j->stat == kCurveNoise) j->noise_level = noise_level;
 	if (!j->d_curves.fit((size_t) j->nlive * nx)) return 1;
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 	return init_from_curves(j, c, jitter);
@@ -677,7 +701,7 @@ static bool table_fits(const mdns_joint *j, const mdns_table *table, const char 
 static bool table_curves(mdns_joint *j, Context *c, mdns_table *table, const double *params, int B)
 {
 	const size_t np = (size_t) B * table->ndim;
-	// (a pageable source: the runtime stages it and returns when the caller's buffer is free)
+	// (a pageable source, as chunk_noise's)
 	return j->d_tparams.fit(np) && j->d_curves.fit((size_t) B * table->nx) &&
 	       MDNS_HIP(hipMemcpyAsync(j->d_tparams.get(), params, np * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
 	       launch_table_curves(table, j->d_tparams.get(), B, j->d_curves.get(), table->nx);
@@ -689,7 +713,7 @@ extern "C" int mdns_joint_init_table(mdns_joint *j, mdns_table *table, const dou
 	if (!c || !j || !params) return 1;
 	if (j->s->nx < 1) { set_error("mdns_joint_init_table: spectra without channels"); return 1; }
 	if (!table_fits(j, table, "mdns_joint_init_table")) return 1;
-	if (j->kind == 0) j->noise_level = noise_level;
+	if (j->stat == kCurveNoise) j->noise_level = noise_level;
 	if (!table_curves(j, c, table, params, j->nlive)) return 1;
 	return init_from_curves(j, c, jitter);
 }
@@ -867,8 +891,7 @@ extern "C" int mdns_joint_score_dev(mdns_joint *j, const double *d_params, int B
 {
 	Context *c = ctx();
 	if (!c || !check_draw(j, B, M, "mdns_joint_score_dev")) return 1;
-	if (curves_only(j, "mdns_joint_score_dev")) return 1;
-	if (j->kind != 0) { set_error("mdns_joint_score_dev: Gaussian-line states only (use the mdns_backend_* entry points)"); return 1; }
+	if (wrong_stat(j, kTakesLine, "mdns_joint_score_dev", "Gaussian-line states only (use the mdns_backend_* entry points)")) return 1;
 	mdns_spectra *s = j->s;
 	j->last_B = 0;
 	j->trail_valid = false;
@@ -1014,25 +1037,14 @@ extern "C" int mdns_joint_commit_bits_dev(mdns_joint *j, const int *d_row_ids, i
 	return joint_commit_dev(j, d_row_ids, M, false, "mdns_joint_commit_bits_dev");
 }
 
-// waits for the mailbox of the last commit (see JointMailbox)
-static bool joint_wait_box(mdns_joint *j, const char *who)
-{
-	if (!j->box_pending) { set_error("%s: no commit to wait for", who); return false; }
-	hipError_t e = hipSuccess;
-	switch (wait_seq(&j->h_box->seq, j->box_seq, &e)) {
-	case Wait::ok: break;
-	case Wait::timeout: set_error("%s: no outcome within MDNS_POLL_TIMEOUT_S", who); return false;
-	case Wait::failed: set_error("%s: the commit failed: %s", who, hipGetErrorString(e)); return false;
-	case Wait::empty: set_error("%s: the commit finished without an outcome", who); return false;
-	}
-	j->box_pending = false;
-	return true;
-}
-
-// the outcome of the last commit from its mailbox: {accepted, status, fill words} -- no copy, no stream synchronisation
+// the outcome of the last commit from its mailbox (JointMailbox), once it is there: {accepted, status, fill words} -- no
+// copy, no stream synchronisation
 static int joint_read_box(mdns_joint *j, int M, int *accepted, unsigned long long *fillbits, const char *who)
 {
-	if (!joint_wait_box(j, who)) return 1;
+	if (!j->box_pending) { set_error("%s: no commit to wait for", who); return 1; }
+	hipError_t e = hipSuccess;
+	if (!wait_ok(wait_seq(&j->h_box->seq, j->box_seq, &e), e, who)) return 1;
+	j->box_pending = false;
 	if (j->h_box->status) { status_error(who, j->h_box->status, j->cap); return 1; }
 	*accepted = j->h_box->accepted;
 	if (fillbits && j->h_box->accepted >= 0) memcpy(fillbits, (const void *) j->h_box->bits, (size_t) ((M + 63) / 64) * 8);
@@ -1068,12 +1080,8 @@ static int joint_stage_and_score(mdns_joint *j, const double *params, int B, dou
 	// candidates and selection travel together: one pinned block, one copy
 	const size_t pbytes = (size_t) B * 24, rbytes = row_ids ? (size_t) M * 4 : 0;
 	const size_t in_bytes = (pbytes + rbytes + 15) & ~(size_t) 15;
-	if (!j->h_pin.fit(in_bytes + result_bytes(j->ndata))) return 1;
-	char *pin = j->h_pin.get();
-	if (pbytes) memcpy(pin, params, pbytes);
-	if (rbytes) memcpy(pin + pbytes, row_ids, rbytes);
-	if (pbytes + rbytes &&
-	    !MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes + rbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	// (behind them, from in_bytes on, the block has room for the outcome that mdns_joint_commit copies back)
+	if (!stage_h2d(j, c, j->params(), params, pbytes, row_ids, rbytes, in_bytes + result_bytes(j->ndata))) return 1;
 	j->d_rows = (int *) ((char *) j->params() + pbytes);
 	j->staged_rows = row_ids != nullptr;
 	j->staged_M = M;
@@ -1254,36 +1262,38 @@ static int next_chunk_flag(mdns_joint *j, Context *c)
 	return ++j->chunk_seq;
 }
 
+// room on every shelf for one more accepted point (shelf_bound: no shelf holds more); false: the shelves could not grow
+static bool room_for_one(mdns_joint *j) { return !(j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0); }
+
+// The accept pass over the dense block d_dense [B][M] (+ d_jitter [B][M] or nullptr), under the next chunk flag: in the
+// stream, and *out = what its commit needs, when this returns true.
+static bool accept_dense(mdns_joint *j, Context *c, int B, int M, const int *d_rows, const double *d_jitter, ChunkScore *out)
+{
+	const int flag = next_chunk_flag(j, c);
+	if (!flag) return false;
+	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
+	                   j->d_dense.get(), d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags.get(), flag, (JointHeader *) j->d_result);
+	*out = {1, B, flag};
+	return true;
+}
+
 // First half of a chunk (B > 0 candidates over a selection of sel_M > 0): candidates, and likelihood noise if any, to the
 // device and the accept pass; *out tells the commit which pass it was.
 static int backend_score(mdns_joint *j, Context *c, const double *params, int B, const double *jitter, ChunkScore *out, const char *who)
 {
 	const int M = j->sel_M;
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
+	if (!room_for_one(j)) return 1;
 	out->B = B;
-	if (j->kind == 1) {
+	if (j->stat == kCurveMarginal) {
 		// templates + K2 into the dense block, jitter, accept flags
-		const size_t pbytes = (size_t) B * j->nparams * sizeof(double), n = (size_t) B * M;
-		if (!j->h_pin.fit(pbytes)) return 1;
-		char *pin = j->h_pin.get();
-		memcpy(pin, params, pbytes);
-		if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+		if (!stage_h2d(j, c, j->params(), params, (size_t) B * j->nparams * sizeof(double))) return 1;
 		const int *d_rows;
 		if (!selection_to_device(j, c, &d_rows)) return 1;
-		if (!j->d_dense.fit(n)) return 1;
-		if (jitter) {
-			if (!j->d_jitter.fit(n)) return 1;
-			// (pageable source: the runtime stages it and returns when the caller's buffer is free)
-			if (!MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-		}
+		if (!j->d_dense.fit((size_t) B * M)) return 1;
+		const double *d_noise = chunk_noise(j, c, jitter, (size_t) B * M);
+		if (jitter && !d_noise) return 1;
 		if (mdns_lines_loglike_batch_dev(j->s, j->params(), B, d_rows, M, j->d_dense.get()) != 0) return 1;
-		const int flag = next_chunk_flag(j, c);
-		if (!flag) return 1;
-		hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-		                   j->d_dense.get(), jitter ? (const double *) j->d_jitter.get() : nullptr, B, M, d_rows, (const double *) j->st.higher,
-		                   j->d_flags.get(), flag, (JointHeader *) j->d_result);
-		out->path = 1; out->flag = flag;
-		return 0;
+		return accept_dense(j, c, B, M, d_rows, d_noise, out) ? 0 : 1;
 	}
 	if (jitter) { set_error("%s: likelihood jitter is not part of the Gaussian-line problem", who); return 1; }
 	const size_t pbytes = (size_t) B * 24;
@@ -1304,10 +1314,7 @@ static int backend_score(mdns_joint *j, Context *c, const double *params, int B,
 		out->path = 2; out->flag = flag;
 		return 0;
 	}
-	if (!j->h_pin.fit(pbytes)) return 1;
-	char *pin = j->h_pin.get();
-	memcpy(pin, params, pbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->params(), pin, pbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!stage_h2d(j, c, j->params(), params, pbytes)) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;
 	if (mdns_joint_score_dev(j, j->params(), B, j->noise_level, d_rows, M) != 0) return 1;
@@ -1350,20 +1357,36 @@ static int backend_fetch(mdns_joint *j, int *accepted, unsigned long long *fillb
 	return 0;
 }
 
+// What every mdns_backend_draw_* entry that scores does first: the state, with *c set, a draw open and B candidates over
+// its selection a valid chunk -- or nullptr: refused, the state as it was.  In this order: no context, no handle or
+// `args` false, i.e. a pointer of the entry's own missing (kNamesNull: with a text); *accepted = -1 from here on where
+// the entry has one; the wrong statistic (how & kTakes...: wrong_stat, with `other`); no draw begun; kBandIdle: a band
+// chunk begun and not collected; sizes.
+static mdns_joint *draw_entry(void *joint, Context **c, bool args, int *accepted, unsigned how, const char *who, const char *other, int B)
+{
+	mdns_joint *j = (mdns_joint *) joint;
+	*c = ctx();
+	if (!*c || !j || !args) {
+		if (how & kNamesNull) set_error("%s: null argument", who);
+		return nullptr;
+	}
+	if (accepted) *accepted = -1;
+	if ((how & (kTakesLine | kTakesTemplate)) && wrong_stat(j, how, who, other)) return nullptr;
+	if (!j->sel_open) { set_error("%s: no draw begun", who); return nullptr; }
+	if ((how & kBandIdle) && j->band_pending) { set_error("%s_begin: the last chunk was not collected", who); return nullptr; }
+	if (!check_draw(j, B, j->sel_M, who)) return nullptr;
+	return j;
+}
+
 // one chunk: score, commit on the accept flags (no votes in between: mdns_backend_draw_score / _commit have those), outcome
 extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B, const double *jitter, int *accepted,
                                        unsigned long long *fillbits, int *nscored)
 {
-	Context *c = ctx();
-	mdns_joint *j = (mdns_joint *) joint;
-	if (!c || !j || !accepted) return 1;
-	*accepted = -1;
-	if (curves_only(j, "mdns_backend_draw_chunk")) return 1;
-	if (!j->sel_open) { set_error("mdns_backend_draw_chunk: no draw begun"); return 1; }
-	const int M = j->sel_M;
-	if (!check_draw(j, B, M, "mdns_backend_draw_chunk")) return 1;
+	Context *c;
+	mdns_joint *j = draw_entry(joint, &c, accepted != nullptr, accepted, kTakesLine | kTakesTemplate, "mdns_backend_draw_chunk", nullptr, B);
+	if (!j) return 1;
 	if (nscored) *nscored = B;
-	if (B == 0 || M == 0) return 0;
+	if (B == 0 || j->sel_M == 0) return 0;
 	ChunkScore sc;
 	if (backend_score(j, c, params, B, jitter, &sc, "mdns_backend_draw_chunk") != 0) return 1;
 	if (backend_commit(j, c, sc, j->d_flags.get(), sc.flag, "mdns_backend_draw_chunk") != 0) return 1;
@@ -1371,85 +1394,81 @@ extern "C" int mdns_backend_draw_chunk(void *joint, const double *params, int B,
 }
 
 // One chunk of a model the caller evaluates (mdns.h: mdns_backend_draw_curves): the candidates arrive as their model
-// curves.  Score into the dense block, then jitter, accept flags, commit and outcome as a chunk of the
-// scale-marginalised likelihood (path 1), for both kinds of state.
+// curves.  Score into the dense block, then jitter, accept flags, commit and outcome as a parameter chunk of the
+// scale-marginalised likelihood (path 1), for a state of any statistic.
 static int draw_curves_dev(mdns_joint *j, Context *c, const double *d_curves, int ldc, int B, const double *d_jitter, int *accepted,
                            unsigned long long *fillbits, const char *who)
 {
 	const int M = j->sel_M;
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
+	if (!room_for_one(j)) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;
 	if (!j->d_dense.fit((size_t) B * M)) return 1;
 	if (!curves_score(j, d_curves, ldc, B, d_rows, M, j->d_dense.get())) return 1;
-	const int flag = next_chunk_flag(j, c);
-	if (!flag) return 1;
-	hipLaunchKernelGGL(k_joint_accept_dense, dim3((M + kBlock - 1) / kBlock, B), dim3(kBlock), 0, c->stream,
-	                   j->d_dense.get(), d_jitter, B, M, d_rows, (const double *) j->st.higher, j->d_flags.get(), flag, (JointHeader *) j->d_result);
-	const ChunkScore sc = {1, B, flag};
-	if (backend_commit(j, c, sc, j->d_flags.get(), flag, who) != 0) return 1;
+	ChunkScore sc;
+	if (!accept_dense(j, c, B, M, d_rows, d_jitter, &sc)) return 1;
+	if (backend_commit(j, c, sc, j->d_flags.get(), sc.flag, who) != 0) return 1;
 	return backend_fetch(j, accepted, fillbits);
 }
 
-// what both forms check first; 1: refused, 0: go on, -1: nothing to score (the outputs say so)
-static int draw_curves_check(mdns_joint *j, Context *c, const void *curves, int ldc, int B, int *accepted, int *nscored, const char *who)
+// what the curve entries check first (draw_entry, then the rows and the curves themselves); *j set: go on; else the entry
+// returns 1: refused, or 0: nothing to score (the outputs say so)
+static int draw_curves_check(void *joint, Context **c, mdns_joint **j, const void *curves, int ldc, int B, int *accepted, int *nscored,
+                             const char *who)
 {
-	if (!c || !j || !accepted) return 1;
-	*accepted = -1;
-	if (!j->sel_open) { set_error("%s: no draw begun", who); return 1; }
-	if (!check_draw(j, B, j->sel_M, who)) return 1;
-	if (ldc < j->s->nx || j->s->nx < 1) { set_error("%s: rows of %d doubles for %d channels", who, ldc, j->s->nx); return 1; }
+	mdns_joint *st = draw_entry(joint, c, accepted != nullptr, accepted, 0, who, nullptr, B);
+	*j = nullptr;
+	if (!st) return 1;
+	if (ldc < st->s->nx || st->s->nx < 1) { set_error("%s: rows of %d doubles for %d channels", who, ldc, st->s->nx); return 1; }
 	if (nscored) *nscored = B;
-	if (B == 0 || j->sel_M == 0) return -1;
+	if (B == 0 || st->sel_M == 0) return 0;
 	if (!curves) { set_error("%s: null curves", who); return 1; }
+	*j = st;
 	return 0;
 }
 
 extern "C" int mdns_backend_draw_curves_dev(void *joint, const double *d_curves, int ldc, int B, const double *d_jitter, int *accepted,
                                             unsigned long long *fillbits, int *nscored)
 {
-	Context *c = ctx();
-	mdns_joint *j = (mdns_joint *) joint;
-	const int rc = draw_curves_check(j, c, d_curves, ldc, B, accepted, nscored, "mdns_backend_draw_curves_dev");
-	if (rc != 0) return rc > 0;
+	Context *c;  mdns_joint *j;
+	const int rc = draw_curves_check(joint, &c, &j, d_curves, ldc, B, accepted, nscored, "mdns_backend_draw_curves_dev");
+	if (!j) return rc;
 	return draw_curves_dev(j, c, d_curves, ldc, B, d_jitter, accepted, fillbits, "mdns_backend_draw_curves_dev");
 }
 
 extern "C" int mdns_backend_draw_curves(void *joint, const double *curves, int B, const double *jitter, int *accepted,
                                         unsigned long long *fillbits, int *nscored)
 {
-	Context *c = ctx();
-	mdns_joint *j = (mdns_joint *) joint;
-	const int nx = j ? j->s->nx : 0;
-	const int rc = draw_curves_check(j, c, curves, nx, B, accepted, nscored, "mdns_backend_draw_curves");
-	if (rc != 0) return rc > 0;
-	const size_t nc = (size_t) B * nx, n = (size_t) B * j->sel_M;
-	// (pageable sources: the runtime stages them and returns when the caller's buffers are free)
+	Context *c;  mdns_joint *j;
+	const int nx = joint ? ((mdns_joint *) joint)->s->nx : 0;
+	const int rc = draw_curves_check(joint, &c, &j, curves, nx, B, accepted, nscored, "mdns_backend_draw_curves");
+	if (!j) return rc;
+	const size_t nc = (size_t) B * nx;
+	// (a pageable source, as chunk_noise's)
 	if (!j->d_curves.fit(nc) ||
 	    !MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, nc * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (jitter && (!j->d_jitter.fit(n) ||
-	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
-	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, jitter ? j->d_jitter.get() : nullptr, accepted, fillbits, "mdns_backend_draw_curves");
+	const double *d_noise = chunk_noise(j, c, jitter, (size_t) B * j->sel_M);
+	if (jitter && !d_noise) return 1;
+	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, d_noise, accepted, fillbits, "mdns_backend_draw_curves");
 }
 
 // the same chunk with the curves made on the device by a table model (mdns.h Part 12): no scoring code of its own
 extern "C" int mdns_backend_draw_table(void *joint, mdns_table *table, const double *params, int B, const double *jitter, int *accepted,
                                        unsigned long long *fillbits, int *nscored)
 {
-	Context *c = ctx();
+	Context *c;
 	mdns_joint *j = (mdns_joint *) joint;
 	const int nx = j ? j->s->nx : 0;
-	if (c && j && accepted) {
+	if (ctx() && j && accepted) {
 		*accepted = -1;
 		if (!table_fits(j, table, "mdns_backend_draw_table")) return 1;
 	}
-	const int rc = draw_curves_check(j, c, params, nx, B, accepted, nscored, "mdns_backend_draw_table");
-	if (rc != 0) return rc > 0;
-	const size_t n = (size_t) B * j->sel_M;
+	const int rc = draw_curves_check(joint, &c, &j, params, nx, B, accepted, nscored, "mdns_backend_draw_table");
+	if (!j) return rc;
 	if (!table_curves(j, c, table, params, B)) return 1;
-	if (jitter && (!j->d_jitter.fit(n) ||
-	               !MDNS_HIP(hipMemcpyAsync(j->d_jitter.get(), jitter, n * sizeof(double), hipMemcpyHostToDevice, c->stream)))) return 1;
-	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, jitter ? j->d_jitter.get() : nullptr, accepted, fillbits, "mdns_backend_draw_table");
+	const double *d_noise = chunk_noise(j, c, jitter, (size_t) B * j->sel_M);
+	if (jitter && !d_noise) return 1;
+	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, d_noise, accepted, fillbits, "mdns_backend_draw_table");
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,
@@ -1459,8 +1478,8 @@ extern "C" int mdns_backend_chunk_size(void *joint, int offered, int M, int hint
 	const mdns_joint *j = (const mdns_joint *) joint;
 	// (a K2 pair reads 16 bytes x 4096 channels against K1's 8 x 200: a twentieth of the pairs,
 	// and each speculative candidate also costs its jitter deviates on the host)
-	const bool muse = j && j->kind == 1;
-	const long long EVAL_BUDGET = muse ? 400000 : 2560000;
+	const bool dense = j && j->stat != kCurveNoise;        // (every chunk of such a state goes through the dense block)
+	const long long EVAL_BUDGET = dense ? 400000 : 2560000;
 	// (over thousands of spectra at least 8: early in a run two candidates in five are accepted and a
 	// chunk of 32 scored 30 of them for nothing -- with 8 a chunk over all 10 000 spectra is two
 	// launches and 22 us instead of five commands and 44.  Over a few hundred spectra at least 32:
@@ -1468,10 +1487,10 @@ extern "C" int mdns_backend_chunk_size(void *joint, int offered, int M, int hint
 	// (K2 with the noise in band form: a speculative candidate costs the host 2 ns per data set and the
 	// device a share of a launch that is latency-bound below ~64 candidates -- round 3, with a Gaussian
 	// deviate per pair on the host, kept these chunks at 4)
-	const int MIN_CHUNK = muse ? 32 : (M > 4096 ? 8 : 32);
+	const int MIN_CHUNK = dense ? 32 : (M > 4096 ? 8 : 32);
 	long long budget = EVAL_BUDGET / (M > 0 ? M : 1);
 	if (budget < MIN_CHUNK) budget = MIN_CHUNK;
-	long long want = (muse ? 8LL : 4LL) * (hint > 0 ? hint : 1);
+	long long want = (dense ? 8LL : 4LL) * (hint > 0 ? hint : 1);
 	if (want < MIN_CHUNK) want = MIN_CHUNK;
 	if (budget > want) budget = want;
 	if (budget > MDNS_JOINT_MAX_BATCH) budget = MDNS_JOINT_MAX_BATCH;
@@ -1507,7 +1526,7 @@ extern "C" int mdns_backend_chain_begin(void *joint, void *region, const mdns_ch
 	// transform and the chunk would take the two-launch path anyway
 	int limit = rq->limit;
 	if (limit > MDNS_JOINT_MAX_BATCH) limit = MDNS_JOINT_MAX_BATCH;
-	const bool full = limit > 0 && j->kind == 0 && !prior->custom && prior->nparams == 3 && prior->jitter_sigma == 0 && M > 0 &&
+	const bool full = limit > 0 && j->stat == kCurveNoise && !prior->custom && prior->nparams == 3 && prior->jitter_sigma == 0 && M > 0 &&
 	                  chunk_fits(j->s, M, limit);
 	ChainSpec spec;
 	memset(&spec, 0, sizeof spec);
@@ -1529,7 +1548,7 @@ extern "C" int mdns_backend_chain_begin(void *joint, void *region, const mdns_ch
 		j->chain_state = 1;
 		return 0;
 	}
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
+	if (!room_for_one(j)) return 1;
 	if (!launch_box_count(rv, spec, j->h_chain_dev, j->d_chain_props.get(), j->d_chain_counts.get(), nullptr)) return 1;
 	JointTrail trail;
 	if (!joint_trail(j, limit, M, &trail)) return 1;
@@ -1559,15 +1578,10 @@ extern "C" int mdns_backend_chain_end(void *joint, void *region, int *counts, in
 	*accepted = -1; *nkept = -1; *B = 0;
 	if (state == 1) {
 		hipError_t e = hipSuccess;
-		switch (wait_seq(&j->h_chain->seq, j->chain_seq, &e)) {
-		case Wait::ok: break;
-		case Wait::timeout: set_error("chain: no membership counts within MDNS_POLL_TIMEOUT_S"); return 1;
-		case Wait::failed: set_error("chain: the membership count failed: %s", hipGetErrorString(e)); return 1;
-		case Wait::empty:
-			(void) hipMemsetAsync(j->d_chain_ticket.get(), 0, sizeof(int), c->stream);
-			set_error("chain: the membership count finished without a result");
-			return 1;
-		}
+		const Wait w = wait_seq(&j->h_chain->seq, j->chain_seq, &e);
+		// (the ticket counter may be anywhere: it is zero between launches)
+		if (w == Wait::empty) (void) hipMemsetAsync(j->d_chain_ticket.get(), 0, sizeof(int), c->stream);
+		if (!wait_ok(w, e, "chain membership count")) return 1;
 		memcpy(counts, (const void *) j->h_chain->counts, (size_t) j->chain_n * sizeof(int));
 		return 0;
 	}
@@ -1600,13 +1614,10 @@ extern "C" int *mdns_joint_votes_dev(mdns_joint *j) { return j ? j->d_votes.get(
 // first half: the score, then one 0 / 1 vote per candidate from its accept flags
 extern "C" int mdns_backend_draw_score(void *joint, const double *params, int B, const double *jitter)
 {
-	Context *c = ctx();
-	mdns_joint *j = (mdns_joint *) joint;
-	if (!c || !j || (!params && B > 0)) return 1;
-	if (curves_only(j, "mdns_backend_draw_score")) return 1;
-	if (!j->sel_open) { set_error("mdns_backend_draw_score: no draw begun"); return 1; }
+	Context *c;
+	mdns_joint *j = draw_entry(joint, &c, params || B <= 0, nullptr, kTakesLine | kTakesTemplate, "mdns_backend_draw_score", nullptr, B);
+	if (!j) return 1;
 	const int M = j->sel_M;
-	if (!check_draw(j, B, M, "mdns_backend_draw_score")) return 1;
 	if (!j->d_votes.get() && !j->d_votes.make(MDNS_JOINT_MAX_BATCH)) return 1;
 	j->half = {0, B, 0};
 	if (!MDNS_HIP(hipMemsetAsync(j->d_votes.get(), 0, (size_t) MDNS_JOINT_MAX_BATCH * sizeof(int), c->stream))) return 1;
@@ -1682,30 +1693,22 @@ static int band_launch(mdns_joint *j, bool filtered)
 // arrived (a look at mapped memory), mdns_backend_draw_band_end waits for it and hands it over
 extern "C" int mdns_backend_draw_band_begin(void *joint, const double *params, int B, const double *bound)
 {
-	Context *c = ctx();
-	mdns_joint *j = (mdns_joint *) joint;
-	if (!c || !j || !params || !bound) { set_error("mdns_backend_draw_band: null argument"); return 1; }
-	if (j->kind != 1) { set_error("mdns_backend_draw_band: a state of the scale-marginalised likelihood is needed"); return 1; }
-	if (curves_only(j, "mdns_backend_draw_band")) return 1;
-	if (!j->sel_open) { set_error("mdns_backend_draw_band: no draw begun"); return 1; }
-	if (j->band_pending) { set_error("mdns_backend_draw_band_begin: the last chunk was not collected"); return 1; }
+	Context *c;
+	mdns_joint *j = draw_entry(joint, &c, params && bound, nullptr, kTakesTemplate | kNamesNull | kBandIdle, "mdns_backend_draw_band",
+	                           "a state of the scale-marginalised likelihood is needed", B);
+	if (!j) return 1;
 	const int M = j->sel_M;
-	if (!check_draw(j, B, M, "mdns_backend_draw_band") || B == 0 || M == 0) return 1;
+	if (B == 0 || M == 0) return 1;
 	if (!j->h_band) {
 		if (!all_or_none(j->band_box.make(sizeof(BandBox)) && j->d_band.make(1, true) && j->d_bound.make(kBandRowAt + j->ndata),
 		                 j->band_box, j->d_band, j->d_bound)) return 1;
 		j->h_band = (BandBox *) j->band_box.get(); j->h_band_dev = (BandBox *) j->band_box.dev();
 	}
-	if (j->shelf_bound + 1 > j->cap && mdns_joint_reserve(j, j->shelf_bound + 1) != 0) return 1;
-	const size_t pbytes = (size_t) B * j->nparams * sizeof(double), bbytes = (size_t) B * sizeof(double), n = (size_t) B * M;
-	if (!j->h_pin.fit(pbytes + bbytes)) return 1;
-	char *pin = j->h_pin.get();
-	memcpy(pin, params, pbytes);
-	memcpy(pin + pbytes, bound, bbytes);
-	if (!MDNS_HIP(hipMemcpyAsync(j->d_bound.get(), pin, pbytes + bbytes, hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!room_for_one(j)) return 1;
+	if (!stage_h2d(j, c, j->d_bound.get(), params, (size_t) B * j->nparams * sizeof(double), bound, (size_t) B * sizeof(double))) return 1;
 	const int *d_rows;
 	if (!selection_to_device(j, c, &d_rows)) return 1;              // (band_launch takes it from the handle)
-	if (!j->d_dense.fit(n)) return 1;
+	if (!j->d_dense.fit((size_t) B * M)) return 1;
 	j->band_B = B;
 	j->trail_valid = false;
 	j->last_B = 0;
@@ -1734,12 +1737,7 @@ extern "C" int mdns_backend_draw_band_end(void *joint, int *status, int *npairs,
 	const int B = j->band_B;
 	for (;;) {
 		hipError_t e = hipSuccess;
-		switch (wait_seq(&j->h_band->seq, j->band_seq, &e)) {
-		case Wait::ok: break;
-		case Wait::timeout: set_error("mdns_backend_draw_band: no outcome within MDNS_POLL_TIMEOUT_S"); return 1;
-		case Wait::failed: set_error("mdns_backend_draw_band: %s", hipGetErrorString(e)); return 1;
-		case Wait::empty: set_error("mdns_backend_draw_band: finished without an outcome"); return 1;
-		}
+		if (!wait_ok(wait_seq(&j->h_band->seq, j->band_seq, &e), e, "mdns_backend_draw_band")) return 1;
 		if (j->band_exact || j->h_band->npairs == 0) break;
 		muse_filter_note(1);
 		if (band_launch(j, false) != 0) return 1;
@@ -1767,7 +1765,7 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 	Context *c = ctx();
 	mdns_joint *j = (mdns_joint *) joint;
 	if (!c || !j || !jitter_row) { set_error("mdns_backend_draw_band_commit: null argument"); return 1; }
-	if (j->kind != 1 || !j->sel_open || j->band_B <= 0 || b < 0 || b >= j->band_B) { set_error("mdns_backend_draw_band_commit: candidate %d of a chunk of %d", b, j->band_B); return 1; }
+	if (j->stat != kCurveMarginal || !j->sel_open || j->band_B <= 0 || b < 0 || b >= j->band_B) { set_error("mdns_backend_draw_band_commit: candidate %d of a chunk of %d", b, j->band_B); return 1; }
 	const int M = j->sel_M, ntiles = (M + 63) / 64;
 	const int *d_rows = selection_rows(j);
 	if (!j->band_exact) {
@@ -1783,10 +1781,7 @@ extern "C" int mdns_backend_draw_band_commit(void *joint, int b, const double *j
 	}
 	j->band_B = 0;
 	double *d_row = j->d_bound.get() + kBandRowAt;
-	if (!j->h_pin.fit((size_t) M * sizeof(double))) return 1;
-	char *pin = j->h_pin.get();
-	memcpy(pin, jitter_row, (size_t) M * sizeof(double));
-	if (!MDNS_HIP(hipMemcpyAsync(d_row, pin, (size_t) M * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
+	if (!stage_h2d(j, c, d_row, jitter_row, (size_t) M * sizeof(double))) return 1;
 	hipLaunchKernelGGL(k_joint_commit_band, dim3((ntiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, c->stream,
 	                   (const double *) j->d_dense.get(), (const double *) d_row, d_rows, M, b, ntiles, j->st, (JointHeader *) j->d_result, result_bits(j));
 	launch_publish(j, c, M);

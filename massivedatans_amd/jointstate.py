@@ -224,6 +224,10 @@ class GaussJointState(object):
         if rc != 0:
             raise _lib.MdnsError("%s failed: %s" % (what, _lib.last_error()))
 
+    def _beats(self, M):
+        """The fill bits the last outcome left in ``_bits``: which of the ``M`` selected data sets the point beats."""
+        return numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+
     def init(self, xs):
         params = _lib.as_f64(self.to_kernel_params(xs))
         if params.shape != (self.nlive, 3):
@@ -295,42 +299,30 @@ class GaussJointState(object):
         if self.via_backend:
             if B == 0 or M == 0:
                 return -1, None, None, B
-            self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.ptr(rows) if rows is not None else None, M),
-                        "mdns_backend_draw_begin")
-            self._check(self._lib.mdns_backend_draw_chunk(self._h, _lib.ptr(params), B,
-                                                          _lib.ptr(jitter) if jitter is not None else None,
-                                                          C.addressof(self._accepted), _lib.ptr(self._bits), C.addressof(self._nscored)),
+            self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows), M), "mdns_backend_draw_begin")
+            self._check(self._lib.mdns_backend_draw_chunk(self._h, _lib.ptr(params), B, _lib.opt(jitter), C.addressof(self._accepted),
+                                                          _lib.ptr(self._bits), C.addressof(self._nscored)),
                         "mdns_backend_draw_chunk")
             self.ncalls += 1
             self.nevals_scored += B * M
             idx = self._accepted.value
             if idx < 0:
                 return -1, None, None, B
-            beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+            beats = self._beats(M)
             self.took(rows, beats)
             return idx, None, beats, B
-        if rows is not None:
-            nmax = int(self.shelf_n[rows].max()) if M else 0
-        else:
-            nmax = int(self.shelf_n.max())
-        if nmax + 1 > self.cap:
-            self._check(self._lib.mdns_joint_reserve(self._h, nmax + 1), "mdns_joint_reserve")
-            self.cap = self._lib.mdns_joint_shelf_cap(self._h)
+        self._reserve_for(rows)
         self._check(self._lib.mdns_joint_draw_gauss(
-            self._h, _lib.ptr(params), B, self.noise_level, _lib.ptr(rows) if rows is not None else None, M,
-            C.byref(self._accepted), _lib.ptr(self._Lrow) if self.fetch_rows else None, _lib.ptr(self._bits)),
+            self._h, _lib.ptr(params), B, self.noise_level, _lib.opt(rows), M,
+            C.byref(self._accepted), _lib.opt(self._Lrow if self.fetch_rows else None), _lib.ptr(self._bits)),
             "mdns_joint_draw_gauss")
         self.ncalls += 1
+        self.nevals_scored += B * M
         idx = self._accepted.value
         if idx < 0:
-            self.nevals_scored += B * M
             return -1, None, None, B
-        self.nevals_scored += B * M
-        beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
-        if rows is None:
-            self.shelf_n[beats] += 1
-        else:
-            self.shelf_n[rows[beats]] += 1
+        beats = self._beats(M)
+        self.took(rows, beats)
         return idx, (self._Lrow[:M].copy() if self.fetch_rows else None), beats, B
 
     # the two halves of a chunk through the entry points a native constrainer uses (include/mdns.h:
@@ -351,10 +343,8 @@ class GaussJointState(object):
             jitter = _lib.as_f64(jitter)
             if jitter.shape != (B, M):
                 raise ValueError("jitter must be [B, M]")
-        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.ptr(rows) if rows is not None and M else None, M),
-                    "mdns_backend_draw_begin")
-        self._check(self._lib.mdns_backend_draw_score(self._h, _lib.ptr(params) if B else None, B,
-                                                      _lib.ptr(jitter) if jitter is not None and B * M else None),
+        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows if M else None), M), "mdns_backend_draw_begin")
+        self._check(self._lib.mdns_backend_draw_score(self._h, _lib.opt(params if B else None), B, _lib.opt(jitter if B * M else None)),
                     "mdns_backend_draw_score")
         self._half = (rows, M, B)
         self.nevals_scored += B * M
@@ -384,17 +374,18 @@ class GaussJointState(object):
         idx = self._accepted.value
         if idx < 0 or M == 0:
             return idx, numpy.zeros(M, dtype=bool)
-        beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+        beats = self._beats(M)
         self.took(rows, beats)
         return idx, beats
 
-    # the two halves of draw() (include/mdns.h: mdns_joint_score / mdns_joint_commit)
     def _reserve_for(self, rows):
+        """Room on the device's shelves for one more point on the fullest shelf of ``rows`` (by the mirror of the sizes)."""
         nmax = int(self.shelf_n.max()) if rows is None else (int(self.shelf_n[rows].max()) if len(rows) else 0)
         if nmax + 1 > self.cap:
             self._check(self._lib.mdns_joint_reserve(self._h, nmax + 1), "mdns_joint_reserve")
             self.cap = self._lib.mdns_joint_shelf_cap(self._h)
 
+    # the two halves of draw() (include/mdns.h: mdns_joint_score / mdns_joint_commit)
     def score(self, xs, rows):
         """Scores the chunk; the accept flags stay on the device (``flags`` / ``set_flags`` /
         ``flags_address`` reach them)."""
@@ -412,8 +403,8 @@ class GaussJointState(object):
         self._reserve_for(rows)
         params = _lib.as_f64(params) if B else numpy.zeros((0, 3))
         self._scored_rows, self._scored_B = rows, B
-        self._check(self._lib.mdns_joint_score(self._h, _lib.ptr(params), B, self.noise_level,
-                                               _lib.ptr(rows) if rows is not None and M else None, M), "mdns_joint_score")
+        self._check(self._lib.mdns_joint_score(self._h, _lib.ptr(params), B, self.noise_level, _lib.opt(rows if M else None), M),
+                    "mdns_joint_score")
         self.nevals_scored += B * M
         self.ncalls += 1
 
@@ -435,19 +426,15 @@ class GaussJointState(object):
         """The first flagged candidate (``idx`` is only checked against it) is the accepted point."""
         rows = self._scored_rows
         M = self.ndata if rows is None else len(rows)
-        self._check(self._lib.mdns_joint_commit(self._h, C.byref(self._accepted),
-                                                _lib.ptr(self._Lrow) if self.fetch_rows else None, _lib.ptr(self._bits)),
-                    "mdns_joint_commit")
+        self._check(self._lib.mdns_joint_commit(self._h, C.byref(self._accepted), _lib.opt(self._Lrow if self.fetch_rows else None),
+                                                _lib.ptr(self._bits)), "mdns_joint_commit")
         got = self._accepted.value
         if M == 0:
             return (numpy.zeros(0) if self.fetch_rows else None), numpy.zeros(0, dtype=bool)
         if got < 0 or (idx is not None and got != idx):
             raise _lib.MdnsError("mdns_joint_commit accepted candidate %d, expected %s" % (got, idx))
-        beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
-        if rows is None:
-            self.shelf_n[beats] += 1
-        else:
-            self.shelf_n[rows[beats]] += 1
+        beats = self._beats(M)
+        self.took(rows, beats)
         return (self._Lrow[:M].copy() if self.fetch_rows else None), beats
 
     def advance(self):
@@ -489,8 +476,7 @@ class MuseJointState(GaussJointState):
             jitter = _lib.as_f64(jitter)
             if jitter.shape != (self.nlive, self.ndata):
                 raise ValueError("jitter must be [nlive, ndata]")
-        self._check(self._lib.mdns_joint_init_muse3(self._h, _lib.ptr(params), _lib.ptr(jitter) if jitter is not None else None),
-                    "mdns_joint_init_muse3")
+        self._check(self._lib.mdns_joint_init_muse3(self._h, _lib.ptr(params), _lib.opt(jitter)), "mdns_joint_init_muse3")
         self.shelf_n[:] = 0
         self.nevals_scored += self.nlive * self.ndata
         self.ncalls += 1
@@ -572,15 +558,14 @@ class CurveJointState(GaussJointState):
                 raise ValueError("jitter must be [nlive, ndata]")
         if self.table is not None:
             xs = _lib.as_f64(xs)
-            self._check(self._lib.mdns_joint_init_table(self._h, self.table.handle, _lib.ptr(xs), self.noise_level,
-                                                        _lib.ptr(jitter) if jitter is not None else None), "mdns_joint_init_table")
+            self._check(self._lib.mdns_joint_init_table(self._h, self.table.handle, _lib.ptr(xs), self.noise_level, _lib.opt(jitter)),
+                        "mdns_joint_init_table")
         else:
             address, ld, on_device, keep = self._curves(xs)
             if on_device:                                     # (once per run: through the host)
                 keep = _lib.as_f64(keep.cpu().numpy())
                 address = _lib.ptr(keep)
-            self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.ptr(jitter) if jitter is not None else None),
-                        "mdns_joint_init_curves")
+            self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.opt(jitter)), "mdns_joint_init_curves")
         self.shelf_n[:] = 0
         self.nevals_scored += self.nlive * self.ndata
         self.ncalls += 1
@@ -620,26 +605,23 @@ class CurveJointState(GaussJointState):
             jitter = _lib.as_f64(jitter)[:B]
             if jitter.shape != (B, M):
                 raise ValueError("jitter must be [B, M]")
-        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.ptr(rows) if rows is not None else None, M),
-                    "mdns_backend_draw_begin")
+        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows), M), "mdns_backend_draw_begin")
         out = (C.addressof(self._accepted), _lib.ptr(self._bits), C.addressof(self._nscored))
         if self.table is not None:
-            self._check(self._lib.mdns_backend_draw_table(self._h, self.table.handle, _lib.ptr(params), B,
-                                                          _lib.ptr(jitter) if jitter is not None else None, *out),
+            self._check(self._lib.mdns_backend_draw_table(self._h, self.table.handle, _lib.ptr(params), B, _lib.opt(jitter), *out),
                         "mdns_backend_draw_table")
         elif on_device:
             self._check(self._lib.mdns_backend_draw_curves_dev(self._h, address, ld, B, self._jitter_to_device(jitter), *out),
                         "mdns_backend_draw_curves_dev")
         else:
-            self._check(self._lib.mdns_backend_draw_curves(self._h, address, B, _lib.ptr(jitter) if jitter is not None else None, *out),
-                        "mdns_backend_draw_curves")
+            self._check(self._lib.mdns_backend_draw_curves(self._h, address, B, _lib.opt(jitter), *out), "mdns_backend_draw_curves")
         del keep
         self.ncalls += 1
         self.nevals_scored += B * M
         idx = self._accepted.value
         if idx < 0:
             return -1, None, None, B
-        beats = numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+        beats = self._beats(M)
         return idx, None, beats, B
 
     def _jitter_to_device(self, jitter):

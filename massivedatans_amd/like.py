@@ -91,7 +91,7 @@ class _Spectra(object):
         out = np.empty((B, M))
         if B and M:
             args = [self._h, _lib.ptr(params), B] + list(extra) + \
-                   [_lib.ptr(rows) if rows is not None else None, M, _lib.ptr(out)]
+                   [_lib.opt(rows), M, _lib.ptr(out)]
             _lib.check(fn(*args), name)
         return out
 
@@ -266,7 +266,7 @@ class CountSpectra(_Spectra):
         if exposure is not None or masked.any():              # one spectrum per row, as the handle keeps them
             rows = np.ascontiguousarray(e.T if channel_major else e)
         offsets = np.ascontiguousarray(offsets)
-        rc = self._lib.mdns_spectra_set_counts(self._h, _lib.ptr(rows) if rows is not None else None, _lib.ptr(offsets))
+        rc = self._lib.mdns_spectra_set_counts(self._h, _lib.opt(rows), _lib.ptr(offsets))
         if rc != 0:
             self.close()
             _lib.check(rc, "mdns_spectra_set_counts")
@@ -297,7 +297,7 @@ class CountSpectra(_Spectra):
         B = len(curves)
         f = np.empty((B, M, self.nx))
         if B and M:
-            _lib.check(self._lib.mdns_curve_background_batch(self._h, _lib.ptr(curves), B, _lib.ptr(rows) if rows is not None else None,
+            _lib.check(self._lib.mdns_curve_background_batch(self._h, _lib.ptr(curves), B, _lib.opt(rows),
                                                              M, _lib.ptr(f)), "mdns_curve_background_batch")
         return f
 
@@ -340,7 +340,7 @@ class MuseSpectra(_Spectra):
         B = len(ypred)
         L, s, coef = np.empty((B, M)), np.empty((B, M)), np.empty((B, M, self.continuum))
         if B and M:
-            _lib.check(self._lib.mdns_muse_continuum_fit_batch(self._h, _lib.ptr(ypred), B, _lib.ptr(rows) if rows is not None else None,
+            _lib.check(self._lib.mdns_muse_continuum_fit_batch(self._h, _lib.ptr(ypred), B, _lib.opt(rows),
                                                                M, _lib.ptr(L), _lib.ptr(s), _lib.ptr(coef)),
                        "mdns_muse_continuum_fit_batch")
         return L, s, coef
