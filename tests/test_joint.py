@@ -19,7 +19,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("fetch_rows", [True, False, "backend"])
 @pytest.mark.parametrize("ndata,nlive,nx", [(1, 5, 200), (7, 9, 33), (100, 50, 200), (1000, 40, 200), (4100, 25, 64), (700, 30, 201),
-                                           (90, 150, 48)])        # more live points than a data set's sixteen lanes hold in registers (128)
+                                           (90, 150, 48),         # more live points than a data set's sixteen lanes hold in registers (128)
+                                           # the commit kernels unroll shelf_append by 16, 25 and 8 live points: at and around those
+                                           (7, 15, 33), (7, 16, 33), (7, 17, 33), (7, 26, 33)])
 def test_joint_state_equals_its_numpy_statement(ndata, nlive, nx, fetch_rows):
     """fetch_rows=False: the outcome of a draw -- index, fill bits -- arrives in mapped host memory
     the commit kernel writes (mdns.h, mdns_joint_fetch), the likelihood row stays on the device;
@@ -104,8 +106,10 @@ def test_shelves_grow_past_their_first_capacity():
 def test_long_shelves_purge_and_threshold():
     """Shelves longer than the 128 entries a data set's sixteen lanes hold in registers
     (k_joint_prepare): more than 128 accepted points waiting, then iterations -- every one replaces the worst
-    live point by the head of the shelf, purges what no longer beats the new minimum (entries move
-    down, in order) and selects the threshold among live + shelf -- against the numpy statement."""
+    live point by the head of the shelf, runs the purge and selects the threshold among live + shelf -- against the
+    numpy statement.  NOTHING is dropped here: in a consistent run the smallest shelf entry stays above the live
+    minimum, so this is the purge that keeps every entry where it is.  The purge that drops entries and moves the
+    survivors down is tested on planted states in test_joint_planted.py."""
     ndata, nlive = 70, 12
     rng = np.random.RandomState(5)
     data = gen.nothing(ndata)
