@@ -953,7 +953,7 @@ int mdns_curve_background_batch_dev(mdns_spectra *s, const double *d_curves, int
                                     double *d_fout);
 
 /* ------------------------------------------------------------------------------------------
- * Part 12 -- a MODEL on the device: a tabulated template grid (csrc/mdns_table.hip, k_table_curves).
+ * Part 12 -- a MODEL on the device: a tabulated template grid (csrc/mdns_table.hip, k_table_curves, k_table_los_*).
  *
  * The model of the reference's real workload (musefuse.py:222-284) and of X-ray table models: templates tabulated over
  * a few parameters, interpolated multilinearly, resampled at x / (1 + z) with numpy.interp's end rules, times an
@@ -997,18 +997,62 @@ int mdns_curve_background_batch_dev(mdns_spectra *s, const double *d_curves, int
  * whose nx is not the spectra's.  mdns_joint_init_table: mdns_joint_init_curves with the live points' curves made from
  * params f64[nlive][ndim] in the same way.
  *
- * Not covered: more than MDNS_TABLE_MAX_AXES axes, interpolation other than linear, line-of-sight broadening or
- * extinction (fold them into the table, or use a model of your own), sharded runs, the chained first batch.
+ * LINE-OF-SIGHT EFFECTS (mdns_table_create_los).  The reference's model has two more parameters of this kind
+ * (musefuse.py:222-284): an attenuation 10 ** (c(lambda) * EBV) of the rest-frame template, and a Gaussian velocity
+ * broadening of it before the resampling.  MDNS_TABLE_EXTINCTION adds the parameter E, MDNS_TABLE_BROADEN the parameter
+ * s (the velocity dispersion sigma_v / c, dimensionless); the candidate's row is (p_1 .. p_d [, z] [, E] [, s] [, A]),
+ * ndim = d + the flags set.  ext f64[nw], finite, required with MDNS_TABLE_EXTINCTION: the exponent per unit E at each
+ * template knot (the caller passes e.g. -0.4 k(lambda)).  MDNS_TABLE_BROADEN requires grid[0] > 0.  10 ** v below is
+ * pow10_dd of csrc/mdns_pow10.h, one faithful rounding that host and device compute identically, so this stays a chain
+ * of single rounded fp64 operations (the fma() calls inside pow10_dd are part of that function's definition).
+ *
+ * With neither new flag nothing changes: the statement above, its kernel and its bits.  With either, cell, f_a, w_c,
+ * u_j, k_j, t_j and the clamps are as above and the value is blend, attenuate, broaden, interpolate:
+ *
+ *   blend     for a template knot m:  S_m = 0, then for c ascending  S_m = S_m + w_c * T_c[m]
+ *   attenuate (MDNS_TABLE_EXTINCTION)  q = ext[m] * E, clamped to [-299, 299] by the same comparisons;
+ *             S_m = S_m * pow10_dd(q)
+ *   broaden   (MDNS_TABLE_BROADEN)  widths, made once at creation:  D_n = (grid[n + 1] - grid[n - 1]) * 0.5 inside,
+ *             D_0 = (grid[1] - grid[0]) * 0.5,  D_{nw-1} = (grid[nw - 1] - grid[nw - 2]) * 0.5.
+ *             s == 0:  R_m = S_m exactly.   s > 0:  d_mn = ((grid[n] - grid[m]) / grid[m]) / s;  the window of m is the
+ *             contiguous run of n around m with |d_mn| <= MDNS_TABLE_BROADEN_CUT (d_mn is monotone in n and d_mm = 0);
+ *             K_n = pow10_dd((MDNS_TABLE_BROADEN_C * d_mn) * d_mn) * D_n;  num = 0, den = 0, then for n ascending over
+ *             the window  num = num + S_n * K_n,  den = den + K_n;  R_m = num / den.  A window cut by an end of the
+ *             grid normalises over what is there.  Without the flag R = S.
+ *   value     curve[b][j] = R_{k_j} + t_j * (R_{k_j + 1} - R_{k_j}), times A with MDNS_TABLE_AMPLITUDE (A * value)
+ *
+ * The divisions of d_mn are divisions (no reciprocal).  The window has NO cap: a large s on a dense grid costs O(nw)
+ * per template knot and O(nw^2) per candidate.  A NaN in any parameter makes the whole row NaN, as above; so does an E
+ * that is not finite, and an s that is not finite or negative; no other row is touched.  A value depends on its
+ * candidate and channel only -- not on B, the candidate's place in the batch, ldc, the entry point, or what the handle
+ * computed before.  Extinction alone is one gather kernel of k_table_curves' shape (k_table_los_gather: a channel needs
+ * S at its two knots only); with broadening three kernels follow each other on the library stream (k_table_los_blend
+ * S[B][nw], k_table_los_broaden R[B][nw], k_table_los_resample), S and R grow-only blocks of the handle: a growth the
+ * device refuses fails that call and leaves the handle usable.
+ *
+ * mdns_table_create_los: mdns_table_create with the two flags and ext (NULL without MDNS_TABLE_EXTINCTION); the same
+ * rules, all or none, looked for in the host arrays first, and beside them: ext null with the flag, ext[i] not finite,
+ * grid[0] <= 0 with MDNS_TABLE_BROADEN.  mdns_table_create takes neither new flag (flags=4: unknown bits).  Every other
+ * entry of this part takes the handles of both.
+ *
+ * Not covered: more than MDNS_TABLE_MAX_AXES axes, interpolation other than linear, a broadening kernel other than a
+ * Gaussian, extinction laws with more than one parameter, sharded runs, the chained first batch.
  * ------------------------------------------------------------------------------------------ */
 #define MDNS_TABLE_MAX_AXES 4
 #define MDNS_TABLE_MAX_NX (1 << 20)            /* channels of x at most                                  */
 #define MDNS_TABLE_MAX_ELEMS 2147483647LL      /* table values at most (and knots of all axes together)   */
-#define MDNS_TABLE_TILE 256                    /* channels per workgroup of k_table_curves                */
+#define MDNS_TABLE_TILE 256                    /* channels (template knots) per workgroup of the kernels  */
 #define MDNS_TABLE_REDSHIFT 1
 #define MDNS_TABLE_AMPLITUDE 2
+#define MDNS_TABLE_EXTINCTION 4
+#define MDNS_TABLE_BROADEN 8
+#define MDNS_TABLE_BROADEN_CUT 5.0             /* the Gaussian's window: |d_mn| <= this many sigmas       */
+#define MDNS_TABLE_BROADEN_C (-0x1.bcb7b1526e50ep-3) /* the double nearest to -0.5 log10(e)                */
 typedef struct mdns_table mdns_table;
 mdns_table *mdns_table_create(const double *x, int nx, int d, const int *n, const double *axes, int nw, const double *grid,
                               const double *table, int flags);
+mdns_table *mdns_table_create_los(const double *x, int nx, int d, const int *n, const double *axes, int nw, const double *grid,
+                                  const double *table, int flags, const double *ext);
 void mdns_table_destroy(mdns_table *t);
 int mdns_table_nparams(const mdns_table *t);
 int mdns_table_nx(const mdns_table *t);

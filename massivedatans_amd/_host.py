@@ -1,7 +1,7 @@
-"""ctypes binding of ``libmdns_host.so`` (csrc/host_groups.c, csrc/host_rng.c): plain C helpers
-of the HOST orchestration -- integer graph work and the two scalar-heavy RNG / pow spots.  No
-GPU code.  Optional: every user has a Python statement of the same thing to fall back on (and
-to be tested against)."""
+"""ctypes binding of ``libmdns_host.so`` (csrc/host_groups.c, csrc/host_rng.c, csrc/host_pow10.cpp):
+plain C helpers of the HOST orchestration -- integer graph work and the two scalar-heavy RNG / pow
+spots.  No GPU code.  Optional: every user has a Python statement of the same thing to fall back on
+(and to be tested against) -- but for ``pow10_dd``, which IS the statement of the device's 10 ** v."""
 import ctypes
 import os
 
@@ -41,6 +41,9 @@ def lib():
             L.mdns_host_minmax.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
             L.mdns_host_pow10.restype = None
             L.mdns_host_pow10.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+            if hasattr(L, "mdns_host_pow10_dd"):      # (csrc/host_pow10.cpp; a build of the other sources alone stays usable)
+                L.mdns_host_pow10_dd.restype = None
+                L.mdns_host_pow10_dd.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
             _LIB = L
         except (OSError, AttributeError):
             _LIB = False
@@ -134,4 +137,19 @@ def pow10(values):
         return numpy.array([10 ** v for v in values.ravel()]).reshape(values.shape)
     out = numpy.empty_like(values)
     L.mdns_host_pow10(values.ctypes.data, values.size, out.ctypes.data)
+    return out
+
+
+def pow10_dd(values):
+    """``10 ** values`` by ``pow10_dd`` of csrc/mdns_pow10.h, the function the device computes bit for bit
+    (csrc/host_pow10.cpp).  There is no Python statement of it to fall back on: without the library this
+    raises."""
+    L = lib()
+    if L is None or not hasattr(L, "mdns_host_pow10_dd"):
+        raise RuntimeError("pow10_dd needs libmdns_host.so with csrc/host_pow10.cpp, which has not been built "
+                           "(make -C massivedatans_amd/csrc)")
+    values = numpy.ascontiguousarray(values, dtype=numpy.float64)
+    out = numpy.empty_like(values)
+    if values.size:
+        L.mdns_host_pow10_dd(values.ctypes.data, values.size, out.ctypes.data)
     return out

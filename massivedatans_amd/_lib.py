@@ -63,7 +63,7 @@ ABI_SYMBOLS = (
     "mdns_spectra_set_background", "mdns_spectra_background", "mdns_curve_wstat_batch", "mdns_curve_wstat_batch_dev",
     "mdns_curve_background_batch", "mdns_curve_background_batch_dev",
     # Part 12: a tabulated template grid as the model, evaluated on the device (csrc/mdns_table.hip k_table_curves)
-    "mdns_table_create", "mdns_table_destroy", "mdns_table_nparams", "mdns_table_nx", "mdns_table_curves_batch",
+    "mdns_table_create", "mdns_table_create_los", "mdns_table_destroy", "mdns_table_nparams", "mdns_table_nx", "mdns_table_curves_batch",
     "mdns_table_curves_batch_dev", "mdns_backend_draw_table", "mdns_joint_init_table",
 )
 
@@ -82,11 +82,15 @@ HOST_ABI_SYMBOLS = (
 
 #: mdns.h MDNS_JOINT_MAX_BATCH
 JOINT_MAX_BATCH = 1024
-#: mdns.h Part 12: MDNS_TABLE_MAX_AXES, MDNS_TABLE_TILE, MDNS_TABLE_REDSHIFT, MDNS_TABLE_AMPLITUDE
+#: mdns.h Part 12: MDNS_TABLE_MAX_AXES, MDNS_TABLE_TILE, the four flags, MDNS_TABLE_BROADEN_CUT, MDNS_TABLE_BROADEN_C
 TABLE_MAX_AXES = 4
 TABLE_TILE = 256
 TABLE_REDSHIFT = 1
 TABLE_AMPLITUDE = 2
+TABLE_EXTINCTION = 4
+TABLE_BROADEN = 8
+TABLE_BROADEN_CUT = 5.0
+TABLE_BROADEN_C = float.fromhex("-0x1.bcb7b1526e50ep-3")      # the double nearest to -0.5 log10(e)
 
 
 class MdnsError(RuntimeError):
@@ -244,6 +248,7 @@ def _declare(lib):
         "mdns_curve_background_batch": (i, [vp, vp, i, vp, i, vp]),
         "mdns_curve_background_batch_dev": (i, [vp, vp, i, i, vp, i, vp]),
         "mdns_table_create": (vp, [vp, i, i, vp, vp, i, vp, vp, i]),
+        "mdns_table_create_los": (vp, [vp, i, i, vp, vp, i, vp, vp, i, vp]),
         "mdns_table_destroy": (None, [vp]),
         "mdns_table_nparams": (i, [vp]),
         "mdns_table_nx": (i, [vp]),

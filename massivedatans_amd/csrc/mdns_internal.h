@@ -239,23 +239,28 @@ struct mdns_table {
 	int nx = 0;         // channels of the abscissa the curves are made on
 	int d = 0;          // grid axes (1 .. MDNS_TABLE_MAX_AXES)
 	int nw = 0;         // knots of the templates' own abscissa
-	int ndim = 0;       // parameters per candidate: d [+ z] [+ A]
-	int flags = 0;      // MDNS_TABLE_REDSHIFT | MDNS_TABLE_AMPLITUDE
+	int ndim = 0;       // parameters per candidate: d [+ z] [+ E] [+ s] [+ A]
+	int flags = 0;      // MDNS_TABLE_REDSHIFT | MDNS_TABLE_AMPLITUDE | MDNS_TABLE_EXTINCTION | MDNS_TABLE_BROADEN
 	int n[MDNS_TABLE_MAX_AXES] = {};
 	// resident blocks, made once at their exact size
 	mdns::DeviceBuffer<double> d_x;       // [nx]
 	mdns::DeviceBuffer<double> d_axes;    // the axes one after the other
 	mdns::DeviceBuffer<double> d_grid;    // [nw]
 	mdns::DeviceBuffer<double> d_table;   // [n_1] .. [n_d][nw]
+	mdns::DeviceBuffer<double> d_ext;     // [nw] exponent per unit E (MDNS_TABLE_EXTINCTION), or empty
+	mdns::DeviceBuffer<double> d_delta;   // [nw] quadrature widths of the knots (MDNS_TABLE_BROADEN), or empty
 	// grow-only scratch of the host-pointer batch call
 	mdns::DeviceBuffer<double> d_params, d_out;
+	// grow-only scratch of the broadening route: the blended and the broadened templates [B][nw]
+	mdns::DeviceBuffer<double> d_S, d_R;
 };
 
 namespace mdns {
 
 // the table model's curves for d_params [B][t->ndim] -> d_out [B][ldc] (ldc >= t->nx; the padding is not touched),
-// asynchronous on ctx()->stream (mdns_table.hip, k_table_curves)
-bool launch_table_curves(const mdns_table *t, const double *d_params, int B, double *d_out, int ldc);
+// asynchronous on ctx()->stream (mdns_table.hip: k_table_curves, or the k_table_los_* route the handle's flags select,
+// which may grow the handle's scratch)
+bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc);
 
 // model row stride for nx channels: multiple of 512 doubles (zero padded), so that every
 // lane / thread of the row kernels can load its channel pair without a bounds test

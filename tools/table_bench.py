@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """What the table model (include/mdns.h Part 12, csrc/mdns_table.hip) costs and saves, measured on the GPU:
 
-    python tools/table_bench.py [--small] [--processes N] [--out profiles/table_bench.jsonl]
+    python tools/table_bench.py [kernel] [chunk] [run] [los] [--small] [--processes N] [--out profiles/table_bench.jsonl]
 
-Three parts, each in fresh child processes (``--child PART``; torch is imported first there: one HIP runtime per
+Four parts, each in fresh child processes (``--child PART``; torch is imported first there: one HIP runtime per
 process), the competitors of a part alternating inside every round of a process; the parent prints and appends one JSON
 line per part with the median over all rounds of all processes and the spread (min, max) beside it.
 
@@ -21,6 +21,14 @@ chunk   ONE draw chunk of 256 candidates x 10 000 spectra x 200 channels from th
         state never changes.
 run     wall time of sample.run_model over 64 spectra x 200 channels with the TableModel against the same seed with
         its statement as a numpy model (identical results are asserted).
+
+los     the line-of-sight routes (mdns_table_create_los) on the shapes above -- the 20 x 20 x 10 x 2000 table, B = 256,
+        nx = 200, 10 000 spectra: ``plain`` (z, A: k_table_curves), ``E`` (+ extinction: k_table_los_gather), ``Es8`` and
+        ``Es64`` (+ broadening with windows of about +-8 and +-64 knots at the middle of the grid: the three k_table_los
+        stages).  ``kernel_us``: the curves alone, as in ``kernel`` (events around 64 calls over 32 batches);
+        ``chunk_us``: one draw chunk as in ``chunk``, and beside the three new routes the same model through the Python
+        route (its numpy statement as the model: ``numpy_E``, ``numpy_Es8``, ``numpy_Es64``).  ``windows``: the knots in
+        the window of the middle knot, and in the longest window of the grid.
 
 Synthetic data from seeds.  There is no CPU path: without a device every part fails."""
 import json
@@ -200,7 +208,85 @@ def child_run(small, rounds):
             "ms": seconds}
 
 
-CHILDREN = {"kernel": (child_kernel, 10), "chunk": (child_chunk, 15), "run": (child_run, 2)}
+def child_los(small, rounds):
+    import numpy as np
+    from massivedatans_amd import _lib, jointstate
+    from massivedatans_amd.like import GaussLineSpectra
+    from massivedatans_amd.tablemodel import BROADEN_CUT, TableModel
+    lib = _lib.require_device()
+    ndata, B, nlive, nx, calls, SETS = (500, 32, 20, 200, 8, 4) if small else (10000, 256, 100, 200, 64, 32)
+    plain = big_model([6, 6, 4] if small else [20, 20, 10], 500 if small else 2000, seed=5)
+    g = plain.grid
+    ext = -0.4 * (3.1 * (g[0] / g) ** 1.3 - 0.8)
+    with_e = TableModel(plain.axes, g, plain.table, redshift=True, amplitude=True, extinction=ext)
+    with_es = TableModel(plain.axes, g, plain.table, redshift=True, amplitude=True, extinction=ext, broadening=True)
+    mid = len(g) // 2
+    step = (g[-1] - g[0]) / (len(g) - 1) / g[mid]                          # the mean spacing, relative, at the middle of the grid
+    x = np.linspace(g[0] * 1.5, g[-1], nx)
+    rng = np.random.RandomState(2)
+    truth = params_of(plain, rng, ndata, 1.0)
+    y = np.ascontiguousarray(plain.statement(x, truth).T + 0.05 * rng.normal(size=(nx, ndata)))
+    spectra = GaussLineSpectra(x, y, noise_level=0.05)
+    live = params_of(plain, rng, nlive, 1.0)
+
+    def widen(xs, E, s):
+        """(p, z, A) rows as (p, z [, E] [, s], A) rows"""
+        cols = [xs[:, :-1]] + ([np.full((len(xs), 1), E)] if E is not None else []) + ([np.full((len(xs), 1), s)] if s is not None else [])
+        return np.ascontiguousarray(np.hstack(cols + [xs[:, -1:]]))
+    routes = {"plain": (plain, None, None), "E": (with_e, 0.3, None), "Es8": (with_es, 0.3, 8 * step / BROADEN_CUT),
+              "Es64": (with_es, 0.3, 64 * step / BROADEN_CUT)}
+    tables = {id(m): m.bind(x) for m, _, _ in routes.values()}
+    many = params_of(plain, np.random.RandomState(1), SETS * B, 1.0)
+    bad = params_of(plain, rng, B, 50.0)                                   # fifty times too bright: nobody takes them
+    d_o = lib.mdns_dev_alloc(B * nx * 8)
+    ev = (lib.mdns_event_create(), lib.mdns_event_create())
+    state, windows = {}, {}
+    for name, (tm, E, s) in routes.items():
+        xs = widen(many, E, s)
+        d_p = lib.mdns_dev_alloc(xs.nbytes)
+        _lib.check(lib.mdns_h2d(d_p, _lib.ptr(xs), xs.nbytes), "h2d")
+        js = jointstate.CurveJointState(spectra, nlive, None, table=tables[id(tm)])
+        js.init(widen(live, E, s))
+        js.prepare()
+        state[name] = (tm, tables[id(tm)], d_p, js, widen(bad, E, s))
+        if s is not None:
+            inside = np.abs((g[None, :] - g[:, None]) / g[:, None] / s) <= BROADEN_CUT
+            windows[name] = {"knots_at_middle": int(inside[mid].sum()), "knots_longest": int(inside.sum(axis=1).max())}
+        if name != "plain":
+            fn = lambda xs, _tm=tm: _tm.statement(x, xs)
+            js2 = jointstate.CurveJointState(spectra, nlive, fn, ndim=tm.ndim)
+            js2.init(widen(live, E, s))
+            js2.prepare()
+            state["numpy_" + name] = (tm, None, None, js2, widen(bad, E, s))
+    kernel_us, chunk_us = {n: [] for n in routes}, {n: [] for n in state}
+    # the Python routes first, then the device routes one after the other behind an untimed chunk: a device route
+    # timed right after seconds of numpy would be timed on a GPU that had gone idle
+    order = sorted(state, key=lambda name: not name.startswith("numpy_"))
+    for r in range(rounds + 2):                                            # (two warm-up rounds)
+        for name in order:
+            tm, table, d_p, js, xs_bad = state[name]
+            if name == "plain":
+                js.draw_params(xs_bad, None)
+            if table is not None:
+                _lib.check(lib.mdns_event_record(ev[0]), "event")
+                for i in range(calls):
+                    _lib.check(lib.mdns_table_curves_batch_dev(table.handle, d_p + (i % SETS) * B * tm.ndim * 8, B, d_o, nx),
+                               "mdns_table_curves_batch_dev")
+                _lib.check(lib.mdns_event_record(ev[1]), "event")
+                t = lib.mdns_event_elapsed_ms(ev[0], ev[1]) * 1e3 / calls
+                if r >= 2:
+                    kernel_us[name].append(t)
+            t0 = time.perf_counter()
+            with np.errstate(all="ignore"):
+                idx = js.draw_params(xs_bad, None)[0]
+            t = (time.perf_counter() - t0) * 1e6
+            assert idx == -1
+            if r >= 2:
+                chunk_us[name].append(t)
+    return {"shape": "%d x %d x %d, %d grid knots" % (B, ndata, nx, len(g)), "windows": windows, "kernel_us": kernel_us, "chunk_us": chunk_us}
+
+
+CHILDREN = {"kernel": (child_kernel, 10), "chunk": (child_chunk, 15), "run": (child_run, 2), "los": (child_los, 5)}
 
 
 # ------------------------------------------------------------------------------------------ the parent ---------
@@ -238,6 +324,10 @@ def main():
                 line[name + "_us"] = spread(sum((g["us"][name] for g in got), []))
             for other in ("numpy", "torch"):
                 line["table_vs_" + other] = round(line[other + "_us"]["median"] / line["table_us"]["median"], 2)
+        elif part == "los":
+            line["shape"], line["windows"] = got[0]["shape"], got[0]["windows"]
+            for kind in ("kernel_us", "chunk_us"):
+                line[kind] = {name: spread(sum((g[kind][name] for g in got), [])) for name in got[0][kind]}
         else:
             line["shape"], line["ndraws"] = got[0]["shape"], got[0]["ndraws"]
             for name in got[0]["ms"]:
