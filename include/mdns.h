@@ -1062,6 +1062,63 @@ int mdns_backend_draw_table(void *joint, mdns_table *table, const double *params
                             unsigned long long *fillbits, int *nscored);
 int mdns_joint_init_table(mdns_joint *j, mdns_table *table, const double *params, double noise_level, const double *jitter);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 13 -- the INSTRUMENT RESPONSE on the device: model curves folded onto the data's channels before any statistic
+ * sees them (csrc/mdns_response.hip, k_response_fold).
+ *
+ * Count spectra of real instruments are not measured on the model's bins: the model lives on n_in fine energy (or
+ * wavelength) bins, the data on nx detector channels, and between the two sits a sparse, mostly banded matrix -- RMF x
+ * ARF in X-ray fitting, a wavelength-dependent line-spread function for a spectrograph.  A response handle holds that
+ * matrix; attached to a spectra handle, every curve entry of Parts 2, 5, 8, 9, 10, 11 and 12 takes curves of n_in bins
+ * and folds them first, on the library stream, between "make curves" and "score curves".  A spectra handle without a
+ * response behaves exactly as before.
+ *
+ * The matrix, CSR by channel:  rowptr i64[nx + 1], rowptr[0] = 0, non-decreasing, rowptr[nx] = nnz;  cols i32[nnz],
+ * strictly increasing inside a row, in [0, n_in);  vals f64[nnz], finite, any sign.
+ *
+ *   folded[b][j] = acc,  where acc = +0.0, then for p = rowptr[j] .. rowptr[j + 1] - 1 ascending
+ *                  acc = acc + vals[p] * curve[b][cols[p]]
+ *
+ * Each multiply and each add is ONE rounded fp64 operation, never contracted into an FMA.  An empty row gives +0.0.  A
+ * NaN or inf in a bin is seen by exactly the channels whose rows hold that bin.  A value depends on its candidate and
+ * channel only -- not on B, the candidate's place in the batch, ldc, the entry point, or what the handle computed
+ * before.  The matrix cores are not used: their accumulation order is not this one.  The numpy statement of the same
+ * chain is massivedatans_amd/response.py, Response.statement: the two agree bit for bit.
+ *
+ * mdns_response_create: every rule above is looked for in the host arrays before the device is asked for anything, and
+ * the message names the array and the index; 1 <= nx, n_in <= MDNS_TABLE_MAX_NX, nnz <= 2^31 - 1.  The matrix is
+ * re-laid per group of 64 channels so that entry l of the 64 rows is contiguous (one length per row; padding is never
+ * multiplied) and copied to the device.  All or none: NULL (mdns_last_error says why) and nothing left allocated.
+ * mdns_response_nx, mdns_response_nin: the two sizes (-1: null handle).
+ *
+ * mdns_response_fold_batch: curves host f64[B][n_in] -> out host f64[B][nx], synchronous, through grow-only scratch of
+ * the handle.  _dev: device pointers, rows of ldc >= n_in and ldo >= nx doubles whose padding is neither read nor
+ * written, asynchronous on the library stream.  B == 0: nothing happens.
+ *
+ * mdns_spectra_set_response(s, r): from now on every entry that takes model curves for s takes n_in bins per curve
+ * (ldc >= n_in; the host forms rows of exactly n_in) and folds them into a grow-only buffer of s before it scores:
+ * mdns_curve_loglike_batch, mdns_curve_chi2_batch, mdns_curve_poisson_batch, mdns_curve_wstat_batch and their _dev
+ * forms, mdns_curve_background_batch[_dev], mdns_muse_loglike_batch[_dev] and mdns_muse_continuum_fit_batch[_dev] (the
+ * scale-marginalised likelihood of curves, without and with a continuum), mdns_joint_init_curves,
+ * mdns_backend_draw_curves[_dev], mdns_joint_init_table and mdns_backend_draw_table -- the last two then require the
+ * table's nx to equal n_in.  No scoring kernel changes.  r == NULL detaches.  Refused: a response whose nx is not the
+ * spectra's, and any change while a joint state lives on s.  The spectra handle BORROWS the response, which counts its
+ * attachments: mdns_response_destroy of an attached response is refused (returns 1, frees nothing); detaching or
+ * destroying the spectra releases it.  A growth of the folded buffer that the device refuses fails that call and leaves
+ * the handles usable.
+ *
+ * Not covered: a response per spectrum (per-spectrum effective area goes into the exposures of Part 10), sharded runs,
+ * the chained first batch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mdns_response mdns_response;
+mdns_response *mdns_response_create(int nx, int n_in, const long long *rowptr, const int *cols, const double *vals);
+int mdns_response_destroy(mdns_response *r);
+int mdns_response_nx(const mdns_response *r);
+int mdns_response_nin(const mdns_response *r);
+int mdns_response_fold_batch(mdns_response *r, const double *curves, int B, double *out);
+int mdns_response_fold_batch_dev(mdns_response *r, const double *d_curves, int ldc, int B, double *d_out, int ldo);
+int mdns_spectra_set_response(mdns_spectra *s, mdns_response *r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,9 @@ ABI_SYMBOLS = (
     # Part 12: a tabulated template grid as the model, evaluated on the device (csrc/mdns_table.hip k_table_curves)
     "mdns_table_create", "mdns_table_create_los", "mdns_table_destroy", "mdns_table_nparams", "mdns_table_nx", "mdns_table_curves_batch",
     "mdns_table_curves_batch_dev", "mdns_backend_draw_table", "mdns_joint_init_table",
+    # Part 13: the instrument response folded into model curves on the device (csrc/mdns_response.hip k_response_fold)
+    "mdns_response_create", "mdns_response_destroy", "mdns_response_nx", "mdns_response_nin", "mdns_response_fold_batch",
+    "mdns_response_fold_batch_dev", "mdns_spectra_set_response",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -256,6 +259,13 @@ def _declare(lib):
         "mdns_table_curves_batch_dev": (i, [vp, vp, i, vp, i]),
         "mdns_backend_draw_table": (i, [vp, vp, vp, i, vp, vp, vp, vp]),
         "mdns_joint_init_table": (i, [vp, vp, vp, d, vp]),
+        "mdns_response_create": (vp, [i, i, vp, vp, vp]),
+        "mdns_response_destroy": (i, [vp]),
+        "mdns_response_nx": (i, [vp]),
+        "mdns_response_nin": (i, [vp]),
+        "mdns_response_fold_batch": (i, [vp, vp, i, vp]),
+        "mdns_response_fold_batch_dev": (i, [vp, vp, i, i, vp, i]),
+        "mdns_spectra_set_response": (i, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

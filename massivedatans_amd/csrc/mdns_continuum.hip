@@ -433,6 +433,8 @@ extern "C" int mdns_muse_continuum_fit_batch_dev(mdns_spectra *s, const double *
 	if (s->continuum < 1) { set_error("mdns_muse_continuum_fit_batch_dev: no continuum is set on these spectra (mdns_spectra_set_continuum)"); return 1; }
 	if (B == 0 || M == 0) return 0;
 	if (!d_ypred || !d_Lout) { set_error("mdns_muse_continuum_fit_batch_dev: null argument"); return 1; }
+	int ldc = curve_bins(s);                                              // (rows of n_in bins with a response: folded to rows of nx)
+	if (!response_fold(s, &d_ypred, &ldc, B)) return 1;
 	const int ldm = model_ld(s->nx);
 	if (!s->d_model.fit((size_t) B * ldm)) return 1;
 	if (!launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;
@@ -457,7 +459,7 @@ extern "C" int mdns_muse_continuum_fit_batch(mdns_spectra *s, const double *ypre
 			}
 	}
 	const int P = s->continuum;
-	const size_t np = (size_t) B * s->nx, n = (size_t) B * M;
+	const size_t np = (size_t) B * curve_bins(s), n = (size_t) B * M;
 	// d_out: L [B][M] | scale [B][M] | coef [B][M][P]
 	if (!s->d_params.fit(np) || !s->d_out.fit(n * (2 + P)) || (row_ids && !s->d_rows.fit((size_t) M))) return 1;
 	// (pageable memory: the runtime stages it; the call ends in a synchronise)

@@ -401,6 +401,7 @@ extern "C" void mdns_spectra_destroy(mdns_spectra *s)
 	if (!s) return;
 	Context *c = ctx();
 	if (c) (void) hipStreamSynchronize(c->stream);
+	if (s->response) s->response->attached--;                     // (borrowed: mdns.h Part 13)
 	delete s;           // (its blocks free themselves)
 }
 extern "C" int mdns_spectra_ndata(const mdns_spectra *s) { return s ? s->ndata : -1; }
@@ -511,6 +512,8 @@ extern "C" int mdns_muse_loglike_batch_dev(mdns_spectra *s, const double *d_ypre
 	if (!ctx() || !check_batch(s, B, M, "mdns_muse_loglike_batch_dev")) return 1;
 	if (!s->d_w.get()) { set_error("spectra were created without variances"); return 1; }
 	if (B == 0 || M == 0) return 0;
+	int ldc = curve_bins(s);                                              // (rows of n_in bins with a response: folded to rows of nx)
+	if (!response_fold(s, &d_ypred, &ldc, B)) return 1;
 	const int ldm = model_ld(s->nx);
 	if (!s->d_model.fit((size_t) B * ldm)) return 1;
 	if (!launch_pad_model(d_ypred, s->nx, B, s->d_model.get(), ldm)) return 1;
@@ -591,13 +594,13 @@ static int fn_muse(mdns_spectra *s, const double *p, int B, const int *r, int M,
 static int fn_muse3(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_muse3_loglike_batch_dev(s, p, B, r, M, o); }
 static int fn_curve(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double noise)
-{ return mdns_curve_loglike_batch_dev(s, p, s->nx, B, noise, r, M, o); }
+{ return mdns_curve_loglike_batch_dev(s, p, curve_bins(s), B, noise, r, M, o); }
 static int fn_curve_chi2(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
-{ return mdns_curve_chi2_batch_dev(s, p, s->nx, B, r, M, o); }
+{ return mdns_curve_chi2_batch_dev(s, p, curve_bins(s), B, r, M, o); }
 static int fn_curve_poisson(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
-{ return mdns_curve_poisson_batch_dev(s, p, s->nx, B, r, M, o); }
+{ return mdns_curve_poisson_batch_dev(s, p, curve_bins(s), B, r, M, o); }
 static int fn_curve_wstat(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
-{ return mdns_curve_wstat_batch_dev(s, p, s->nx, B, r, M, o); }
+{ return mdns_curve_wstat_batch_dev(s, p, curve_bins(s), B, r, M, o); }
 static int fn_lines(mdns_spectra *s, const double *p, int B, const int *r, int M, double *o, double)
 { return mdns_lines_loglike_batch_dev(s, p, B, r, M, o); }
 
@@ -609,24 +612,24 @@ extern "C" int mdns_gauss_loglike_batch(mdns_spectra *s, const double *params, i
 extern "C" int mdns_curve_loglike_batch(mdns_spectra *s, const double *curves, int B, double noise_level,
                                         const int *row_ids, int M, double *Lout)
 {
-	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, noise_level, fn_curve, "mdns_curve_loglike_batch");
+	return host_batch(s, curves, B, s ? curve_bins(s) : 0, row_ids, M, Lout, noise_level, fn_curve, "mdns_curve_loglike_batch");
 }
 extern "C" int mdns_curve_chi2_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout)
 {
-	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_curve_chi2, "mdns_curve_chi2_batch");
+	return host_batch(s, curves, B, s ? curve_bins(s) : 0, row_ids, M, Lout, 0, fn_curve_chi2, "mdns_curve_chi2_batch");
 }
 extern "C" int mdns_curve_poisson_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout)
 {
-	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_curve_poisson, "mdns_curve_poisson_batch");
+	return host_batch(s, curves, B, s ? curve_bins(s) : 0, row_ids, M, Lout, 0, fn_curve_poisson, "mdns_curve_poisson_batch");
 }
 extern "C" int mdns_curve_wstat_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *Lout)
 {
-	return host_batch(s, curves, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_curve_wstat, "mdns_curve_wstat_batch");
+	return host_batch(s, curves, B, s ? curve_bins(s) : 0, row_ids, M, Lout, 0, fn_curve_wstat, "mdns_curve_wstat_batch");
 }
 extern "C" int mdns_muse_loglike_batch(mdns_spectra *s, const double *ypred, int B,
                                        const int *row_ids, int M, double *Lout)
 {
-	return host_batch(s, ypred, B, s ? s->nx : 0, row_ids, M, Lout, 0, fn_muse, "mdns_muse_loglike_batch");
+	return host_batch(s, ypred, B, s ? curve_bins(s) : 0, row_ids, M, Lout, 0, fn_muse, "mdns_muse_loglike_batch");
 }
 extern "C" int mdns_muse3_loglike_batch(mdns_spectra *s, const double *params, int B,
                                         const int *row_ids, int M, double *Lout)

@@ -496,8 +496,9 @@ static int curve_batch_check(const mdns_spectra *s, const double *d_curves, int 
 {
 	if (!ctx()) return 1;
 	if (!s) { set_error("%s: null spectra handle", who); return 1; }
-	if (B < 0 || M < 0 || M > s->ndata || s->nx < 1 || ldc < s->nx || (!d_row_ids && M != s->ndata && M != 0)) {
-		set_error("%s: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", who, B, M, s->ndata, ldc, s->nx);
+	if (B < 0 || M < 0 || M > s->ndata || s->nx < 1 || ldc < curve_bins(s) || (!d_row_ids && M != s->ndata && M != 0)) {
+		if (s->response) set_error("%s: bad sizes B=%d M=%d (ndata=%d) ldc=%d (n_in=%d of the response)", who, B, M, s->ndata, ldc, curve_bins(s));
+		else set_error("%s: bad sizes B=%d M=%d (ndata=%d) ldc=%d (nx=%d)", who, B, M, s->ndata, ldc, s->nx);
 		return 1;
 	}
 	if (stat == kCurveChi2 && !s->d_w.get()) { set_error("%s: spectra were created without variances", who); return 1; }
@@ -513,6 +514,7 @@ static int curve_batch_dev(CurveStat stat, mdns_spectra *s, const double *d_curv
 {
 	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_Lout, stat, who);
 	if (rc != 0) return rc > 0;
+	if (!response_fold(s, &d_curves, &ldc, B)) return 1;
 	return launch_curve(stat, s, d_curves, ldc, B, noise_level, d_row_ids, M, d_Lout) ? 0 : 1;
 }
 
@@ -634,13 +636,14 @@ extern "C" int mdns_curve_background_batch_dev(mdns_spectra *s, const double *d_
 {
 	const int rc = curve_batch_check(s, d_curves, ldc, B, d_row_ids, M, d_fout, kCurveWstat, "mdns_curve_background_batch_dev");
 	if (rc != 0) return rc > 0;
+	if (!response_fold(s, &d_curves, &ldc, B)) return 1;
 	return launch_curve_background(s, d_curves, ldc, B, d_row_ids, M, d_fout) ? 0 : 1;
 }
 
 extern "C" int mdns_curve_background_batch(mdns_spectra *s, const double *curves, int B, const int *row_ids, int M, double *fout)
 {
 	Context *c = ctx();
-	const int rc = curve_batch_check(s, curves, s ? s->nx : 0, B, row_ids, M, fout, kCurveWstat, "mdns_curve_background_batch");
+	const int rc = curve_batch_check(s, curves, s ? curve_bins(s) : 0, B, row_ids, M, fout, kCurveWstat, "mdns_curve_background_batch");
 	if (rc != 0) return rc > 0;
 	if (row_ids) {
 		for (int k = 0; k < M; k++)
@@ -649,12 +652,15 @@ extern "C" int mdns_curve_background_batch(mdns_spectra *s, const double *curves
 				return 1;
 			}
 	}
-	const size_t np = (size_t) B * s->nx, no = (size_t) B * M * s->nx;
+	const size_t np = (size_t) B * curve_bins(s), no = (size_t) B * M * s->nx;
 	if (!s->d_params.fit(np) || !s->d_out.fit(no) || (row_ids && !s->d_rows.fit((size_t) M))) return 1;
 	// (pageable memory: the runtime stages it; the call ends in a synchronise)
 	if (!MDNS_HIP(hipMemcpyAsync(s->d_params.get(), curves, np * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
 	if (row_ids && !MDNS_HIP(hipMemcpyAsync(s->d_rows.get(), row_ids, (size_t) M * sizeof(int), hipMemcpyHostToDevice, c->stream))) return 1;
-	if (!launch_curve_background(s, s->d_params.get(), s->nx, B, row_ids ? s->d_rows.get() : nullptr, M, s->d_out.get())) return 1;
+	const double *d_curves = s->d_params.get();
+	int ldc = curve_bins(s);
+	if (!response_fold(s, &d_curves, &ldc, B)) return 1;
+	if (!launch_curve_background(s, d_curves, ldc, B, row_ids ? s->d_rows.get() : nullptr, M, s->d_out.get())) return 1;
 	if (!MDNS_HIP(hipMemcpyAsync(fout, s->d_out.get(), no * sizeof(double), hipMemcpyDeviceToHost, c->stream))) return 1;
 	return MDNS_HIP(hipStreamSynchronize(c->stream)) ? 0 : 1;
 }

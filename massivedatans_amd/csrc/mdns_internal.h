@@ -232,6 +232,29 @@ struct mdns_spectra {
 	// this handle is then the W statistic (k_curve_rows_b); fixed like the line list (njoint)
 	int background = 0;
 	mdns::DeviceBuffer<double> d_b, d_g, d_kw;
+	// the instrument response (mdns_response.hip, mdns_spectra_set_response; mdns.h Part 13), borrowed, or nullptr: with
+	// one every curve entry takes curves of response->n_in bins and response_fold() puts them, folded onto the nx
+	// channels, into d_folded [B][nx] (grow-only) before anything scores them.  Fixed like the line list (njoint)
+	mdns_response *response = nullptr;
+	mdns::DeviceBuffer<double> d_folded;
+};
+
+// an instrument response on the device (mdns.h Part 13, mdns_response.hip): validated once at creation, never changed.
+// The matrix per group of 64 channels (a wave), entry l of the 64 rows contiguous: entry l of channel j is element
+// d_slice[j / 64] + 64 l + j % 64 of d_vals and d_cols, for l < d_len[j]; a group is as wide as its longest row and
+// what lies behind a row's length is padding (vals 0, cols 0) that nothing multiplies
+struct mdns_response {
+	int nx = 0;         // output channels
+	int n_in = 0;       // model bins
+	long long nnz = 0;
+	int attached = 0;   // spectra handles that borrow this response (mdns_spectra_set_response)
+	// resident blocks, made once at their exact size
+	mdns::DeviceBuffer<int> d_len;            // [nx]
+	mdns::DeviceBuffer<long long> d_slice;    // [ceil(nx / 64)]
+	mdns::DeviceBuffer<double> d_vals;        // the groups one after the other
+	mdns::DeviceBuffer<int> d_cols;
+	// grow-only scratch of the host-pointer batch call
+	mdns::DeviceBuffer<double> d_in, d_out;
 };
 
 // a tabulated template grid on the device (mdns.h Part 12, mdns_table.hip): validated once at creation, never changed
@@ -261,6 +284,16 @@ namespace mdns {
 // asynchronous on ctx()->stream (mdns_table.hip: k_table_curves, or the k_table_los_* route the handle's flags select,
 // which may grow the handle's scratch)
 bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc);
+
+// the instrument response (mdns_response.hip; mdns.h Part 13), asynchronous on ctx()->stream:
+// d_curves [B][ldc] (ldc >= r->n_in) -> d_out [B][ldo] (ldo >= r->nx); the padding is neither read nor written
+bool launch_response_fold(const mdns_response *r, const double *d_curves, int ldc, int B, double *d_out, int ldo);
+// bins of a model curve for s: the response's n_in, or nx without one
+inline int curve_bins(const mdns_spectra *s) { return s->response ? s->response->n_in : s->nx; }
+// THE place that decides whether curves are folded: with a response on s, *d_curves [B][*ldc] is folded into
+// s->d_folded [B][nx] and *d_curves, *ldc name that block afterwards; without one nothing happens.  false (the error
+// set): the folded buffer could not grow, or the launch was refused
+bool response_fold(mdns_spectra *s, const double **d_curves, int *ldc, int B);
 
 // model row stride for nx channels: multiple of 512 doubles (zero padded), so that every
 // lane / thread of the row kernels can load its channel pair without a bounds test

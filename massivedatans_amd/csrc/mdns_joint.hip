@@ -660,17 +660,18 @@ extern "C" int mdns_joint_init_muse3(mdns_joint *j, const double *params, const 
 static bool curves_score(mdns_joint *j, const double *d_curves, int ldc, int B, const int *d_rows, int M, double *d_out)
 {
 	mdns_spectra *s = j->s;
+	if (!response_fold(s, &d_curves, &ldc, B)) return false;
 	if (j->stat != kCurveMarginal) return launch_curve(j->stat, s, d_curves, ldc, B, j->noise_level, d_rows, M, d_out);
 	const int ldm = model_ld(s->nx);
 	return ensure_model(s, (size_t) B * ldm) && launch_curve_pad(d_curves, ldc, s->nx, B, s->d_model.get(), ldm) &&
 	       launch_muse_rows(s, s->d_model.get(), ldm, B, d_rows, M, d_out);
 }
 
-// the live points' likelihoods from their curves in j->d_curves [nlive][nx], plus the jitter (host [nlive][ndata] or
+// the live points' likelihoods from their curves in j->d_curves [nlive][curve_bins], plus the jitter (host [nlive][ndata] or
 // nullptr); the state is reset and the stream drained
 static int init_from_curves(mdns_joint *j, Context *c, const double *jitter)
 {
-	if (!curves_score(j, j->d_curves.get(), j->s->nx, j->nlive, nullptr, j->ndata, j->st.live)) return 1;
+	if (!curves_score(j, j->d_curves.get(), curve_bins(j->s), j->nlive, nullptr, j->ndata, j->st.live)) return 1;
 	return init_finish(j, c, jitter);
 }
 
@@ -678,8 +679,8 @@ extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, doubl
 {
 	Context *c = ctx();
 	if (!c || !j || !curves) return 1;
-	const int nx = j->s->nx;
-	if (nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
+	if (j->s->nx < 1) { set_error("mdns_joint_init_curves: spectra without channels"); return 1; }
+	const int nx = curve_bins(j->s);                                      // (what a curve holds: the response's bins, or the channels)
 	if (j->stat == kCurveNoise) j->noise_level = noise_level;
 	if (!j->d_curves.fit((size_t) j->nlive * nx)) return 1;
 	if (!MDNS_HIP(hipMemcpyAsync(j->d_curves.get(), curves, (size_t) j->nlive * nx * sizeof(double), hipMemcpyHostToDevice, c->stream))) return 1;
@@ -690,7 +691,11 @@ extern "C" int mdns_joint_init_curves(mdns_joint *j, const double *curves, doubl
 static bool table_fits(const mdns_joint *j, const mdns_table *table, const char *who)
 {
 	if (!table) { set_error("%s: null table handle", who); return false; }
-	if (table->nx != j->s->nx) {
+	if (j->s->response && table->nx != j->s->response->n_in) {
+		set_error("%s: the table model makes curves of %d bins, the spectra's response takes %d", who, table->nx, j->s->response->n_in);
+		return false;
+	}
+	if (!j->s->response && table->nx != j->s->nx) {
 		set_error("%s: the table model makes curves of %d channels, the spectra have %d", who, table->nx, j->s->nx);
 		return false;
 	}
@@ -1419,7 +1424,11 @@ static int draw_curves_check(void *joint, Context **c, mdns_joint **j, const voi
 	mdns_joint *st = draw_entry(joint, c, accepted != nullptr, accepted, 0, who, nullptr, B);
 	*j = nullptr;
 	if (!st) return 1;
-	if (ldc < st->s->nx || st->s->nx < 1) { set_error("%s: rows of %d doubles for %d channels", who, ldc, st->s->nx); return 1; }
+	if (st->s->response && ldc < st->s->response->n_in) {
+		set_error("%s: rows of %d doubles for the %d bins of the spectra's response", who, ldc, st->s->response->n_in);
+		return 1;
+	}
+	if (ldc < curve_bins(st->s) || st->s->nx < 1) { set_error("%s: rows of %d doubles for %d channels", who, ldc, st->s->nx); return 1; }
 	if (nscored) *nscored = B;
 	if (B == 0 || st->sel_M == 0) return 0;
 	if (!curves) { set_error("%s: null curves", who); return 1; }
@@ -1440,7 +1449,7 @@ extern "C" int mdns_backend_draw_curves(void *joint, const double *curves, int B
                                         unsigned long long *fillbits, int *nscored)
 {
 	Context *c;  mdns_joint *j;
-	const int nx = joint ? ((mdns_joint *) joint)->s->nx : 0;
+	const int nx = joint ? curve_bins(((mdns_joint *) joint)->s) : 0;     // (what a curve holds: the response's bins, or the channels)
 	const int rc = draw_curves_check(joint, &c, &j, curves, nx, B, accepted, nscored, "mdns_backend_draw_curves");
 	if (!j) return rc;
 	const size_t nc = (size_t) B * nx;
@@ -1458,7 +1467,7 @@ extern "C" int mdns_backend_draw_table(void *joint, mdns_table *table, const dou
 {
 	Context *c;
 	mdns_joint *j = (mdns_joint *) joint;
-	const int nx = j ? j->s->nx : 0;
+	const int nx = j ? curve_bins(j->s) : 0;
 	if (ctx() && j && accepted) {
 		*accepted = -1;
 		if (!table_fits(j, table, "mdns_backend_draw_table")) return 1;

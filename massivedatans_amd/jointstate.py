@@ -509,6 +509,8 @@ class CurveJointState(GaussJointState):
         super(CurveJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
         self.model = model
         self.nx = int(spectra.nx)
+        # what a model curve holds: the bins of the spectra's response, or -- without one -- the channels
+        self.n_in = int(getattr(spectra, "n_in", spectra.nx))
         self.nparams = int(ndim) if ndim is not None else None
         # a table model on the device (tablemodel.DeviceTable): init and draw_params hand it the parameters and
         # ``model`` is never called (mdns_joint_init_table, mdns_backend_draw_table)
@@ -532,20 +534,20 @@ class CurveJointState(GaussJointState):
         curves = self.model(xs)
         if hasattr(curves, "data_ptr") and getattr(curves, "is_cuda", False):
             import torch
-            if curves.dtype != torch.float64 or curves.dim() != 2 or tuple(curves.shape) != (n, self.nx):
+            if curves.dtype != torch.float64 or curves.dim() != 2 or tuple(curves.shape) != (n, self.n_in):
                 raise ValueError("the model must return float64 curves [%d, %d], got %s %s"
-                                 % (n, self.nx, curves.dtype, tuple(curves.shape)))
-            if curves.stride(1) != 1 or (n > 1 and curves.stride(0) < self.nx):
+                                 % (n, self.n_in, curves.dtype, tuple(curves.shape)))
+            if curves.stride(1) != 1 or (n > 1 and curves.stride(0) < self.n_in):
                 curves = curves.contiguous()
             # the library reads on its own stream: what torch has queued for the tensor must be done
             torch.cuda.current_stream(curves.device).synchronize()
-            return curves.data_ptr(), max(int(curves.stride(0)), self.nx), True, curves
+            return curves.data_ptr(), max(int(curves.stride(0)), self.n_in), True, curves
         if hasattr(curves, "detach"):                     # a host tensor
             curves = curves.detach().numpy()
         curves = _lib.as_f64(curves)
-        if curves.shape != (n, self.nx):
-            raise ValueError("the model must return curves [%d, %d], got %s" % (n, self.nx, curves.shape))
-        return _lib.ptr(curves), self.nx, False, curves
+        if curves.shape != (n, self.n_in):
+            raise ValueError("the model must return curves [%d, %d], got %s" % (n, self.n_in, curves.shape))
+        return _lib.ptr(curves), self.n_in, False, curves
 
     def init(self, xs, jitter=None):
         xs = numpy.asarray(xs, dtype=float)
@@ -596,7 +598,7 @@ class CurveJointState(GaussJointState):
             params = _lib.as_f64(params)
             if params.ndim != 2 or params.shape[1] != self.table.ndim:
                 raise ValueError("params must be [B, %d], got %s" % (self.table.ndim, params.shape))
-            address, ld, on_device, keep = None, self.nx, False, params
+            address, ld, on_device, keep = None, self.n_in, False, params
         else:
             address, ld, on_device, keep = self._curves(params)
         if rows is not None:

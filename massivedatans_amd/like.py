@@ -53,6 +53,7 @@ class _Spectra(object):
         else:
             raise ValueError(layout)
         self.ndata, self.nx = int(ndata), int(nx)
+        self._response = None
         xp = None
         if x is not None:
             x = _lib.as_f64(x)
@@ -75,14 +76,37 @@ class _Spectra(object):
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.mdns_spectra_destroy(self._h)
+            self._lib.mdns_spectra_destroy(self._h)           # (releases a response it had borrowed)
             self._h = None
+            self._response = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    @property
+    def response(self):
+        """The :class:`massivedatans_amd.response.DeviceResponse` attached to these spectra, or None."""
+        return self._response
+
+    @property
+    def n_in(self):
+        """Values per model curve: the bins of the attached response, or -- without one -- the channels."""
+        return self.nx if self._response is None else self._response.n_in
+
+    def set_response(self, response):
+        """Attaches an instrument response (a :class:`massivedatans_amd.response.DeviceResponse`; a
+        :class:`massivedatans_amd.response.Response` is bound first; None detaches): from now on every scoring on these
+        spectra takes curves of ``response.n_in`` bins and folds them on the device first (include/mdns.h Part 13).
+        The spectra keep the device response alive.  Refused (MdnsError) for a response of another ``nx`` and while a
+        joint state lives on the spectra."""
+        if response is not None and not hasattr(response, "handle"):
+            response = response.bind()
+        _lib.check(self._lib.mdns_spectra_set_response(self._h, None if response is None else response.handle),
+                   "mdns_spectra_set_response")
+        self._response = response
 
     def _batch(self, fn, name, params, data_mask, *extra):
         params = _lib.as_f64(params)
@@ -96,10 +120,11 @@ class _Spectra(object):
         return out
 
     def _curves_batch(self, name, curves, data_mask, *extra):
-        """``curves[B, nx]`` (one curve: ``[nx]``) through the library's batch function ``name`` -> ``L[B, mask.sum()]``."""
+        """``curves[B, nx]`` (one curve: ``[nx]``; with a response ``[B, n_in]``, folded on the device) through the library's
+        batch function ``name`` -> ``L[B, mask.sum()]``."""
         curves = np.atleast_2d(_lib.as_f64(curves))
-        if curves.shape[1] != self.nx:
-            raise ValueError("curves must be [B, %d]" % self.nx)
+        if curves.shape[1] != self.n_in:
+            raise ValueError("curves must be [B, %d]" % self.n_in)
         return self._batch(getattr(self._lib, name), name, curves, data_mask, *extra)
 
 
@@ -291,8 +316,8 @@ class CountSpectra(_Spectra):
         if not self.has_background:
             raise ValueError("these spectra were made without a background")
         curves = np.atleast_2d(_lib.as_f64(curves))
-        if curves.shape[1] != self.nx:
-            raise ValueError("curves must be [B, %d]" % self.nx)
+        if curves.shape[1] != self.n_in:                      # (with a response: unfolded curves, folded on the device)
+            raise ValueError("curves must be [B, %d]" % self.n_in)
         rows, M = _rows_from_mask(data_mask, self.ndata)
         B = len(curves)
         f = np.empty((B, M, self.nx))
@@ -334,8 +359,8 @@ class MuseSpectra(_Spectra):
         if not self.continuum:
             raise ValueError("these spectra were made without a continuum")
         ypred = np.atleast_2d(_lib.as_f64(ypred))
-        if ypred.shape[1] != self.nx:
-            raise ValueError("templates must be [B, %d]" % self.nx)
+        if ypred.shape[1] != self.n_in:
+            raise ValueError("templates must be [B, %d]" % self.n_in)
         rows, M = _rows_from_mask(data_mask, self.ndata)
         B = len(ypred)
         L, s, coef = np.empty((B, M)), np.empty((B, M)), np.empty((B, M, self.continuum))
@@ -348,8 +373,8 @@ class MuseSpectra(_Spectra):
     def loglike_batch(self, ypred, data_mask=None):
         """``ypred[B, nx]`` precomputed templates -> ``L[B, mask.sum()]`` (= -0.5 chi)."""
         ypred = np.atleast_2d(_lib.as_f64(ypred))
-        if ypred.shape[1] != self.nx:
-            raise ValueError("templates must be [B, %d]" % self.nx)
+        if ypred.shape[1] != self.n_in:
+            raise ValueError("templates must be [B, %d]" % self.n_in)
         return self._batch(self._lib.mdns_muse_loglike_batch, "mdns_muse_loglike_batch",
                            ypred, data_mask)
 

@@ -27,19 +27,28 @@ MAX_DIM = 16                                 # include/mdns.h MDNS_MAX_DIM
 
 
 def default_backend(x, y, noise_level, v=None, continuum=0, marginalise_scale=True, poisson=False, exposure=None,
-                    background=None, background_exposure=None):
+                    background=None, background_exposure=None, response=None):
     """The spectra on the GPU: fixed noise, or -- with variances ``v`` -- the scale-marginalised likelihood
     (``continuum``: like.MuseSpectra), or -- ``marginalise_scale=False`` -- the fixed-scale one (like.WeightedSpectra), or
     -- ``poisson=True``, ``y`` holding counts -- the Poisson one (``exposure``: like.CountSpectra), with ``background``
-    (and ``background_exposure``) the W statistic."""
+    (and ``background_exposure``) the W statistic.  ``response`` (a :class:`massivedatans_amd.response.Response`) is
+    attached: the spectra then take curves of ``response.n_in`` bins and fold them on the device."""
     from .like import CountSpectra, GaussLineSpectra, MuseSpectra, WeightedSpectra
     if poisson:
-        return CountSpectra(x, y, exposure, background, background_exposure)
-    if v is None:
-        return GaussLineSpectra(x, y, noise_level=noise_level)
-    if not marginalise_scale:
-        return WeightedSpectra(x, y, v)
-    return MuseSpectra(x, y, v, continuum=continuum)
+        spectra = CountSpectra(x, y, exposure, background, background_exposure)
+    elif v is None:
+        spectra = GaussLineSpectra(x, y, noise_level=noise_level)
+    elif not marginalise_scale:
+        spectra = WeightedSpectra(x, y, v)
+    else:
+        spectra = MuseSpectra(x, y, v, continuum=continuum)
+    if response is not None:
+        try:
+            spectra.set_response(response)
+        except Exception:
+            spectra.close()
+            raise
+    return spectra
 
 
 def host_curves(curves):
@@ -92,6 +101,14 @@ class CurveProblem(object):
     curve is made in Python; ``multi_loglikelihood[_batch]`` fetch the device's curves and score them like any other.
     Over a ``backend`` that is not on the device the model is ``TableModel.statement``.
 
+    ``response`` (a :class:`massivedatans_amd.response.Response` of ``nx`` channels; works with every likelihood above):
+    the instrument response between the model and the data.  ``model`` then returns ``[B, response.n_in]``, on the
+    response's model bins, and every curve is folded onto the channels on the device before it is scored (include/mdns.h
+    Part 13); a ``TableModel`` is evaluated on ``response.x_in``; ``multi_loglikelihood[_batch]`` and
+    ``backend.background_fit`` take unfolded curves.  Over a ``backend`` that is not on the device the model becomes
+    ``response.statement(model(xs))``.  One response serves all spectra of the run (a per-spectrum effective area goes
+    into ``exposure``); sharded runs and the chained first batch do not take one.
+
     ``jitter_sigma > 0`` adds ``N(0, jitter_sigma)`` to every likelihood evaluation from the global random
     stream, as musefuse.py:535 does.  ``backend``: any object with ``loglike_batch(curves[B, nx], mask) ->
     L[B, M]`` (tests put a numpy scorer there; the state is then the numpy one); by default the spectra go
@@ -100,8 +117,10 @@ class CurveProblem(object):
     Gives ``sample.build_sampler`` what it reads of a problem."""
 
     def __init__(self, x, y, model, priortransform_batch, ndim, noise_level=0.01, v=None, jitter_sigma=0.0, backend=None,
-                 continuum=0, marginalise_scale=True, poisson=False, exposure=None, background=None, background_exposure=None):
+                 continuum=0, marginalise_scale=True, poisson=False, exposure=None, background=None, background_exposure=None,
+                 response=None):
         from .continuum import check_terms
+        from .response import Response
         self.continuum = check_terms(continuum)
         self.marginalise_scale = bool(marginalise_scale)
         self.poisson = bool(poisson)
@@ -135,6 +154,11 @@ class CurveProblem(object):
             if a is not None and a.shape != self.y.shape:
                 raise ValueError("%s has shape %s, y has %s" % (name, a.shape, self.y.shape))
         self.nx, self.ndata = self.y.shape
+        if response is not None and not isinstance(response, Response):
+            raise ValueError("response must be a massivedatans_amd.response.Response, got %r" % type(response).__name__)
+        if response is not None and response.nx != self.nx:
+            raise ValueError("the response folds onto %d channels, y has %d" % (response.nx, self.nx))
+        self.response = response
         if not 1 <= int(ndim) <= MAX_DIM:
             raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
         self.nparams = int(ndim)
@@ -142,6 +166,9 @@ class CurveProblem(object):
         table_model = model if isinstance(model, TableModel) else None
         if table_model is not None and table_model.ndim != self.nparams:
             raise ValueError("ndim = %d, the table model takes %d parameters" % (self.nparams, table_model.ndim))
+        if table_model is not None and response is not None and response.x_in is None:
+            raise ValueError("a table model under a response is evaluated on the response's model bins: the response needs x_in")
+        model_x = self.x if response is None else response.x_in     # the abscissa a table model is bound to
         self.table = None                            # a table model on the device (tablemodel.DeviceTable)
         self.model = model
         self.priortransform_batch = priortransform_batch
@@ -159,8 +186,14 @@ class CurveProblem(object):
                     kw["background"] = self.background
                 if self.background_exposure is not None:
                     kw["background_exposure"] = self.background_exposure
+            if response is not None:
+                kw["response"] = response
             backend = default_backend(self.x, self.y, self.noise_level, self.v, **kw)
         self.backend = backend
+        if response is not None and self._on_device():
+            attached = getattr(backend, "response", None)
+            if attached is None or attached.response is not response:
+                raise ValueError("the backend was made without this response (default_backend(..., response=) attaches it)")
         if getattr(backend, "continuum", 0) != self.continuum:
             raise ValueError("the backend was made with continuum = %r, the problem with %d"
                              % (getattr(backend, "continuum", 0), self.continuum))
@@ -168,10 +201,13 @@ class CurveProblem(object):
             # on the device the joint state hands parameters to the table (no curves are made in Python); what scores
             # outside a draw fetches the device's curves.  Over any other backend the model is its numpy statement
             if self._on_device():
-                self.table = table_model.bind(self.x)
+                self.table = table_model.bind(model_x)
                 self.model = self.table.curves
             else:
-                self.model = lambda xs, _tm=table_model, _x=self.x: _tm.statement(_x, xs)
+                self.model = lambda xs, _tm=table_model, _x=model_x: _tm.statement(_x, xs)
+        if response is not None and not self._on_device():
+            # (on the device the spectra fold; over any other backend the model does, by the numpy statement)
+            self.model = lambda xs, _m=self.model, _r=response: _r.statement(host_curves(_m(xs)))
         if jitter_sigma > 0:
             self.multi_loglikelihood_batch = None         # (every evaluation draws its noise: one candidate at a time)
         self.ncalls = 0

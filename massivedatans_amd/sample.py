@@ -250,7 +250,9 @@ def load_model(path):
     variances ``v`` in the data file) and ``poisson`` (default False; True: ``y`` of the data file holds photon counts,
     ``e`` -- if there -- their exposures, and the likelihood is the Poisson one of problem.CurveProblem; the data file
     must not hold ``v``; if it holds ``b``, the counts of a background region per spectrum -- and ``eb``, their exposures
-    --, the likelihood is the W statistic).  Returns them as a dict; ValueError says what is wrong with the file."""
+    --, the likelihood is the W statistic) and ``response`` (a massivedatans_amd.response.Response: the instrument response
+    between the model's bins and the data's channels; ``model`` then returns ``[B, response.n_in]``).  Returns them as a
+    dict; ValueError says what is wrong with the file."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("mdns_model", path)
     if spec is None or spec.loader is None:
@@ -277,6 +279,10 @@ def load_model(path):
     out["noise_level"] = float(getattr(module, "noise_level", noise_level))
     out["marginalise_scale"] = bool(getattr(module, "marginalise_scale", True))
     out["poisson"] = bool(getattr(module, "poisson", False))
+    out["response"] = getattr(module, "response", None)
+    from .response import Response
+    if out["response"] is not None and not isinstance(out["response"], Response):
+        raise ValueError("%s: `response` is a %s, not a massivedatans_amd.response.Response" % (path, type(out["response"]).__name__))
     return out
 
 
@@ -445,7 +451,8 @@ def main(argv=None):
             data['x'], data['y'], definition['model'], definition['priortransform_batch'], definition['ndim'],
             noise_level=definition['noise_level'], v=data.get('v'), marginalise_scale=definition['marginalise_scale'],
             **(dict(poisson=True, exposure=data.get('e'), background=data.get('b'), background_exposure=data.get('eb'))
-               if definition['poisson'] else {})), **settings)
+               if definition['poisson'] else {}),
+            **(dict(response=definition['response']) if definition['response'] is not None else {})), **settings)
     else:
         backend = distributed_backend(data['x'], data['y'])
         results, sampler, problem, duration = run(data['x'], data['y'], backend=backend, **settings)
