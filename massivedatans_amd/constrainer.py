@@ -23,6 +23,7 @@ import os
 import numpy
 
 from . import _host, _lib
+from .jointstate import pack_fill_bits
 
 MAX_DIM = 16
 
@@ -247,7 +248,8 @@ def chain_statement(u, mn, mx, radius, count, mean, scale, prior, limit, pow10=N
 
 
 def hip_backend(joint):
-    """The device entry points of libmdns_hip.so for a :class:`jointstate.GaussJointState`."""
+    """The device entry points of libmdns_hip.so on the handle of a :class:`jointstate.DeviceJointState` whose
+    model the library evaluates itself (Gaussian line, MUSE-style lines)."""
     lib = _lib.require_device()
     be = DrawBackend()
     be.user = joint._h
@@ -343,6 +345,10 @@ def python_backend(joint, member_set_factory=None):
     def ms_ndim(ms):
         return ms.ndim if hasattr(ms, "ndim") else numpy.shape(ms.members)[1]
 
+    def put_fill_bits(bits_ptr, beats):
+        words = pack_fill_bits(beats)
+        numpy.ctypeslib.as_array(bits_ptr, (len(words),))[:] = words
+
     def draw_begin(_user, rows_ptr, M):
         state["rows"] = numpy.ctypeslib.as_array(rows_ptr, (M,)).copy() if rows_ptr else None
         state["M"] = M
@@ -360,11 +366,7 @@ def python_backend(joint, member_set_factory=None):
             accepted_ptr[0] = idx
             nscored_ptr[0] = nscored
             if idx >= 0:
-                M = state["M"]
-                words = numpy.zeros((M + 63) // 64, dtype=numpy.uint64)
-                packed = numpy.packbits(numpy.asarray(beats, dtype=numpy.uint8), bitorder='little')
-                words.view(numpy.uint8)[:len(packed)] = packed
-                numpy.ctypeslib.as_array(bits_ptr, (len(words),))[:] = words
+                put_fill_bits(bits_ptr, beats)
             return 0
         except Exception:       # noqa: BLE001
             import traceback
@@ -419,11 +421,7 @@ def python_backend(joint, member_set_factory=None):
         try:
             M = state["M"]
             joint._scored_L[b] = joint._scored_L[b] + numpy.ctypeslib.as_array(row_ptr, (M,))
-            _, beats = joint.commit(b)
-            words = numpy.zeros((M + 63) // 64, dtype=numpy.uint64)
-            packed = numpy.packbits(numpy.asarray(beats, dtype=numpy.uint8), bitorder='little')
-            words.view(numpy.uint8)[:len(packed)] = packed
-            numpy.ctypeslib.as_array(bits_ptr, (len(words),))[:] = words
+            put_fill_bits(bits_ptr, joint.commit(b)[1])
             return 0
         except Exception:       # noqa: BLE001
             import traceback
@@ -493,11 +491,7 @@ def python_backend(joint, member_set_factory=None):
         numpy.ctypeslib.as_array(counts_ptr, (len(out["counts"]),))[:] = out["counts"]
         nkept_ptr[0], B_ptr[0], accepted_ptr[0] = out["nkept"], out["B"], out["accepted"]
         if out["accepted"] >= 0:
-            M = state["M"]
-            words = numpy.zeros((M + 63) // 64, dtype=numpy.uint64)
-            packed = numpy.packbits(numpy.asarray(out["beats"], dtype=numpy.uint8), bitorder='little')
-            words.view(numpy.uint8)[:len(packed)] = packed
-            numpy.ctypeslib.as_array(bits_ptr, (len(words),))[:] = words
+            put_fill_bits(bits_ptr, out["beats"])
         if params_ptr and out["B"] > 0:
             numpy.ctypeslib.as_array(params_ptr, (out["B"], 3))[:] = out["params"]
         return 0

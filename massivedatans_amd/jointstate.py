@@ -7,12 +7,17 @@ accept test ``any(L > Lmins)`` (hiermetriclearn.py:193) and the shelf fill (:482
 sampler of this package can hand all of that to a *joint state* object and keep only the
 integer side (point ids, queues of ids, the data-set graph):
 
-* :class:`GaussJointState` -- the state lives in HBM (``mdns_joint_*`` of include/mdns.h); a
-  draw chunk is scored, decided and committed on the GPU and only the accepted candidate's
-  index, likelihood row and fill bits come back.
-* :class:`CurveJointState` -- the same state for a model the CALLER evaluates: a Python function makes
-  one model curve per candidate (numpy, or a torch tensor on the device), the device does everything
-  after the curves.
+* :class:`DeviceJointState` -- the state lives in HBM behind an ``mdns_joint`` handle (``mdns_joint_*``
+  of include/mdns.h); a draw chunk is scored, decided and committed on the GPU and only the accepted
+  candidate's index and fill bits come back.  Its three kinds differ in how the initial points are
+  scored and how a chunk is handed over:
+
+  - :class:`GaussJointState` -- the Gaussian line, from the parameters (optionally with the
+    accepted candidate's likelihood row);
+  - :class:`MuseJointState` -- the MUSE-style lines, from the parameters;
+  - :class:`CurveJointState` -- a model the CALLER evaluates: a Python function makes one model curve
+    per candidate (numpy, or a torch tensor on the device), or a table on the device does; the device
+    does everything after the curves.
 * :class:`HostJointState` -- the same interface in numpy over any ``loglike_batch`` scorer.  It
   is the statement the device implementation is tested against (tests/), and what the CPU
   tests run the orchestration with.
@@ -30,6 +35,15 @@ Interface (``rows`` are ORIGINAL data-set indices, ascending; ``running`` likewi
                                  takes the point in; ``nscored`` candidates were looked at
     advance()                    end of an iteration
     live_matrix() -> L[nlive, nrunning]
+
+The chunk in two halves, for whoever reduces the candidates' votes over several states in between
+(``parallel.ShardedJointState``: one state per rank, each over its block of the data sets):
+
+    score_backend(params, rows, jitter=None)     scores the chunk (kernel parameter rows): one 0 / 1 vote
+                                                 per candidate, 1 where a selected data set accepts it
+    votes() -> int32[B]          set_votes(v)    (device states also: votes_address(), to reduce in place)
+    commit_backend() -> idx, Lrow or None, beats     the first candidate with a vote (-1: none) is taken in
+                                                     by the data sets of THIS state it beats
 """
 import ctypes as C
 
@@ -163,6 +177,22 @@ class HostJointState(object):
             self.higher[d] = self._threshold(d)
         return Lrow, beats
 
+    # the same two halves as every state speaks them (module docstring): the votes are the accept flags
+    def score_backend(self, params, rows, jitter=None):
+        self._votes = self.score_params(params, rows, jitter=jitter)
+
+    def votes(self):
+        return self._votes
+
+    def set_votes(self, votes):
+        self._votes = numpy.asarray(votes, dtype=numpy.int32)
+
+    def commit_backend(self):
+        hit = numpy.flatnonzero(self._votes)
+        if len(hit) == 0:
+            return -1, None, numpy.zeros(len(self._scored_rows), dtype=bool)
+        return (int(hit[0]),) + self.commit(int(hit[0]))
+
     def advance(self):
         for d in self.running:
             self.live[self.argmin[d], d] = self.shelfL[d].pop(0)
@@ -174,23 +204,31 @@ class HostJointState(object):
         return self.higher.copy(), numpy.array([len(s) for s in self.shelfL])
 
 
-class GaussJointState(object):
-    """The joint state of the Gaussian-line problem on the GPU, bound to a
-    :class:`massivedatans_amd.like.GaussLineSpectra` (include/mdns.h Part 2b)."""
+def pack_fill_bits(beats):
+    """Fill bits as the library keeps them: bit ``k`` of the uint64 words = ``beats[k]``."""
+    words = numpy.zeros((len(beats) + 63) // 64, dtype=numpy.uint64)
+    packed = numpy.packbits(numpy.asarray(beats, dtype=numpy.uint8), bitorder='little')
+    words.view(numpy.uint8)[:len(packed)] = packed
+    return words
 
-    #: (candidate, spectrum) pairs scored per chunk at most: ~50 us of GPU time
-    EVAL_BUDGET = 2560000
-    MIN_CHUNK = 32
+
+def unpack_fill_bits(words, M):
+    """The first ``M`` fill bits of ``words`` (uint64) as a bool vector."""
+    return numpy.unpackbits(words[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+
+
+class DeviceJointState(object):
+    """A joint state in HBM behind an ``mdns_joint`` handle on ``spectra`` (include/mdns.h Part 2b): what every
+    kind of it does the same way.  A kind adds ``init`` and, where its chunks are not kernel parameter rows
+    through the entry points a native constrainer calls (``mdns_backend_draw_*``), its own ``draw_params``."""
 
     nparams = 3
+    #: the accepted candidate's likelihood row comes to the host with every draw (GaussJointState can)
+    fetch_rows = False
+    #: draws go through the entry points a native constrainer calls (GaussJointState has another route)
+    via_backend = True
 
-    def __init__(self, spectra, nlive, to_kernel_params, shelf_cap=64, fetch_rows=True, via_backend=False):
-        #: copy the accepted candidate's likelihood row to the host with every draw (the sampler
-        #: itself needs only the index and the fill bits: sample.py turns this off)
-        self.fetch_rows = fetch_rows
-        #: make ``draw`` go through the entry points a native constrainer calls
-        #: (mdns_backend_draw_begin / mdns_backend_draw_chunk; no likelihood row) -- tests
-        self.via_backend = via_backend
+    def __init__(self, spectra, nlive, to_kernel_params, shelf_cap=64):
         self._nscored = C.c_int(0)
         self._lib = _lib.require_device()
         self.spectra = spectra                             # keeps the spectra handle alive
@@ -203,7 +241,6 @@ class GaussJointState(object):
         self.running = numpy.arange(self.ndata, dtype=numpy.int32)
         self.shelf_n = numpy.zeros(self.ndata, dtype=numpy.int64)     # mirror of the device's shelf sizes
         self.cap = self._lib.mdns_joint_shelf_cap(self._h)
-        self._Lrow = numpy.empty(self.ndata)
         self._bits = numpy.zeros((self.ndata + 63) // 64, dtype=numpy.uint64)
         self._accepted = C.c_int(-1)
         self.nevals_scored = 0
@@ -226,13 +263,18 @@ class GaussJointState(object):
 
     def _beats(self, M):
         """The fill bits the last outcome left in ``_bits``: which of the ``M`` selected data sets the point beats."""
-        return numpy.unpackbits(self._bits[:(M + 63) // 64].view(numpy.uint8), bitorder='little')[:M].astype(bool)
+        return unpack_fill_bits(self._bits, M)
 
-    def init(self, xs):
-        params = _lib.as_f64(self.to_kernel_params(xs))
-        if params.shape != (self.nlive, 3):
-            raise ValueError("initial points must be [nlive, 3]")
-        self._check(self._lib.mdns_joint_init_gauss(self._h, _lib.ptr(params), self.noise_level), "mdns_joint_init_gauss")
+    def _init_jitter(self, jitter):
+        """The noise block ``init`` adds to the initial points' likelihoods, checked (None stays None)."""
+        if jitter is not None:
+            jitter = _lib.as_f64(jitter)
+            if jitter.shape != (self.nlive, self.ndata):
+                raise ValueError("jitter must be [nlive, ndata]")
+        return jitter
+
+    def _initialised(self):
+        """(the end of every ``init``: empty shelves, nlive x ndata pairs scored)"""
         self.shelf_n[:] = 0
         self.nevals_scored += self.nlive * self.ndata
         self.ncalls += 1
@@ -266,56 +308,56 @@ class GaussJointState(object):
         return Lmin, arg.astype(int), keep
 
     def chunk_size(self, offered, M, hint=None):
-        """How many of the offered candidates one launch scores: four times the tries the last
-        draw needed (``hint``), within a budget of (candidate, spectrum) pairs."""
-        budget = max(self.MIN_CHUNK, self.EVAL_BUDGET // max(1, M))
-        if hint is not None:
-            budget = min(budget, max(self.MIN_CHUNK, 4 * int(hint)))
-        return int(min(offered, budget, _lib.JOINT_MAX_BATCH))
+        """How many of the offered candidates one chunk scores (the library's own choice)."""
+        return int(self._lib.mdns_backend_chunk_size(self._h, int(offered), int(M), int(hint or 1)))
 
     def took(self, rows, beats):
-        """A draw made through the native constrainer (mdns_backend_draw_chunk on this state's
-        handle) put its point on the shelves of ``rows[beats]``: keep the mirror of the sizes."""
+        """A point went onto the shelves of ``rows[beats]`` (``rows`` None: of ``beats``): the mirror of the
+        sizes follows.  A parameter draw of this state says so itself; whoever reaches the handle another
+        way -- a native constrainer (mdns_backend_draw_chunk), a test -- calls this."""
         if rows is None:
             self.shelf_n[beats] += 1
         else:
             self.shelf_n[rows[beats]] += 1
 
+    def _selection(self, rows):
+        """``rows`` as the library takes a selection, and how many data sets it names."""
+        if rows is None:
+            return None, self.ndata
+        rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
+        return rows, len(rows)
+
+    def _outcome(self, B, M):
+        """What a chunk handed over another way than :meth:`draw_params` left: ``(idx, None, beats, B)`` as ``draw``
+        answers (whether the point counts into the mirror is the caller's)."""
+        self.ncalls += 1
+        self.nevals_scored += B * M
+        idx = self._accepted.value
+        if idx < 0:
+            return -1, None, None, B
+        return idx, None, self._beats(M), B
+
     def draw(self, xs, rows):
-        B = min(len(xs), _lib.JOINT_MAX_BATCH)
-        return self.draw_params(self.to_kernel_params(xs[:B]), rows)
+        return self.draw_params(self.to_kernel_params(xs[:_lib.JOINT_MAX_BATCH]), rows)
 
     def draw_params(self, params, rows, jitter=None):
-        """``draw`` for candidates given as kernel parameter rows (A, mu, sig)."""
+        """``draw`` for candidates given as kernel parameter rows, through the entry points a native constrainer
+        calls (mdns_backend_draw_begin / mdns_backend_draw_chunk; no likelihood row); ``jitter`` [B, M] is added
+        to their likelihoods before anything is compared or kept.  (Every chunk of a run that is not a native
+        constrainer's own comes through here: the steps stand in line, without helpers.)"""
         M = self.ndata if rows is None else len(rows)
-        if jitter is not None:
-            if not self.via_backend:
-                raise ValueError("likelihood jitter goes through the backend entry points")
-            jitter = _lib.as_f64(jitter)
         B = min(len(params), _lib.JOINT_MAX_BATCH)
+        if B == 0 or M == 0:
+            return -1, None, None, B
         params = _lib.as_f64(params[:B])
         if rows is not None:
             rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
-        if self.via_backend:
-            if B == 0 or M == 0:
-                return -1, None, None, B
-            self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows), M), "mdns_backend_draw_begin")
-            self._check(self._lib.mdns_backend_draw_chunk(self._h, _lib.ptr(params), B, _lib.opt(jitter), C.addressof(self._accepted),
-                                                          _lib.ptr(self._bits), C.addressof(self._nscored)),
-                        "mdns_backend_draw_chunk")
-            self.ncalls += 1
-            self.nevals_scored += B * M
-            idx = self._accepted.value
-            if idx < 0:
-                return -1, None, None, B
-            beats = self._beats(M)
-            self.took(rows, beats)
-            return idx, None, beats, B
-        self._reserve_for(rows)
-        self._check(self._lib.mdns_joint_draw_gauss(
-            self._h, _lib.ptr(params), B, self.noise_level, _lib.opt(rows), M,
-            C.byref(self._accepted), _lib.opt(self._Lrow if self.fetch_rows else None), _lib.ptr(self._bits)),
-            "mdns_joint_draw_gauss")
+        if jitter is not None:
+            jitter = _lib.as_f64(jitter)
+        self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows), M), "mdns_backend_draw_begin")
+        self._check(self._lib.mdns_backend_draw_chunk(self._h, _lib.ptr(params), B, _lib.opt(jitter), C.addressof(self._accepted),
+                                                      _lib.ptr(self._bits), C.addressof(self._nscored)),
+                    "mdns_backend_draw_chunk")
         self.ncalls += 1
         self.nevals_scored += B * M
         idx = self._accepted.value
@@ -323,11 +365,10 @@ class GaussJointState(object):
             return -1, None, None, B
         beats = self._beats(M)
         self.took(rows, beats)
-        return idx, (self._Lrow[:M].copy() if self.fetch_rows else None), beats, B
+        return idx, None, beats, B
 
-    # the two halves of a chunk through the entry points a native constrainer uses (include/mdns.h:
-    # mdns_backend_draw_score / mdns_backend_draw_commit): what parallel.ShardedJointState puts the MAX
-    # all-reduce of the candidates' votes between.  Both kinds of state (Gaussian line, MUSE-style).
+    # the two halves of a chunk (include/mdns.h: mdns_backend_draw_score / mdns_backend_draw_commit): what
+    # parallel.ShardedJointState puts the MAX all-reduce of the candidates' votes between
     def score_backend(self, params, rows, jitter=None):
         """Scores the chunk against the selected data sets ``rows`` (ORIGINAL indices of this state's
         spectra, ascending; None: all); one 0 / 1 vote per candidate stays on the device
@@ -335,16 +376,14 @@ class GaussJointState(object):
         B = len(params)
         if B > _lib.JOINT_MAX_BATCH:
             raise ValueError("at most %d candidates per chunk" % _lib.JOINT_MAX_BATCH)
-        M = self.ndata if rows is None else len(rows)
-        params = _lib.as_f64(params) if B else numpy.zeros((0, self.nparams))
-        if rows is not None:
-            rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
+        rows, M = self._selection(rows)
+        params = _lib.as_f64(params) if B else None
         if jitter is not None:
             jitter = _lib.as_f64(jitter)
             if jitter.shape != (B, M):
                 raise ValueError("jitter must be [B, M]")
         self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows if M else None), M), "mdns_backend_draw_begin")
-        self._check(self._lib.mdns_backend_draw_score(self._h, _lib.opt(params if B else None), B, _lib.opt(jitter if B * M else None)),
+        self._check(self._lib.mdns_backend_draw_score(self._h, _lib.opt(params), B, _lib.opt(jitter if B * M else None)),
                     "mdns_backend_draw_score")
         self._half = (rows, M, B)
         self.nevals_scored += B * M
@@ -366,17 +405,17 @@ class GaussJointState(object):
             self._check(self._lib.mdns_h2d(self.votes_address(), _lib.ptr(votes), votes.nbytes), "mdns_h2d")
 
     def commit_backend(self):
-        """The first candidate that has a vote now is the accepted point: (its index or -1, which of the
-        selected data sets of THIS state it beats)."""
+        """The first candidate that has a vote now is the accepted point: (its index or -1, None -- no
+        likelihood row leaves the device --, which of the selected data sets of THIS state it beats)."""
         rows, M, B = self._half
         self._check(self._lib.mdns_backend_draw_commit(self._h, C.addressof(self._accepted), _lib.ptr(self._bits)),
                     "mdns_backend_draw_commit")
         idx = self._accepted.value
         if idx < 0 or M == 0:
-            return idx, numpy.zeros(M, dtype=bool)
+            return idx, None, numpy.zeros(M, dtype=bool)
         beats = self._beats(M)
         self.took(rows, beats)
-        return idx, beats
+        return idx, None, beats
 
     def _reserve_for(self, rows):
         """Room on the device's shelves for one more point on the fullest shelf of ``rows`` (by the mirror of the sizes)."""
@@ -384,58 +423,6 @@ class GaussJointState(object):
         if nmax + 1 > self.cap:
             self._check(self._lib.mdns_joint_reserve(self._h, nmax + 1), "mdns_joint_reserve")
             self.cap = self._lib.mdns_joint_shelf_cap(self._h)
-
-    # the two halves of draw() (include/mdns.h: mdns_joint_score / mdns_joint_commit)
-    def score(self, xs, rows):
-        """Scores the chunk; the accept flags stay on the device (``flags`` / ``set_flags`` /
-        ``flags_address`` reach them)."""
-        return self.score_params(self.to_kernel_params(xs) if len(xs) else numpy.zeros((0, 3)), rows)
-
-    def score_params(self, params, rows):
-        """``score`` for candidates given as kernel parameter rows (A, mu, sig)."""
-        xs = params
-        B = len(xs)
-        if B > _lib.JOINT_MAX_BATCH:
-            raise ValueError("at most %d candidates per chunk" % _lib.JOINT_MAX_BATCH)
-        if rows is not None:
-            rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
-        M = self.ndata if rows is None else len(rows)
-        self._reserve_for(rows)
-        params = _lib.as_f64(params) if B else numpy.zeros((0, 3))
-        self._scored_rows, self._scored_B = rows, B
-        self._check(self._lib.mdns_joint_score(self._h, _lib.ptr(params), B, self.noise_level, _lib.opt(rows if M else None), M),
-                    "mdns_joint_score")
-        self.nevals_scored += B * M
-        self.ncalls += 1
-
-    def flags_address(self):
-        return self._lib.mdns_joint_flags_dev(self._h)
-
-    def flags(self):
-        out = numpy.zeros(self._scored_B, dtype=numpy.int32)
-        if self._scored_B:
-            self._check(self._lib.mdns_d2h(_lib.ptr(out), self.flags_address(), out.nbytes), "mdns_d2h")
-        return out
-
-    def set_flags(self, flags):
-        flags = numpy.ascontiguousarray(flags, dtype=numpy.int32)
-        if len(flags):
-            self._check(self._lib.mdns_h2d(self.flags_address(), _lib.ptr(flags), flags.nbytes), "mdns_h2d")
-
-    def commit(self, idx=None):
-        """The first flagged candidate (``idx`` is only checked against it) is the accepted point."""
-        rows = self._scored_rows
-        M = self.ndata if rows is None else len(rows)
-        self._check(self._lib.mdns_joint_commit(self._h, C.byref(self._accepted), _lib.opt(self._Lrow if self.fetch_rows else None),
-                                                _lib.ptr(self._bits)), "mdns_joint_commit")
-        got = self._accepted.value
-        if M == 0:
-            return (numpy.zeros(0) if self.fetch_rows else None), numpy.zeros(0, dtype=bool)
-        if got < 0 or (idx is not None and got != idx):
-            raise _lib.MdnsError("mdns_joint_commit accepted candidate %d, expected %s" % (got, idx))
-        beats = self._beats(M)
-        self.took(rows, beats)
-        return (self._Lrow[:M].copy() if self.fetch_rows else None), beats
 
     def advance(self):
         self._check(self._lib.mdns_joint_advance(self._h), "mdns_joint_advance")
@@ -455,37 +442,81 @@ class GaussJointState(object):
         return higher, n.astype(int)
 
 
-class MuseJointState(GaussJointState):
+class GaussJointState(DeviceJointState):
+    """The joint state of the Gaussian-line problem on the GPU, bound to a
+    :class:`massivedatans_amd.like.GaussLineSpectra`."""
+
+    #: (candidate, spectrum) pairs scored per chunk at most: ~50 us of GPU time
+    EVAL_BUDGET = 2560000
+    MIN_CHUNK = 32
+
+    def __init__(self, spectra, nlive, to_kernel_params, shelf_cap=64, fetch_rows=True, via_backend=False):
+        super(GaussJointState, self).__init__(spectra, nlive, to_kernel_params, shelf_cap=shelf_cap)
+        #: copy the accepted candidate's likelihood row to the host with every draw (the sampler
+        #: itself needs only the index and the fill bits: sample.py turns this off)
+        self.fetch_rows = fetch_rows
+        #: make ``draw`` go through the entry points a native constrainer calls
+        #: (mdns_backend_draw_begin / mdns_backend_draw_chunk; no likelihood row) -- tests
+        self.via_backend = via_backend
+        self._Lrow = numpy.empty(self.ndata)
+
+    def init(self, xs):
+        params = _lib.as_f64(self.to_kernel_params(xs))
+        if params.shape != (self.nlive, 3):
+            raise ValueError("initial points must be [nlive, 3]")
+        self._check(self._lib.mdns_joint_init_gauss(self._h, _lib.ptr(params), self.noise_level), "mdns_joint_init_gauss")
+        self._initialised()
+
+    def chunk_size(self, offered, M, hint=None):
+        """How many of the offered candidates one launch scores: four times the tries the last
+        draw needed (``hint``), within a budget of (candidate, spectrum) pairs."""
+        budget = max(self.MIN_CHUNK, self.EVAL_BUDGET // max(1, M))
+        if hint is not None:
+            budget = min(budget, max(self.MIN_CHUNK, 4 * int(hint)))
+        return int(min(offered, budget, _lib.JOINT_MAX_BATCH))
+
+    def draw_params(self, params, rows, jitter=None):
+        """``draw`` for candidates given as kernel parameter rows (A, mu, sig): through the backend entry points
+        (``via_backend``), or in one call that can hand the likelihood row over (mdns_joint_draw_gauss)."""
+        if self.via_backend:
+            return DeviceJointState.draw_params(self, params, rows, jitter)
+        if jitter is not None:
+            raise ValueError("likelihood jitter goes through the backend entry points")
+        rows, M = self._selection(rows)
+        B = min(len(params), _lib.JOINT_MAX_BATCH)
+        params = _lib.as_f64(params[:B])
+        self._reserve_for(rows)
+        self._check(self._lib.mdns_joint_draw_gauss(
+            self._h, _lib.ptr(params), B, self.noise_level, _lib.opt(rows), M,
+            C.byref(self._accepted), _lib.opt(self._Lrow if self.fetch_rows else None), _lib.ptr(self._bits)),
+            "mdns_joint_draw_gauss")
+        idx, _, beats, _ = self._outcome(B, M)
+        if idx < 0:
+            return -1, None, None, B
+        self.took(rows, beats)
+        return idx, (self._Lrow[:M].copy() if self.fetch_rows else None), beats, B
+
+
+class MuseJointState(DeviceJointState):
     """The joint state of the MUSE-style problem on the GPU: spectra with per-pixel variances
     (:class:`massivedatans_amd.like.MuseSpectra`), the template evaluated on the device from the
     parameters -- 5 of the built-in three lines, G + 2 of the spectra's line list --, the
-    scale-marginalised likelihood of cmuselike.c:45-64.  Draw chunks go through the entry points a
-    native constrainer calls (``mdns_backend_draw_*``)."""
-
-    nparams = 5
+    scale-marginalised likelihood of cmuselike.c:45-64."""
 
     def __init__(self, spectra, nlive, shelf_cap=64):
-        super(MuseJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
+        super(MuseJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap)
         self.nparams = int(self._lib.mdns_spectra_nparams(spectra.handle))
 
     def init(self, xs, jitter=None):
         params = _lib.as_f64(xs)
         if params.shape != (self.nlive, self.nparams):
             raise ValueError("initial points must be [nlive, %d]" % self.nparams)
-        if jitter is not None:
-            jitter = _lib.as_f64(jitter)
-            if jitter.shape != (self.nlive, self.ndata):
-                raise ValueError("jitter must be [nlive, ndata]")
-        self._check(self._lib.mdns_joint_init_muse3(self._h, _lib.ptr(params), _lib.opt(jitter)), "mdns_joint_init_muse3")
-        self.shelf_n[:] = 0
-        self.nevals_scored += self.nlive * self.ndata
-        self.ncalls += 1
-
-    def chunk_size(self, offered, M, hint=None):
-        return int(self._lib.mdns_backend_chunk_size(self._h, int(offered), int(M), int(hint or 1)))
+        self._check(self._lib.mdns_joint_init_muse3(self._h, _lib.ptr(params), _lib.opt(self._init_jitter(jitter))),
+                    "mdns_joint_init_muse3")
+        self._initialised()
 
 
-class CurveJointState(GaussJointState):
+class CurveJointState(DeviceJointState):
     """The joint state of a caller-defined model on the GPU.  ``model(xs f64[B, ndim]) -> curves [B, nx]``
     makes one model curve per candidate -- a C-contiguous float64 numpy array, or a float64 torch tensor
     on the device the library runs on, which is then read where it lies (by pointer and row stride; nothing
@@ -501,12 +532,12 @@ class CurveJointState(GaussJointState):
     are made on the device from the parameters and ``model`` is not called.
 
     A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in
-    :meth:`draw_params`.  Whoever drives the draws -- the sampler, the native core, a test -- may or may not
-    count accepted points into ``shelf_n`` itself, so :meth:`prepare` reads the shelf sizes back from the
-    device instead of trusting the mirror."""
+    :meth:`draw_params`.  A curve chunk does not count its point into ``shelf_n``: whoever drives the draws
+    -- the sampler, the native core, a test -- may or may not do so itself (:meth:`took`), so
+    :meth:`prepare` reads the shelf sizes back from the device instead of trusting the mirror."""
 
     def __init__(self, spectra, nlive, model, shelf_cap=64, ndim=None, table=None):
-        super(CurveJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap, fetch_rows=False, via_backend=True)
+        super(CurveJointState, self).__init__(spectra, nlive, lambda xs: xs, shelf_cap=shelf_cap)
         self.model = model
         self.nx = int(spectra.nx)
         # what a model curve holds: the bins of the spectra's response, or -- without one -- the channels
@@ -554,10 +585,7 @@ class CurveJointState(GaussJointState):
         if xs.ndim != 2 or len(xs) != self.nlive or (self.nparams is not None and xs.shape[1] != self.nparams):
             raise ValueError("initial points must be [nlive, ndim]")
         self.nparams = int(xs.shape[1])
-        if jitter is not None:
-            jitter = _lib.as_f64(jitter)
-            if jitter.shape != (self.nlive, self.ndata):
-                raise ValueError("jitter must be [nlive, ndata]")
+        jitter = self._init_jitter(jitter)
         if self.table is not None:
             xs = _lib.as_f64(xs)
             self._check(self._lib.mdns_joint_init_table(self._h, self.table.handle, _lib.ptr(xs), self.noise_level, _lib.opt(jitter)),
@@ -568,28 +596,17 @@ class CurveJointState(GaussJointState):
                 keep = _lib.as_f64(keep.cpu().numpy())
                 address = _lib.ptr(keep)
             self._check(self._lib.mdns_joint_init_curves(self._h, address, self.noise_level, _lib.opt(jitter)), "mdns_joint_init_curves")
-        self.shelf_n[:] = 0
-        self.nevals_scored += self.nlive * self.ndata
-        self.ncalls += 1
+        self._initialised()
 
     def prepare(self):
         self._check(self._lib.mdns_joint_get_thresholds(self._h, None, _lib.ptr(self._n32)), "mdns_joint_get_thresholds")
         self.shelf_n[:] = self._n32
         return super(CurveJointState, self).prepare()
 
-    def chunk_size(self, offered, M, hint=None):
-        return int(self._lib.mdns_backend_chunk_size(self._h, int(offered), int(M), int(hint or 1)))
-
-    def took(self, rows, beats):
-        """(``prepare`` reads the shelf sizes from the device: nothing to keep here)"""
-
-    def draw(self, xs, rows):
-        return self.draw_params(xs, rows)
-
     def draw_params(self, params, rows, jitter=None):
         """One chunk: ``params[B, ndim]`` as the model takes them (at most ``MDNS_JOINT_MAX_BATCH`` are
         looked at); ``jitter`` [B, M] is added to the likelihoods before anything is compared or kept."""
-        M = self.ndata if rows is None else len(rows)
+        rows, M = self._selection(rows)
         B = min(len(params), _lib.JOINT_MAX_BATCH)
         if B == 0 or M == 0:
             return -1, None, None, B
@@ -601,8 +618,6 @@ class CurveJointState(GaussJointState):
             address, ld, on_device, keep = None, self.n_in, False, params
         else:
             address, ld, on_device, keep = self._curves(params)
-        if rows is not None:
-            rows = numpy.ascontiguousarray(rows, dtype=numpy.int32)
         if jitter is not None:
             jitter = _lib.as_f64(jitter)[:B]
             if jitter.shape != (B, M):
@@ -618,13 +633,7 @@ class CurveJointState(GaussJointState):
         else:
             self._check(self._lib.mdns_backend_draw_curves(self._h, address, B, _lib.opt(jitter), *out), "mdns_backend_draw_curves")
         del keep
-        self.ncalls += 1
-        self.nevals_scored += B * M
-        idx = self._accepted.value
-        if idx < 0:
-            return -1, None, None, B
-        beats = self._beats(M)
-        return idx, None, beats, B
+        return self._outcome(B, M)
 
     def _jitter_to_device(self, jitter):
         """The noise block of a chunk whose curves are on the device already (a synchronous copy)."""
@@ -645,13 +654,7 @@ class CurveJointState(GaussJointState):
     def draw_gauss_params(self, params, rows):
         """A chunk of the built-in Gaussian line, ``params[B, 3]`` = (A, mu, sig), on this state (fixed-noise
         spectra only): parameter chunks and curve chunks may alternate."""
-        return GaussJointState.draw_params(self, params, rows)
-
-    # the halves of a chunk exist for sharded runs, which take parameters
-    def score_params(self, params, rows):
-        raise NotImplementedError("a curve state is driven through draw / draw_params")
-
-    score = score_backend = score_params
+        return DeviceJointState.draw_params(self, params, rows)
 
 
 _POP8 = numpy.array([bin(i).count("1") for i in range(256)], dtype=numpy.int64)
@@ -664,4 +667,5 @@ def _popcount(words):
     return _POP8[numpy.ascontiguousarray(words).view(numpy.uint8).reshape(len(words), 8)].sum(axis=1)
 
 
-__all__ = ['HostJointState', 'GaussJointState', 'MuseJointState', 'CurveJointState']
+__all__ = ['HostJointState', 'DeviceJointState', 'GaussJointState', 'MuseJointState', 'CurveJointState',
+           'pack_fill_bits', 'unpack_fill_bits']

@@ -205,28 +205,29 @@ class ShardedJointState(object):
     keeps live likelihoods, shelves and thresholds of ITS block next to its block of spectra.
     Per draw chunk the ranks exchange
 
-    * one MAX all-reduce of the accept flags (B integers): every rank learns the first candidate
+    * one MAX all-reduce of the candidates' votes (B integers): every rank learns the first candidate
       that ANY data set accepts -- not the likelihoods ``L[B, M]``;
-    * one all-gather of the accepted candidate's block: likelihoods + fill bits of the selected
-      data sets of each rank (M numbers in all), for the host bookkeeping every rank repeats.
+    * one all-gather of the accepted candidate's block: the fill bits of the selected data sets of
+      each rank, preceded by their likelihoods when the local state hands a row over (a
+      ``HostJointState`` does, a device state does not), for the host bookkeeping every rank repeats.
 
-    Per iteration: the per-data-set minima / slots / purge decisions of ``prepare`` (two tensor
-    all-gathers of fixed shape: lengths, then the padded vectors).  With the ``nccl`` backend the flags are reduced on the device
-    (RCCL reduces the state's own flag buffer in place, on the library stream, which is torch's
-    current stream); with ``gloo`` through the host.  Same interface as the single-process states."""
+    The local state is spoken to through the chunk's two halves (``jointstate``: ``score_backend``,
+    ``votes`` / ``set_votes``, ``commit_backend``), whatever its kind.  Per iteration: the per-data-set
+    minima / slots / purge decisions of ``prepare`` (two tensor all-gathers of fixed shape: lengths, then
+    the padded vectors).  With the ``nccl`` backend the votes of a device state are reduced where they lie
+    (RCCL on the library stream, or torch over a view of the state's own vote buffer); otherwise through
+    the host.  Same interface as the single-process states."""
 
     def __init__(self, local, ndata, lo, hi):
         torch, dist = _dist()
+        from .jointstate import DeviceJointState
         self.local, self.ndata, self.lo, self.hi = local, int(ndata), int(lo), int(hi)
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.bounds = shard_bounds(self.ndata, self.world)
         self.nlive = local.nlive
         self.running = np.arange(self.ndata)
-        self._device_flags = dist.get_backend() == "nccl" and hasattr(local, "flags_address")
-        if self._device_flags:
-            from . import _lib
-            # the state's own flag buffer, reduced in place
-            self._flags_t = device_view(local.flags_address(), (_lib.JOINT_MAX_BATCH,), "<i4")
+        #: the votes are reduced in place, on the device
+        self._in_place = dist.get_backend() == "nccl" and isinstance(local, DeviceJointState)
         self.nevals_scored = 0
         self.ncalls = 0
 
@@ -305,18 +306,6 @@ class ShardedJointState(object):
             at += c
         return Lmin, arg, keep
 
-    def _reduce_flags(self, B):
-        torch, dist = _dist()
-        if self._device_flags:
-            dist.all_reduce(self._flags_t[:B], op=dist.ReduceOp.MAX)
-            return self._flags_t[:B].cpu().numpy()
-        flags = torch.from_numpy(np.ascontiguousarray(self._local_flags, dtype=np.int32)).to(_device())
-        dist.all_reduce(flags, op=dist.ReduceOp.MAX)
-        flags = flags.cpu().numpy()
-        if hasattr(self.local, "set_flags"):
-            self.local.set_flags(flags)
-        return flags
-
     @property
     def nparams(self):
         return getattr(self.local, "nparams", 3)
@@ -330,47 +319,53 @@ class ShardedJointState(object):
     def draw_params(self, params, rows, jitter=None):
         """``draw`` for candidates given as kernel parameter rows: what a native constrainer hands over
         (``constrainer.python_backend``); every rank runs the same constrainer on the same random
-        stream and meets the others here."""
+        stream and meets the others here.  One chunk: this rank scores its selected data sets, the ranks
+        MAX-reduce the candidates' votes, every rank commits the first candidate that has one, and the
+        accepted candidate's block of every rank is gathered for the bookkeeping every rank keeps."""
         torch, dist = _dist()
         mine, counts = self._mine(rows)
-        xs = params
-        B = len(xs)
-        if hasattr(self.local, "score_backend"):
-            return self._draw_halves(params, mine, counts, jitter)
+        B = len(params)
+        mine_jitter = None
         if jitter is not None:
             # every rank's constrainer drew the noise of ALL selected data sets from the common stream
             # (candidate by candidate, musefuse.py:535): this rank adds the columns of its own
             at = int(counts[:self.rank].sum())
             mine_jitter = np.ascontiguousarray(np.asarray(jitter)[:, at:at + int(counts[self.rank])])
-            self._local_flags = self.local.score_params(params, mine, jitter=mine_jitter)
-        else:
-            self._local_flags = self.local.score_params(params, mine)
-        if self._local_flags is None and not self._device_flags:
-            self._local_flags = self.local.flags()
+        self.local.score_backend(params, mine, mine_jitter)
         self.ncalls += 1
         self.nevals_scored += B * int(counts.sum())
-        flags = self._reduce_flags(B)
-        hit = np.flatnonzero(flags)
-        if len(hit) == 0:
+        direct = self._direct() if self._in_place else None
+        if direct is not None:
+            # in place, on the stream the kernels run on
+            rccl, comm, stream = direct
+            comm.all_reduce(self.local.votes_address(), self.local.votes_address(), B, rccl.INT32, rccl.MAX, stream)
+        elif self._in_place:
+            from . import _lib
+            votes_t = device_view(self.local.votes_address(), (_lib.JOINT_MAX_BATCH,), "<i4")
+            dist.all_reduce(votes_t[:B], op=dist.ReduceOp.MAX)
+        else:
+            votes = torch.from_numpy(self.local.votes()).to(_device())
+            dist.all_reduce(votes, op=dist.ReduceOp.MAX)
+            self.local.set_votes(votes.cpu().numpy())
+        idx, Lrow, beats = self.local.commit_backend()
+        # (every rank found the same first voted candidate; -1: nobody accepted anything)
+        if idx < 0:
             return -1, None, None, B
-        idx = int(hit[0])
-        Lrow, beats = self.local.commit(idx)
         # the accepted candidate's block of every rank: likelihoods (when the local state hands
         # them over), then fill bits
-        width = int(counts.max())
-        block = np.zeros(2 * width)
+        width, nrow = int(counts.max()), (1 if Lrow is None else 2)
+        block = np.zeros((nrow, width))
         if Lrow is not None:
-            block[:len(Lrow)] = Lrow
-        block[width:width + len(beats)] = beats
-        mine_t = torch.from_numpy(block).to(_device())
-        gathered = torch.empty(self.world * 2 * width, dtype=mine_t.dtype, device=_device())
+            block[0, :len(Lrow)] = Lrow
+        block[-1, :len(beats)] = beats
+        mine_t = torch.from_numpy(block.ravel()).to(_device())
+        gathered = torch.empty(self.world * nrow * width, dtype=mine_t.dtype, device=_device())
         dist.all_gather_into_tensor(gathered, mine_t)
-        g = gathered.cpu().numpy().reshape(self.world, 2, width)
+        g = gathered.cpu().numpy().reshape(self.world, nrow, width)
         L = np.concatenate([g[r, 0, :counts[r]] for r in range(self.world)]) if Lrow is not None else None
-        b = np.concatenate([g[r, 1, :counts[r]] for r in range(self.world)]) != 0
+        b = np.concatenate([g[r, -1, :counts[r]] for r in range(self.world)]) != 0
         return idx, L, b, B
 
-    # ---- the chunk in two halves on the device (local states on the GPU) -------------------------
     def _direct(self):
         """RCCL called directly on the library's stream (massivedatans_amd.rccl), or None: backend not
         nccl, library not bindable, or MDNS_SHARDED_COLLECTIVES=torch."""
@@ -384,49 +379,9 @@ class ShardedJointState(object):
                     comm = rccl.from_torch_distributed()
                     stream = _lib.require_device().mdns_get_stream()
                     self._rccl = (rccl, comm, stream)
-                    self._allbits = None
                 except Exception:       # noqa: BLE001 -- the torch path is always there
                     self._rccl = None
         return self._rccl
-
-    def _draw_halves(self, params, mine, counts, jitter):
-        """One chunk: this rank scores its selected data sets (votes on the device), the ranks MAX-reduce
-        the votes -- in place, on the stream the kernels run on -- every rank commits the first candidate
-        that has a vote, and the fill bits of all ranks are gathered for the bookkeeping every rank keeps."""
-        torch, dist = _dist()
-        from . import _lib
-        B = len(params)
-        mine_jitter = None
-        if jitter is not None:
-            at = int(counts[:self.rank].sum())
-            mine_jitter = np.ascontiguousarray(np.asarray(jitter)[:, at:at + int(counts[self.rank])])
-        self.local.score_backend(params, mine, mine_jitter)
-        self.ncalls += 1
-        self.nevals_scored += B * int(counts.sum())
-        direct = self._direct()
-        if direct is not None:
-            rccl, comm, stream = direct
-            comm.all_reduce(self.local.votes_address(), self.local.votes_address(), B, rccl.INT32, rccl.MAX, stream)
-        elif dist.get_backend() == "nccl":
-            votes_t = device_view(self.local.votes_address(), (_lib.JOINT_MAX_BATCH,), "<i4")
-            dist.all_reduce(votes_t[:B], op=dist.ReduceOp.MAX)
-        else:
-            votes = torch.from_numpy(self.local.votes())
-            dist.all_reduce(votes, op=dist.ReduceOp.MAX)
-            self.local.set_votes(votes.numpy())
-        idx, beats = self.local.commit_backend()
-        # (every rank found the same first voted candidate; -1: nobody accepted anything)
-        if idx < 0:
-            return -1, None, None, B
-        width = int(counts.max())
-        block = np.zeros(width)
-        block[:len(beats)] = beats
-        mine_t = torch.from_numpy(block).to(_device())
-        gathered = torch.empty(self.world * width, dtype=mine_t.dtype, device=_device())
-        dist.all_gather_into_tensor(gathered, mine_t)
-        g = gathered.cpu().numpy().reshape(self.world, width)
-        b = np.concatenate([g[r, :counts[r]] for r in range(self.world)]) != 0
-        return idx, None, b, B
 
     def advance(self):
         self.local.advance()

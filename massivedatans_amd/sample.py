@@ -127,17 +127,16 @@ def native_context(joint, prior, ndata):
     """The shared part of the native constrainers (massivedatans_amd.constrainer) for a joint
     state, or None where they cannot run (library not built).  With the data sets sharded over
     ranks every rank runs the same constrainer on the same random stream; its chunks go through
-    ``ShardedJointState.draw_params``, where the ranks exchange their accept flags."""
+    ``ShardedJointState.draw_params``, where the ranks exchange their candidates' votes."""
     from . import constrainer, parallel
-    from .jointstate import CurveJointState, GaussJointState, HostJointState
+    from .jointstate import CurveJointState, DeviceJointState, HostJointState
     if not constrainer.available():
         return None
-    if isinstance(joint, CurveJointState):
-        # the model is a Python function: the chunks of a draw come back through it
-        backend = constrainer.python_backend(joint)
-    elif isinstance(joint, GaussJointState):
+    if isinstance(joint, DeviceJointState) and not isinstance(joint, CurveJointState):
+        # on the device, model included: the library's own backend on the state's handle
         backend = constrainer.hip_backend(joint)
-    elif isinstance(joint, (HostJointState, parallel.ShardedJointState)):
+    elif isinstance(joint, (CurveJointState, HostJointState, parallel.ShardedJointState)):
+        # (a curve state's model is a Python function: the chunks of a draw come back through it)
         backend = constrainer.python_backend(joint)
     else:
         return None
@@ -178,8 +177,8 @@ def build_sampler(problem, nlive_points=400, nsuperset_draws=10, use_graph=False
     cc = CachedConstrainer()
     _, _, individual_draw_constrained = generate_individual_constrainer()
     # the graph variant of the grouping runs on the device when the likelihoods do
-    from .jointstate import GaussJointState
-    on_device = isinstance(joint, GaussJointState) or isinstance(getattr(joint, 'local', None), GaussJointState)
+    from .jointstate import DeviceJointState
+    on_device = isinstance(joint, DeviceJointState) or isinstance(getattr(joint, 'local', None), DeviceJointState)
     device_groups = use_graph and on_device and os.environ.get('MDNS_DEVICE_GROUPS', '1') != '0'
     if core is None:
         core = context is not None and os.environ.get('MDNS_NATIVE_CORE', '1') != '0'

@@ -98,7 +98,7 @@ def child_k1(d):
         bits.ctypes.data_as(C.POINTER(C.c_ulonglong)), params.ctypes.data_as(C.POINTER(C.c_double))), "chain_end")
     dev._check(lib.mdns_backend_region_radius(dev._h, region, C.byref(radius)), "region_radius")
     lib.mdns_backend_region_destroy(dev._h, region)
-    beats = np.unpackbits(bits[:(M + 63) // 64].view(np.uint8), bitorder="little")[:M].astype(bool)
+    beats = jointstate.unpack_fill_bits(bits, M)
     if accepted.value >= 0:
         dev.took(rows, beats)
     out.append(dict(counts=counts.tolist(), nkept=nkept.value, B=B.value, accepted=accepted.value, radius=radius.value.hex(),
@@ -110,7 +110,7 @@ def child_k1(d):
     # a chunk in two halves (the votes)
     dev.score_backend(d["params_c"], d["rows_c"])
     votes = dev.votes()
-    idx, beats = dev.commit_backend()
+    idx, _, beats = dev.commit_backend()
     out.append([votes.tolist(), int(idx), _bits(beats), _state(dev)])
     # accepted points pile up on shelves of four: the shelves are replaced by larger ones
     for k in range(int(d["nfill"])):
