@@ -371,6 +371,8 @@ int mdns_joint_restore_live_dev(mdns_joint *j, const double *d_liveL);
 /* Takes back the last mdns_joint_advance[_dev]: every running data set's replaced live slot gets
  * the likelihood back that the preceding prepare found there; shelves emptied (bench.py). */
 int mdns_joint_undo_advance_dev(mdns_joint *j);
+/* The live matrix f64[nlive, ndata] where it lies, to read: the entries above are its only writers (a commit trusts what
+ * the last prepare saw of a column until one of them, or the next prepare, says otherwise). */
 const double *mdns_joint_live_dev(mdns_joint *j);
 
 /* K3 on device: d_members f64[K,ndim], d_cands f64[M,ndim]; d_counts int32[M] is

@@ -317,6 +317,16 @@ int gauss_cols_tile(int M, int B);
 // (d_zero, nzero): a small int buffer the kernel clears on the way (accept flags + result header)
 bool launch_gauss_model_t(const double *d_x, int nx, const double *d_params, int B, int bt,
                           double *d_model_t, int *d_zero = nullptr, int nzero = 0);
+// What k_joint_prepare saw of a data set's live column when it fixed the threshold, for the appends that follow
+// (shelf_append): with it they need no second pass over the column.  It describes the column as it stood in epoch
+// `epoch` of the state; every entry that writes live values starts a new epoch (joint_new_epoch, mdns_joint.hip), so a
+// record never outlives the column it was read from.  Zeroed memory is no record: epochs start at 1.
+struct alignas(32) JointRecord {
+	double key;                    // the threshold prepare wrote to higher[d]
+	double next;                   // the smallest live value > key, +inf if there is none
+	unsigned long long epoch;      // JointArrays::epoch when it was written
+	int cnt, pad;                  // live values <= key
+};
 // device arrays of the joint sampler state (mdns_joint.hip), all indexed by original data set
 struct JointArrays {
 	double *live;      // [nlive][ndata]   live-point likelihoods (multi_nested_sampler.py:111)
@@ -324,6 +334,8 @@ struct JointArrays {
 	int *shelfn;       // [ndata]          how many
 	double *higher;    // [ndata]          threshold of the next draw (:438-447)
 	int nlive, cap, ndata;
+	JointRecord *rec;  // [ndata]          prepare's view of the live column (a NaN live value: not counted, never `next`)
+	unsigned long long epoch;              // the state's current epoch: a record of another one is not used
 };
 // what a chunk of a constrained draw leaves for the host (mdns.h, mdns_joint_commit_dev)
 struct JointHeader { int accepted; int status; long long pad; };
@@ -591,32 +603,45 @@ __device__ __forceinline__ double wave_sum(double v)
 // jointstate.py).  With n waiting the threshold was the (n+1)-th smallest of live + shelf, and L lies above it: the
 // (n+2)-th smallest of the enlarged set is the old threshold again when it occurs more than once, else the smaller of
 // L and the next value above it.  False, and nothing changed, when the shelf is full: the caller raises its status
-// bit.  One lane per data set: no two callers share state.  U live-point loads are in flight at a time (the latency
-// of a round trip, not the count, is what this pass costs); counts and fmin do not depend on the order, so neither
-// does the result on U.
+// bit.  One lane per data set: no two callers share state.
+// The live part of the two questions -- how many values at or below thr, which is the next one above -- is answered by
+// prepare's record when that is of this epoch and for this very threshold (a first append since prepare, or a later one
+// after appends that left the threshold where it was): then only the n shelf entries are walked.  Otherwise (the
+// threshold has moved, or there is no record) the column is scanned, U live-point loads in flight at a time (the latency
+// of a round trip, not the count, is what this pass costs).  Counts and fmin do not depend on the order, so the result
+// depends neither on U nor on which of the two answered.
 template <int U>
 __device__ __forceinline__ bool shelf_append(const JointArrays &st, int d, double L, double thr)
 {
+	// shelfn[d], the record and the caller's higher[d] leave together: nothing branches on one of them before all are
+	// asked for (the full shelf is refused below, in front of the stores: with a branch up here the compiler moves the
+	// other loads behind it)
 	const int n = st.shelfn[d];
-	if (n >= st.cap) return false;
+	const JointRecord rec = st.rec[d];
 	int at_most = 0;
 	double next = INFINITY;
-	int p = 0;
-	for (; p + U <= st.nlive; p += U) {
-		double v[U];
+	if (rec.epoch == st.epoch && rec.key == thr) {
+		at_most = rec.cnt;
+		next = rec.next;
+	} else {
+		int p = 0;
+		for (; p + U <= st.nlive; p += U) {
+			double v[U];
 #pragma unroll
-		for (int u = 0; u < U; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
+			for (int u = 0; u < U; u++) v[u] = st.live[(size_t) (p + u) * st.ndata + d];
 #pragma unroll
-		for (int u = 0; u < U; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
-	}
-	for (; p < st.nlive; p++) {
-		const double v = st.live[(size_t) p * st.ndata + d];
-		if (v <= thr) at_most++; else next = fmin(next, v);
+			for (int u = 0; u < U; u++) { if (v[u] <= thr) at_most++; else next = fmin(next, v[u]); }
+		}
+		for (; p < st.nlive; p++) {
+			const double v = st.live[(size_t) p * st.ndata + d];
+			if (v <= thr) at_most++; else next = fmin(next, v);
+		}
 	}
 	for (int e = 0; e < n; e++) {
 		const double v = st.shelfL[(size_t) e * st.ndata + d];
 		if (v <= thr) at_most++; else next = fmin(next, v);
 	}
+	if (n >= st.cap) return false;
 	st.shelfL[(size_t) n * st.ndata + d] = L;
 	st.shelfn[d] = n + 1;
 	st.higher[d] = at_most >= n + 2 ? thr : fmin(L, next);

@@ -75,11 +75,13 @@ __global__ __launch_bounds__(kBlock) void k_joint_prepare(JointArrays st, const 
 		lv[u] = st.live[(size_t) (p < st.nlive ? p : 0) * nd + d];
 	}
 	const int n0 = st.shelfn[d];
+	// (the index is kept inside the shelf by its capacity, a kernel argument, so these loads leave with the ones above
+	// and do not wait for n0; what lies at and beyond n0 is replaced by NaN below)
 	double sv[kHeld];                                            // shelf entries sl, sl + 16, ...
 #pragma unroll
 	for (int u = 0; u < kHeld; u++) {
 		const int e = sl + kSlices * u;
-		sv[u] = st.shelfL[(size_t) (e < n0 ? e : 0) * nd + d];
+		sv[u] = st.shelfL[(size_t) (e < st.cap ? e : 0) * nd + d];
 	}
 	double m = INFINITY;
 	int am = 0x7fffffff;
@@ -197,7 +199,18 @@ __global__ __launch_bounds__(kBlock) void k_joint_prepare(JointArrays st, const 
 		const int total = over_slices(count, [](int x, int y) { return x + y; });
 		if (!done) { if (total >= target) hi = pivot; else lo = pivot; }
 	}
+	// the record for the appends of this iteration (JointRecord; the two statements are shelf_append's own): the live
+	// values are still in the registers
+	int cnt = 0;
+	double next = INFINITY;
+	auto note = [&](double v) { if (v <= thr) cnt++; else next = fmin(next, v); };
+#pragma unroll
+	for (int u = 0; u < kHeld; u++) note(lv[u]);
+	for (int p = sl + kSlices * kHeld; p < st.nlive; p += kSlices) note(st.live[(size_t) p * nd + d]);
+	cnt = over_slices(cnt, [](int x, int y) { return x + y; });
+	next = over_slices(next, [](double x, double y) { return fmin(x, y); });
 	if (!real || sl != 0) return;
+	st.rec[d] = JointRecord{thr, next, st.epoch, cnt, 0};
 	st.higher[d] = thr;
 	Lmin[r] = m;
 	argmin_run[r] = am;
@@ -380,6 +393,7 @@ struct mdns_joint {
 	// are made, and again when mdns_joint_reserve replaces the shelves)
 	DeviceBuffer<double> live, shelfL, higher;
 	DeviceBuffer<int> shelfn;
+	DeviceBuffer<JointRecord> rec;
 	JointArrays st = {};
 	DeviceBuffer<int> d_running;  int nrun = 0;
 	DeviceBuffer<double> d_Lmin;       // [ndata] by position in the running list
@@ -475,6 +489,14 @@ struct mdns_joint {
 	int chain_n = 0;
 };
 
+// EVERY entry that puts a write of live values into the stream calls this before it returns.  The complete list:
+// joint_reset -- behind mdns_joint_set_live, mdns_joint_restore_live_dev and, through init_finish, every
+// mdns_joint_init_* with its noise pass --, mdns_joint_advance_dev and mdns_joint_undo_advance_dev; and
+// mdns_joint_prepare_dev, which writes the records of the new epoch.  The kernels launched from then on take the new
+// epoch with `st`, so no append of theirs uses what a prepare saw of a column that has changed since (JointRecord).
+// mdns_joint_reserve replaces the shelves only: the records say nothing about those.
+static void joint_new_epoch(mdns_joint *j) { j->st.epoch++; }
+
 static size_t result_bytes(int M) { return sizeof(JointHeader) + (size_t) ((M + 63) / 64) * 8 + (size_t) M * 8; }
 extern "C" size_t mdns_joint_result_bytes(int M) { return result_bytes(M > 0 ? M : 0); }
 static int keep_words_of(int cap) { return (cap + 63) / 64; }
@@ -505,7 +527,7 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	const size_t res = (size_t) kFlagInts * sizeof(int) + result_bytes(s->ndata);
 	static_assert(sizeof(JointHeader) % sizeof(int) == 0, "d_flags is counted in ints");
 	bool ok =
-	    j->live.make((size_t) nlive * nd) && j->shelfL.make((size_t) shelf_cap * nd) && j->shelfn.make(nd) && j->higher.make(nd) &&
+	    j->live.make((size_t) nlive * nd) && j->shelfL.make((size_t) shelf_cap * nd) && j->shelfn.make(nd) && j->higher.make(nd) && j->rec.make(nd) &&
 	    j->d_running.make(nd) && j->d_Lmin.make(nd) && j->d_argmin_run.make(nd) && j->d_argmin.make(nd) && j->d_status.make(1) &&
 	    j->d_flags.make(res / sizeof(int)) &&
 	    // candidates [B, 3] followed by the selection's row ids: one staging block (kCurveMarginal: candidates [B, nparams] alone)
@@ -514,10 +536,11 @@ extern "C" mdns_joint *mdns_joint_create(mdns_spectra *s, int nlive, int shelf_c
 	if (ok) {
 		j->h_box = (JointMailbox *) j->box.get(); j->h_box_dev = (JointMailbox *) j->box.dev();
 		j->d_result = (char *) (j->d_flags.get() + kFlagInts);
-		j->st = {j->live.get(), j->shelfL.get(), j->shelfn.get(), j->higher.get(), nlive, shelf_cap, s->ndata};
+		j->st = {j->live.get(), j->shelfL.get(), j->shelfn.get(), j->higher.get(), nlive, shelf_cap, s->ndata, j->rec.get(), 1};
 		std::vector<int> all(nd);
 		for (size_t i = 0; i < nd; i++) all[i] = (int) i;
 		ok = MDNS_HIP(hipMemsetAsync(j->st.shelfn, 0, nd * sizeof(int), c->stream)) &&
+		     MDNS_HIP(hipMemsetAsync(j->st.rec, 0, nd * sizeof(JointRecord), c->stream)) &&
 		     MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) &&
 		     MDNS_HIP(hipMemsetAsync(j->d_flags.get(), 0, res, c->stream)) &&
 		     MDNS_HIP(hipMemsetAsync(j->d_argmin.get(), 0, nd * sizeof(int), c->stream)) &&
@@ -561,6 +584,7 @@ static int joint_reset(mdns_joint *j)
 	Context *c = ctx();
 	j->prepared = false;
 	j->shelf_bound = 0;
+	joint_new_epoch(j);
 	return MDNS_HIP(hipMemsetAsync(j->st.shelfn, 0, (size_t) j->ndata * sizeof(int), c->stream)) &&
 	       MDNS_HIP(hipMemsetAsync(j->d_status.get(), 0, sizeof(int), c->stream)) ? 0 : 1;
 }
@@ -737,6 +761,7 @@ extern "C" int mdns_joint_undo_advance_dev(mdns_joint *j)
 	if (!c || !j) return 1;
 	if (!j->prepared) { set_error("mdns_joint_undo_advance_dev: nothing to take back"); return 1; }
 	if (j->nrun == 0) return 0;
+	joint_new_epoch(j);
 	hipLaunchKernelGGL(k_joint_undo_advance, dim3((j->nrun + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
 	                   j->st, j->d_running.get(), j->nrun, j->d_argmin.get(), j->d_Lmin.get());
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
@@ -794,6 +819,7 @@ extern "C" int mdns_joint_prepare_dev(mdns_joint *j)
 	if (!j->d_keep.fit((size_t) j->ndata * kw)) return 1;              // (room for every data set: no growth as the running list changes)
 	j->prepared = true;
 	if (j->nrun == 0) return 0;
+	joint_new_epoch(j);
 	hipLaunchKernelGGL(k_joint_prepare, dim3((j->nrun + 15) / 16), dim3(kBlock), 0, c->stream,
 	                   j->st, j->d_running.get(), j->nrun, j->d_Lmin.get(), j->d_argmin_run.get(), j->d_argmin.get(), j->d_keep.get(), kw);
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;
@@ -835,6 +861,7 @@ extern "C" int mdns_joint_advance_dev(mdns_joint *j)
 	if (!c || !j) return 1;
 	if (!j->prepared) { set_error("mdns_joint_advance: no prepare since the state was set"); return 1; }
 	if (j->nrun == 0) return 0;
+	joint_new_epoch(j);
 	hipLaunchKernelGGL(k_joint_advance, dim3((j->nrun + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
 	                   j->st, j->d_running.get(), j->nrun, j->d_argmin.get(), j->d_status.get());
 	return MDNS_HIP(hipGetLastError()) ? 0 : 1;

@@ -651,6 +651,9 @@ __global__ __launch_bounds__(2 * kBlock) void k_gauss_cols_accept(
 	const bool live = k[0] < M;
 	const int kk = live ? k[0] : M - 1;
 	// a quiet NaN compares false with everything: lanes past the selection never vote
+	// (asking for the threshold BEFORE the channel loop, so that nothing waits for it here, was measured and lost: 76 ->
+	// 78 VGPRs, and <8, false> at 10 000 x 256 took 42.1 / 43.1 us against 41.2 / 42.3 in two A/B traces; presumably the
+	// waves of a launch end staggered and hide this wait behind one another, while at the start all of them pay for it)
 	const double thr = live ? higher[thr_rows ? thr_rows[kk] : kk] : __builtin_nan("");
 #pragma unroll
 	for (int b = 0; b < BT; b++)
@@ -755,12 +758,23 @@ __global__ __launch_bounds__(kBlock) void k_joint_commit_trail(
 	const bool mine = bstar < B && tile < ntiles;
 	if (!mine && !box) return;
 	const size_t at = mine ? (size_t) bstar * ntiles + tile : 0;
-	// (a candidate flagged by another rank's data sets only has no entry here: nobody beats)
-	const unsigned long long word = mine && trail.stamp_of[at] == trail.stamp ? trail.word[at] : 0ull;
+	// everything that hangs on (bstar, tile) alone leaves in one batch -- stamp, word, likelihood, data set: one round
+	// trip instead of four behind one another (an entry of another stamp is read and not used)
 	const int k = tile * 64 + lane;
+	int stamp = 0, d = 0;
+	unsigned long long entry = 0ull;
+	double L = 0.0;
+	if (mine) {
+		stamp = trail.stamp_of[at];
+		entry = trail.word[at];
+		L = trail.L[at * 64 + lane];
+		if (k < M) d = thr_rows ? thr_rows[k] : k;
+	}
+	// (a candidate flagged by another rank's data sets only has no entry here: nobody beats)
+	const unsigned long long word = mine && stamp == trail.stamp ? entry : 0ull;
 	if (mine && k < M && (word >> lane & 1ull)) {
-		const int d = thr_rows ? thr_rows[k] : k;
-		if (!shelf_append<25>(st, d, trail.L[at * 64 + lane], st.higher[d])) atomicOr(&header->status, 1);
+		// (higher[d], shelfn[d] and the record of d leave together as well: shelf_append)
+		if (!shelf_append<25>(st, d, L, st.higher[d])) atomicOr(&header->status, 1);
 	}
 	if (!box) { if (lane == 0) fillbits[tile] = word; return; }
 	// box != nullptr: the mailbox is filled by the last workgroup to finish (hand-over of mdns_internal.h: the fill
