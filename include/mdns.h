@@ -157,7 +157,11 @@ int mdns_curve_loglike_batch(mdns_spectra *s, const double *curves, int B, doubl
 
 /* Live-point pool resident on the device: the members of a RadFriends region
  * (clustering/radfriendsregion.py:59-70 keeps `members` and `maxdistance`; every are_inside /
- * count_nearby_members call of a region's life re-uses them, radfriendsregion.py:82-98). */
+ * count_nearby_members call of a region's life re-uses them, radfriendsregion.py:82-98).
+ * Input contract of everything below (and of the cneighbors drop-ins of Part 1): member and point
+ * coordinates are not NaN.  Infinite and denormal squared distances are handled as IEEE handles
+ * them; a NaN distance is not -- the kernels that take minima with v_min_f64 / v_max_f64 (which
+ * return the non-NaN operand) and the ones that compare would answer differently. */
 typedef struct mdns_region mdns_region;
 
 /* members f64[K, ndim] on the host (copied to the device) ... */
@@ -176,7 +180,9 @@ double mdns_region_bootstrap_radius(mdns_region *r, const double *chosen, int nb
 double mdns_region_bootstrap_radius_dev(mdns_region *r, const double *d_chosen, int nbootstraps);
 /* The same with the choice matrix packed by the caller: bit b of packed[i] (uint32[K], host) is
  * set when point i is chosen in round b, i.e. chosen[i][b] != 0 (cneighbors.c:146); at most 16
- * rounds.  A twentieth of the bytes to build and to upload. */
+ * rounds.  A twentieth of the bytes to build and to upload.  Bits nbootstraps..15 are ignored;
+ * bits 16..31 MUST be zero (the opt-in sorted path keeps a flag of its own in bit 31).  The same
+ * holds for every other `packed` argument of this header. */
 double mdns_region_bootstrap_radius_packed(mdns_region *r, const unsigned *packed, int nbootstraps);
 /* The same without waiting: radius and membership threshold are finished ON the device, so a
  * following mdns_region_count_dev needs no host round trip; mdns_region_radius() then waits

@@ -315,18 +315,50 @@ extern "C" int mdns_profile_every(int n)
 	g_prof_every = n > 1 ? n : 1;
 	return 0;
 }
+// Launchers call note_kernel on every launch (the region kernels among them, on the sampler step's critical path), so
+// it only keeps the format and its arguments -- fmt is a literal with at most four %d (int) / %s (a literal) -- and
+// mdns_profile_kernel puts the name together when somebody asks for it.
+static constexpr int kNoteArgs = 4;
+struct KernelNote { const char *fmt; int narg; int num[kNoteArgs]; const char *str[kNoteArgs]; };
+static KernelNote g_kernel_note[4];
 static char g_kernel_name[4][64];
 void mdns::note_kernel(int which, const char *fmt, ...)
 {
 	if (which < 0 || which > 3) return;
+	KernelNote &n = g_kernel_note[which];
+	n.fmt = fmt;
+	n.narg = 0;
 	va_list ap;
 	va_start(ap, fmt);
-	vsnprintf(g_kernel_name[which], sizeof g_kernel_name[which], fmt, ap);
+	for (const char *p = fmt; *p && n.narg < kNoteArgs; p++) {
+		if (*p != '%') continue;
+		if (!*++p) break;
+		if (*p == 'd') { n.str[n.narg] = nullptr; n.num[n.narg++] = va_arg(ap, int); }
+		else if (*p == 's') { n.num[n.narg] = 0; n.str[n.narg++] = va_arg(ap, const char *); }
+	}
 	va_end(ap);
 }
 extern "C" const char *mdns_profile_kernel(int which)
 {
-	return which >= 0 && which <= 3 ? g_kernel_name[which] : "";
+	if (which < 0 || which > 3) return "";
+	const KernelNote &n = g_kernel_note[which];
+	char *out = g_kernel_name[which];
+	const size_t cap = sizeof g_kernel_name[which];
+	size_t len = 0;
+	int a = 0;
+	out[0] = 0;
+	for (const char *p = n.fmt; p && *p && len + 1 < cap; p++) {
+		if (*p == '%' && (p[1] == 'd' || p[1] == 's') && a < n.narg) {
+			const int w = n.str[a] ? snprintf(out + len, cap - len, "%s", n.str[a]) : snprintf(out + len, cap - len, "%d", n.num[a]);
+			len = w < 0 || len + (size_t) w >= cap ? cap - 1 : len + (size_t) w;
+			a++;
+			p++;
+		} else {
+			out[len++] = *p;
+			out[len] = 0;
+		}
+	}
+	return out;
 }
 extern "C" int mdns_profile_read(int which, long long *launches, double *total_ms)
 {

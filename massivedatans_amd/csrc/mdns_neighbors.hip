@@ -403,7 +403,8 @@ bool launch_count_within(const double *d_members, int K, int ndim, double thresh
 	const size_t lds = (size_t) tile_n * ndim * sizeof(double) + fixed;
 	dim3 grid(gx, gy);
 	ProfileScope prof(2);
-#define COUNT_LAUNCH(D) do { if (fine) hipLaunchKernelGGL((k_count_within<D, 16>), grid, dim3(kBlock), lds, c->stream, \
+#define COUNT_LAUNCH(D) do { note_kernel(2, "k_count_within<%d, %d>", D, fine ? 16 : (small ? 4 : 1)); \
+	if (fine) hipLaunchKernelGGL((k_count_within<D, 16>), grid, dim3(kBlock), lds, c->stream, \
 		d_members, K, ndim, thresh_sq, d_res, d_cands, M, d_counts, kchunk, tile_n, accumulate, post); \
 	else if (small) hipLaunchKernelGGL((k_count_within<D, 4>), grid, dim3(kBlock), lds, c->stream, \
 		d_members, K, ndim, thresh_sq, d_res, d_cands, M, d_counts, kchunk, tile_n, accumulate, post); \
@@ -451,8 +452,9 @@ static bool launch_nearest(const double *d_members, int K, int ndim, const doubl
 		BootstrapFinish fin = {nullptr, nullptr, nullptr, 0};
 		if (finish && b0 + kRounds >= nboot) fin = *finish;
 		ProfileScope prof(3);
-#define NEAR_LAUNCH_R(D, SL, RT) hipLaunchKernelGGL((k_nearest_chosen<D, NN, SL, RT>), grid, dim3(kBlock), lds, c->stream, \
-		d_members, K, ndim, d_mask, nb, d_round_sq + b0, tile_n, fin, d_round_sq, nboot, fused ? d_chosen : nullptr, nboot, b0)
+#define NEAR_LAUNCH_R(D, SL, RT) do { note_kernel(3, "k_nearest_chosen<%d, %s, %d, %d>", D, NN ? "true" : "false", SL, RT); \
+		hipLaunchKernelGGL((k_nearest_chosen<D, NN, SL, RT>), grid, dim3(kBlock), lds, c->stream, \
+		d_members, K, ndim, d_mask, nb, d_round_sq + b0, tile_n, fin, d_round_sq, nboot, fused ? d_chosen : nullptr, nboot, b0); } while (0)
 #define NEAR_LAUNCH(D) do { \
 	if (small) { if (NN || nb <= 10) NEAR_LAUNCH_R(D, 4, 10); else NEAR_LAUNCH_R(D, 4, kRounds); } \
 	else       { if (NN || nb <= 10) NEAR_LAUNCH_R(D, 1, 10); else NEAR_LAUNCH_R(D, 1, kRounds); } } while (0)
