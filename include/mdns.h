@@ -501,8 +501,11 @@ typedef struct mdns_draw_backend {
 	 * every likelihood with its threshold +- 1.01 bound[b] (bound f64[B]: no deviate of candidate b exceeds
 	 * it): status int32[B] = 1 when some selected data set is beaten whatever the noise, 0 when none can
 	 * be, 2 when that hangs on the pairs listed: pair_b / pair_k int32 (candidate, position in the
-	 * selection), pair_L / pair_thr f64 (likelihood without noise, threshold); *npairs their number (more
-	 * than cap: the caller falls back to draw_chunk with the whole block).  Nothing is committed.
+	 * selection), pair_L / pair_thr f64 (likelihood without noise, threshold); *npairs their number.  The
+	 * arrays hold cap entries and the device keeps at most 4096 pairs of a chunk: with no more pairs than
+	 * min(cap, 4096) *npairs is their true number and all of them are handed over; with more, the first
+	 * min(cap, 4096) are and *npairs > cap (the caller falls back to draw_chunk with the whole block).
+	 * Nothing is committed.
 	 * draw_band_commit: candidate b is the accepted one; jitter_row f64[M] is added to its likelihoods,
 	 * then shelves, thresholds and fill bits as in draw_chunk. */
 	int (*draw_band)(void *user, const double *params, int B, const double *bound, int *status, int *npairs,

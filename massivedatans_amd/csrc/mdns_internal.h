@@ -416,8 +416,12 @@ bool launch_muse_model(const mdns_spectra *s, const double *d_params, int B, dou
 bool launch_gauss_rows(const mdns_spectra *s, const double *d_model, int ldm, int B,
                        double scale, const int *d_rows, int M, double *d_out);
 struct MuseBandFused;
-// band != nullptr (pairs of candidates only: muse_rows_variant(...) == 1): the band test of the likelihood noise and its
-// mailbox ride along with the scoring -- no k_joint_band behind it
+// the most channels the k_muse_rows<NP, .> / k_muse_rows2<NP> instantiations take (NP <= 8); longer spectra go to
+// k_muse_rows_generic
+static constexpr int kMuseRowsNxMost = 4096;
+// band != nullptr (pairs of candidates only: muse_rows_variant(...) == 1, and nx <= kMuseRowsNxMost: the generic kernel
+// carries no vote -- refused, never dropped): the band test of the likelihood noise and its mailbox ride along with
+// the scoring -- no k_joint_band behind it
 bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int B,
                       const int *d_rows, int M, double *d_out, int B_shape = 0, const MuseBandFused *band = nullptr);
 int muse_rows_variant(int B, int M);

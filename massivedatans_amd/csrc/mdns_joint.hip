@@ -1708,8 +1708,10 @@ static int band_launch(mdns_joint *j, bool filtered)
 		const MuseBandOut out = {&j->d_band.get()->counter, j->d_band.get()->clear, j->d_band.get()->maybe, j->d_band.get()->pair_b, j->d_band.get()->pair_k,
 		                         j->d_band.get()->pair_L, j->d_band.get()->pair_thr, kBandCap, &((JointHeader *) j->d_result)->status};
 		if (!launch_muse_filter(j->s, j->s->d_model.get(), ldm, B, d_rows, M, j->st.higher, d_b, out)) return 1;
-	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w.get() && j->s->d_x.get() && j->s->continuum == 0) {
+	} else if (muse_rows_variant(B, M) == 1 && j->s->d_w.get() && j->s->d_x.get() && j->s->continuum == 0 && j->s->nx <= kMuseRowsNxMost) {
 		// small chunks (pairs of candidates per workgroup): templates, then ONE kernel that scores, votes and publishes
+		// (only k_muse_rows<NP, 2> carries the vote: past kMuseRowsNxMost channels the generic row kernel scores, so the
+		// chunk takes the dense route below, as it does with a continuum)
 		const int ldm = model_ld(j->s->nx);
 		if (!ensure_model(j->s, (size_t) B * ldm) || !launch_muse_model(j->s, d_p, B, j->s->d_model.get(), ldm)) return 1;
 		const MuseBandFused fused = {j->d_band.get(), j->h_band_dev, ++j->band_seq, j->st.higher, d_b, &((JointHeader *) j->d_result)->status};
@@ -1779,9 +1781,15 @@ extern "C" int mdns_backend_draw_band_end(void *joint, int *status, int *npairs,
 		if (band_launch(j, false) != 0) return 1;
 	}
 	memcpy(status, (const void *) j->h_band->status, (size_t) B * sizeof(int));
-	*npairs = j->h_band->npairs;
-	const int m = *npairs < cap ? (*npairs < kBandCap ? *npairs : kBandCap) : cap;
-	if (*npairs > kBandCap && *npairs <= cap) *npairs = cap + 1;          // (more than the device lists: the caller falls back)
+	// n pairs were inside the band; the device keeps the first kBandCap of them, the caller has room for `cap`.
+	// With room = min(cap, kBandCap):
+	//   n <= room: *npairs = n, all n pairs are copied
+	//   n >  room: `room` pairs are copied and *npairs > cap (n itself, or cap + 1 where n <= cap): the caller falls back
+	// Never more than kBandCap entries leave the box, whatever `cap`.
+	const int n = j->h_band->npairs;
+	const int room = cap < kBandCap ? (cap > 0 ? cap : 0) : kBandCap;
+	const int m = n < room ? n : room;
+	*npairs = n > room && n <= cap ? cap + 1 : n;
 	memcpy(pair_b, (const void *) j->h_band->pair_b, (size_t) m * sizeof(int));
 	memcpy(pair_k, (const void *) j->h_band->pair_k, (size_t) m * sizeof(int));
 	memcpy(pair_L, (const void *) j->h_band->pair_L, (size_t) m * sizeof(double));

@@ -1467,6 +1467,7 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
 		return launch_continuum_rows(s, d_model, ldm, B, d_rows, M, d_out, nullptr, nullptr);
 	}
 	if (band && muse_rows_variant(B_shape > 0 ? B_shape : B, M) != 1) { set_error("launch_muse_rows: the band test rides along with pairs of candidates only"); return false; }
+	if (band && s->nx > kMuseRowsNxMost) { set_error("launch_muse_rows: no fused band test past %d channels, nx=%d (the chunk takes the dense route)", kMuseRowsNxMost, s->nx); return false; }
 	const MuseBandFused fused = band ? *band : none;
 	Context *c = ctx();
 	const int nx = s->nx;
@@ -1486,7 +1487,7 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
 	// NP = ceil(nx / 512) exactly: a row kernel then reads 512 NP <= model_ld(nx) <= ldm doubles of a template row
 	// -- its own row and nothing behind it -- with no test on the load (what lies in [nx, 512 NP) is the zero pad)
 	const int np = nx <= 512 ? 1 : (nx + 511) / 512;
-	if (nx <= 4096) note_kernel(1, two_rows ? "k_muse_rows2<%d>" : (variant == 1 ? "k_muse_rows<%d, 2>" : "k_muse_rows<%d, 1>"), np);
+	if (nx <= kMuseRowsNxMost) note_kernel(1, two_rows ? "k_muse_rows2<%d>" : (variant == 1 ? "k_muse_rows<%d, 2>" : "k_muse_rows<%d, 1>"), np);
 	else note_kernel(1, "k_muse_rows_generic");
 #define MUSE_LAUNCH(NP) do { if (two_rows) hipLaunchKernelGGL((k_muse_rows2<NP>), dim3((blocks + 1) / 2), dim3(kBlock), 0, c->stream, \
 		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out); \
@@ -1495,7 +1496,7 @@ bool launch_muse_rows(const mdns_spectra *s, const double *d_model, int ldm, int
 	else hipLaunchKernelGGL((k_muse_rows<NP, 1>), dim3(blocks), dim3(kBlock), 0, c->stream, \
 		s->d_y.get(), s->d_w.get(), s->ld, nx, d_model, ldm, B, d_rows, M, d_out, B, none); } while (0)
 	if (ldm < model_ld(nx)) { set_error("launch_muse_rows: template rows %d apart, nx=%d needs %d", ldm, nx, model_ld(nx)); return false; }
-	switch (nx <= 4096 ? np : 0) {
+	switch (nx <= kMuseRowsNxMost ? np : 0) {
 	case 1: MUSE_LAUNCH(1); break;
 	case 2: MUSE_LAUNCH(2); break;
 	case 3: MUSE_LAUNCH(3); break;

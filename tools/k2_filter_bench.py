@@ -13,11 +13,11 @@ from massivedatans_amd import _lib, gen, jointstate, musefuse
 from massivedatans_amd.like import MuseSpectra
 
 
-def planted_state(ndata, nx, nlive, B, seed, offsets, rows=None):
+def planted_state(ndata, nx, nlive, B, seed, offsets, rows=None, continuum=0):
     """spectra, a joint state whose thresholds sit next to the likelihoods of `params`, and those"""
     rng = np.random.RandomState(seed)
     data = gen.muse_like(ndata, nx)
-    sp = MuseSpectra(data["x"], data["y"], data["v"])
+    sp = MuseSpectra(data["x"], data["y"], data["v"], continuum=continuum)
     st = jointstate.MuseJointState(sp, nlive, shelf_cap=4)
     st.init(musefuse.priortransform_batch(rng.uniform(size=(nlive, 5))))
     params = musefuse.priortransform_batch(rng.uniform(size=(B, 5)))
@@ -36,13 +36,12 @@ def planted_state(ndata, nx, nlive, B, seed, offsets, rows=None):
     return sp, st, params, L, thr
 
 
-def band(st, params, rows, bound, mode):
+def band(st, params, rows, bound, mode, cap=4096):
     lib = st._lib
     lib.mdns_muse_filter_mode(mode)
     B = len(params)
     M = st.ndata if rows is None else len(rows)
     st._check(lib.mdns_backend_draw_begin(st._h, _lib.ptr(rows) if rows is not None else None, M), "draw_begin")
-    cap = 4096
     status = np.zeros(B, dtype=np.int32)
     npairs = C.c_int(0)
     pb, pk = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
