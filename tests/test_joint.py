@@ -29,7 +29,10 @@ def test_joint_state_equals_its_numpy_statement(ndata, nlive, nx, fetch_rows):
     native constrainer calls (mdns_backend_draw_begin / _chunk) -- for selections of up to 4096
     spectra the chunk is two launches (csrc/mdns_chunk.hip: templates computed in the accept
     kernel, candidates and row ids read from mapped host memory, commit + mailbox in one
-    workgroup); the shelf capacity of 4 also makes it grow the shelves itself."""
+    workgroup); the shelf capacity of 4 also makes it grow the shelves itself.  This drive is random and
+    compares with the lane kernel; the route's edges -- every k_chunk_accept<NST> at its first and last
+    stage count, partial tiles, the commit switch at 128 | 129 spectra, the rows' hand-over from the mapped
+    block -- are planted in test_chunk_shapes.py against the high-precision statement."""
     rng = np.random.RandomState(ndata * 7 + nlive)
     data = gen.horns(ndata)
     x = np.linspace(400, 800, nx) if nx > 200 else data["x"][:nx]
