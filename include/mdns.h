@@ -1130,6 +1130,94 @@ int mdns_response_fold_batch(mdns_response *r, const double *curves, int B, doub
 int mdns_response_fold_batch_dev(mdns_response *r, const double *d_curves, int ldc, int B, double *d_out, int ldo);
 int mdns_spectra_set_response(mdns_spectra *s, mdns_response *r);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 14 -- a SUM of components as the model, evaluated on the device (csrc/mdns_sum.hip, k_sum_curves).
+ *
+ * Real analyses fit sums: absorption x (power law + line) + scattered table, population A + population B + emission
+ * line.  A sum model has 1 <= C <= MDNS_SUM_MAX_COMPONENTS components in the order they were added -- a table of Part
+ * 12 (MDNS_SUM_TABLE), a power law (MDNS_SUM_POWERLAW), a Gaussian line (MDNS_SUM_GAUSS) --, each with a flag
+ * `attenuated`, and optionally ONE common attenuation factor.  It lives on an abscissa x f64[nx], finite, 1 <= nx <=
+ * MDNS_TABLE_MAX_NX: the data's x, or under a response (Part 13) its model bins.  All float64.
+ *
+ * A candidate's row is the components' parameters one after the other in that order and, with an attenuation, N at the
+ * end; ndim = the components' parameters + (attenuation ? 1 : 0) <= MDNS_MAX_DIM.
+ *
+ * Per candidate b and bin j, every step ONE rounded fp64 operation, in this order, nothing contracted into an FMA
+ * (10 ** v is pow10_dd of csrc/mdns_pow10.h, one faithful rounding that host and device compute identically; the fma()
+ * calls inside it belong to that function); clamp is Part 12's comparison clamp to [-299, 299]:
+ *
+ *   TABLE     parameters: Part 12's row (p_1 .. p_d [, z] [, E] [, s] [, A]).  v = exactly Part 12's value for that
+ *             slice of the row on x, by either of its routes.
+ *   POWERLAW  parameters (logA, G); lx f64[nx], finite, given at creation (the Python layer: log10(x / x0)).
+ *             q = G * lx[j];  q = logA - q;  q = clamp(q);  v = pow10_dd(q)
+ *   GAUSS     parameters (A, mu, sigma): the peak amplitude, as the reference's line (sample.py:60-62).
+ *             d = (x[j] - mu) / sigma;  q = (MDNS_TABLE_BROADEN_C * d) * d;  q = clamp(q);  v = A * pow10_dd(q)
+ *             It is not cut: far from the line the value is A * 1e-299, not 0.
+ *   sums      a = +0.0, then for the attenuated components ascending  a = a + v_c;
+ *             u = +0.0, then for the others ascending  u = u + v_c.
+ *             Without an attenuation every component counts as attenuated.
+ *   attenuate (optional; att f64[nx], finite)  q = clamp(att[j] * N);  a = a * pow10_dd(q)
+ *   value     curve[b][j] = a + u
+ *
+ * A NaN anywhere in the row makes the whole row NaN.  So does a parameter of an analytic component that is not finite,
+ * a sigma that is not > 0, and an N that is not finite.  A table slice follows Part 12's own rules: a slice that Part 12
+ * makes NaN is NaN in every bin and so is the sum.  A NaN's payload is not part of the statement.  With finite
+ * parameters no step of a component's chain or of the attenuation can produce a NaN: G * lx, x - mu and att * N may
+ * overflow to +-inf, logA - q and d then stay infinite (sigma is finite and > 0, so d is never inf / inf; d = 0 gives
+ * q = -0.0 and pow10_dd(+-0.0) = 1), and the clamp catches them; pow10_dd of a clamped q lies in [1e-299, 1e299], so
+ * A * pow10_dd(q) is finite and a * pow10_dd(q) is 0 * finite or +-inf * positive at worst.  The ADDS alone can: partial
+ * sums beyond 1.8e308 of opposite sign in a and u give inf + -inf.  A value depends on its candidate and bin only --
+ * not on B, the candidate's place in the batch, ldc, the entry point, or what the handle computed before.  A model of
+ * one TABLE component without attenuation gives the table's own curves, except that -0.0 becomes +0.0 (0.0 + -0.0).
+ * The numpy statement of the same chain is massivedatans_amd/summodel.py, SumModel.statement: the two agree bit for bit.
+ *
+ * mdns_sum_create: copies x; NULL (mdns_last_error says why) for a null x, nx outside 1 .. MDNS_TABLE_MAX_NX, x[i] not
+ * finite, or a device that refuses.  The sum OWNS what its components need: mdns_sum_add_table takes
+ * mdns_table_create_los's arguments and builds that table on the sum's own x (every rule and message of Part 12, under
+ * the name mdns_sum_add_table); mdns_sum_add_powerlaw copies lx; mdns_sum_add_gauss needs nothing;
+ * mdns_sum_set_attenuation copies att.  Adding is all or none: a refused call (returns 1) leaves the model as it was and
+ * nothing allocated; every rule is looked for in the host arrays before the device is asked for anything, and the
+ * message names the function, the array and the index.  Refused: a null argument; lx[i] or att[i] not finite; a ninth
+ * component; ndim above MDNS_MAX_DIM; a second mdns_sum_set_attenuation; any add or set_attenuation after the handle's
+ * first use -- a curves, init or draw call that got as far as making curves -- ("the model is fixed at its first use");
+ * a model without components in any curves, init or draw call.  mdns_sum_destroy frees the tables with the rest.
+ * mdns_sum_nparams: ndim; mdns_sum_nx; mdns_sum_ncomponents (-1: null handle).
+ *
+ * mdns_sum_curves_batch: params host f64[B][ndim] -> out host f64[B][nx] (synchronous).  _dev: device pointers, rows of
+ * ldc >= nx doubles whose padding is not touched, asynchronous on the library stream.  B == 0: nothing happens.  The
+ * table components' curves go through a grow-only block [tables][B][nx] of the handle: a growth the device refuses fails
+ * that call and leaves the handle usable.  One launch_table_curves per table component (1 or 3 kernels each), then ONE
+ * k_sum_curves, grid (B, ceil(nx / MDNS_TABLE_TILE)), a bin per thread.
+ *
+ * mdns_backend_draw_sum, mdns_joint_init_sum: mdns_backend_draw_table and mdns_joint_init_table with the curves made by
+ * the sum: the same checks, then exactly the path of mdns_backend_draw_curves_dev, under every curve statistic, with or
+ * without a response.  Refused beside the above: a sum whose nx is not the spectra's, or not the response's n_in where
+ * one is attached.  No scoring, accept or commit kernel changes.
+ *
+ * Not covered: parameters shared between components (one redshift for a table and a line), bin-integrated components,
+ * components other than these three, more than one attenuation, sharded runs, the chained first batch.
+ * ------------------------------------------------------------------------------------------ */
+#define MDNS_SUM_MAX_COMPONENTS 8
+#define MDNS_SUM_TABLE 0
+#define MDNS_SUM_POWERLAW 1
+#define MDNS_SUM_GAUSS 2
+typedef struct mdns_sum mdns_sum;
+mdns_sum *mdns_sum_create(const double *x, int nx);
+int mdns_sum_add_table(mdns_sum *m, int d, const int *n, const double *axes, int nw, const double *grid, const double *table,
+                       int flags, const double *ext, int attenuated);
+int mdns_sum_add_powerlaw(mdns_sum *m, const double *lx, int attenuated);
+int mdns_sum_add_gauss(mdns_sum *m, int attenuated);
+int mdns_sum_set_attenuation(mdns_sum *m, const double *att);
+void mdns_sum_destroy(mdns_sum *m);
+int mdns_sum_nparams(const mdns_sum *m);
+int mdns_sum_nx(const mdns_sum *m);
+int mdns_sum_ncomponents(const mdns_sum *m);
+int mdns_sum_curves_batch(mdns_sum *m, const double *params, int B, double *out);
+int mdns_sum_curves_batch_dev(mdns_sum *m, const double *d_params, int B, double *d_out, int ldc);
+int mdns_backend_draw_sum(void *joint, mdns_sum *m, const double *params, int B, const double *jitter, int *accepted,
+                          unsigned long long *fillbits, int *nscored);
+int mdns_joint_init_sum(mdns_joint *j, mdns_sum *m, const double *params, double noise_level, const double *jitter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,10 @@ ABI_SYMBOLS = (
     # Part 13: the instrument response folded into model curves on the device (csrc/mdns_response.hip k_response_fold)
     "mdns_response_create", "mdns_response_destroy", "mdns_response_nx", "mdns_response_nin", "mdns_response_fold_batch",
     "mdns_response_fold_batch_dev", "mdns_spectra_set_response",
+    # Part 14: a sum of tables, power laws and Gaussian lines as the model (csrc/mdns_sum.hip k_sum_curves)
+    "mdns_sum_create", "mdns_sum_add_table", "mdns_sum_add_powerlaw", "mdns_sum_add_gauss", "mdns_sum_set_attenuation",
+    "mdns_sum_destroy", "mdns_sum_nparams", "mdns_sum_nx", "mdns_sum_ncomponents", "mdns_sum_curves_batch",
+    "mdns_sum_curves_batch_dev", "mdns_backend_draw_sum", "mdns_joint_init_sum",
 )
 
 #: the symbols of include/mdns.h Part 5 that live in libmdns_host.so (plain host code, no GPU)
@@ -94,6 +98,8 @@ TABLE_EXTINCTION = 4
 TABLE_BROADEN = 8
 TABLE_BROADEN_CUT = 5.0
 TABLE_BROADEN_C = float.fromhex("-0x1.bcb7b1526e50ep-3")      # the double nearest to -0.5 log10(e)
+#: mdns.h Part 14: MDNS_SUM_MAX_COMPONENTS
+SUM_MAX_COMPONENTS = 8
 
 
 class MdnsError(RuntimeError):
@@ -266,6 +272,19 @@ def _declare(lib):
         "mdns_response_fold_batch": (i, [vp, vp, i, vp]),
         "mdns_response_fold_batch_dev": (i, [vp, vp, i, i, vp, i]),
         "mdns_spectra_set_response": (i, [vp, vp]),
+        "mdns_sum_create": (vp, [vp, i]),
+        "mdns_sum_add_table": (i, [vp, i, vp, vp, i, vp, vp, i, vp, i]),
+        "mdns_sum_add_powerlaw": (i, [vp, vp, i]),
+        "mdns_sum_add_gauss": (i, [vp, i]),
+        "mdns_sum_set_attenuation": (i, [vp, vp]),
+        "mdns_sum_destroy": (None, [vp]),
+        "mdns_sum_nparams": (i, [vp]),
+        "mdns_sum_nx": (i, [vp]),
+        "mdns_sum_ncomponents": (i, [vp]),
+        "mdns_sum_curves_batch": (i, [vp, vp, i, vp]),
+        "mdns_sum_curves_batch_dev": (i, [vp, vp, i, vp, i]),
+        "mdns_backend_draw_sum": (i, [vp, vp, vp, i, vp, vp, vp, vp]),
+        "mdns_joint_init_sum": (i, [vp, vp, vp, d, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include <utility>
+#include <vector>
 #include "mdns.h"
 
 namespace mdns {
@@ -278,12 +279,46 @@ struct mdns_table {
 	mdns::DeviceBuffer<double> d_S, d_R;
 };
 
+// a sum of components as the model (mdns.h Part 14, mdns_sum.hip): built by the add entries, fixed at its first use
+struct mdns_sum {
+	int nx = 0;         // bins of the abscissa the curves are made on
+	int ncomp = 0;      // components, in the order they were added
+	int nparams = 0;    // parameters of the components together; a candidate's row has nparams + has_att
+	int has_att = 0;    // 1: the common attenuation is set and N stands last in the row
+	int used = 0;       // 1: a curves, init or draw call has run; nothing is added any more
+	int kind[MDNS_SUM_MAX_COMPONENTS] = {};        // MDNS_SUM_TABLE | MDNS_SUM_POWERLAW | MDNS_SUM_GAUSS
+	int at[MDNS_SUM_MAX_COMPONENTS] = {};          // where the component's parameters begin in a row
+	int attenuated[MDNS_SUM_MAX_COMPONENTS] = {};
+	mdns_table *table[MDNS_SUM_MAX_COMPONENTS] = {};           // OWNED: a TABLE component's table on this x, else nullptr
+	mdns::DeviceBuffer<double> d_lx[MDNS_SUM_MAX_COMPONENTS];  // [nx] of a POWERLAW component, else empty
+	std::vector<double> x;                 // the host's copy: what mdns_sum_add_table builds its table on
+	// resident blocks, made once at their exact size
+	mdns::DeviceBuffer<double> d_x;        // [nx]
+	mdns::DeviceBuffer<double> d_att;      // [nx] the attenuation's exponent per unit N, or empty
+	// grow-only scratch: the table components' curves [tables][B][nx]; the host-pointer batch call's two blocks
+	mdns::DeviceBuffer<double> d_tcurves, d_params, d_out;
+	int ndim() const { return nparams + has_att; }
+};
+
 namespace mdns {
 
 // the table model's curves for d_params [B][t->ndim] -> d_out [B][ldc] (ldc >= t->nx; the padding is not touched),
 // asynchronous on ctx()->stream (mdns_table.hip: k_table_curves, or the k_table_los_* route the handle's flags select,
 // which may grow the handle's scratch)
 bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc);
+// the same for candidates whose rows lie pstride >= t->ndim doubles apart (a slice of wider rows: mdns_sum.hip)
+bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc, int pstride);
+// what every entry that makes a table goes through (mdns_table.hip): `who` names the entry in the messages, `known` the
+// flag bits it takes.  All or none: nullptr (the error set) and nothing left allocated
+mdns_table *table_create(const char *who, int known, const double *x, int nx, int d, const int *n, const double *axes, int nw,
+                         const double *grid, const double *table, int flags, const double *ext);
+
+// a sum model (mdns_sum.hip; mdns.h Part 14).  sum_ready: false (the error set under `who`) for a null handle or a model
+// without components.  launch_sum_curves: d_params [B][m->ndim] -> d_out [B][ldc] (ldc >= m->nx; the padding is not
+// touched), asynchronous on ctx()->stream: launch_table_curves per table component into the handle's grow-only scratch,
+// then k_sum_curves.  The model is fixed from the first call on
+bool sum_ready(const mdns_sum *m, const char *who);
+bool launch_sum_curves(mdns_sum *m, const double *d_params, int B, double *d_out, int ldc);
 
 // the instrument response (mdns_response.hip; mdns.h Part 13), asynchronous on ctx()->stream:
 // d_curves [B][ldc] (ldc >= r->n_in) -> d_out [B][ldo] (ldo >= r->nx); the padding is neither read nor written

@@ -747,6 +747,42 @@ extern "C" int mdns_joint_init_table(mdns_joint *j, mdns_table *table, const dou
 	return init_from_curves(j, c, jitter);
 }
 
+// the same two for a sum model (mdns.h Part 14): table_fits' wording
+static bool sum_fits(const mdns_joint *j, const mdns_sum *m, const char *who)
+{
+	if (!sum_ready(m, who)) return false;
+	if (j->s->response && m->nx != j->s->response->n_in) {
+		set_error("%s: the sum model makes curves of %d bins, the spectra's response takes %d", who, m->nx, j->s->response->n_in);
+		return false;
+	}
+	if (!j->s->response && m->nx != j->s->nx) {
+		set_error("%s: the sum model makes curves of %d channels, the spectra have %d", who, m->nx, j->s->nx);
+		return false;
+	}
+	return true;
+}
+
+// params host [B][ndim] -> j->d_curves [B][nx], made by the sum model on the library's stream
+static bool sum_curves(mdns_joint *j, Context *c, mdns_sum *m, const double *params, int B)
+{
+	const size_t np = (size_t) B * m->ndim();
+	// (a pageable source, as chunk_noise's)
+	return j->d_tparams.fit(np) && j->d_curves.fit((size_t) B * m->nx) &&
+	       MDNS_HIP(hipMemcpyAsync(j->d_tparams.get(), params, np * sizeof(double), hipMemcpyHostToDevice, c->stream)) &&
+	       launch_sum_curves(m, j->d_tparams.get(), B, j->d_curves.get(), m->nx);
+}
+
+extern "C" int mdns_joint_init_sum(mdns_joint *j, mdns_sum *m, const double *params, double noise_level, const double *jitter)
+{
+	Context *c = ctx();
+	if (!c || !j || !params) return 1;
+	if (j->s->nx < 1) { set_error("mdns_joint_init_sum: spectra without channels"); return 1; }
+	if (!sum_fits(j, m, "mdns_joint_init_sum")) return 1;
+	if (j->stat == kCurveNoise) j->noise_level = noise_level;
+	if (!sum_curves(j, c, m, params, j->nlive)) return 1;
+	return init_from_curves(j, c, jitter);
+}
+
 extern "C" int mdns_joint_restore_live_dev(mdns_joint *j, const double *d_liveL)
 {
 	Context *c = ctx();
@@ -1505,6 +1541,25 @@ extern "C" int mdns_backend_draw_table(void *joint, mdns_table *table, const dou
 	const double *d_noise = chunk_noise(j, c, jitter, (size_t) B * j->sel_M);
 	if (jitter && !d_noise) return 1;
 	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, d_noise, accepted, fillbits, "mdns_backend_draw_table");
+}
+
+// and by a sum model (mdns.h Part 14): mdns_backend_draw_table with the curves made by launch_sum_curves
+extern "C" int mdns_backend_draw_sum(void *joint, mdns_sum *m, const double *params, int B, const double *jitter, int *accepted,
+                                     unsigned long long *fillbits, int *nscored)
+{
+	Context *c;
+	mdns_joint *j = (mdns_joint *) joint;
+	const int nx = j ? curve_bins(j->s) : 0;
+	if (ctx() && j && accepted) {
+		*accepted = -1;
+		if (!sum_fits(j, m, "mdns_backend_draw_sum")) return 1;
+	}
+	const int rc = draw_curves_check(joint, &c, &j, params, nx, B, accepted, nscored, "mdns_backend_draw_sum");
+	if (!j) return rc;
+	if (!sum_curves(j, c, m, params, B)) return 1;
+	const double *d_noise = chunk_noise(j, c, jitter, (size_t) B * j->sel_M);
+	if (jitter && !d_noise) return 1;
+	return draw_curves_dev(j, c, j->d_curves.get(), nx, B, d_noise, accepted, fillbits, "mdns_backend_draw_sum");
 }
 
 // candidates per chunk: four times the tries the last draw needed, within a budget of (candidate,

@@ -23,6 +23,7 @@ namespace mdns {
 struct TableView {
 	const double *x, *axes, *grid, *table;
 	int nx, d, nw, ndim, flags;
+	int pstride;                               // doubles between the rows of two candidates in `params` (>= ndim)
 	int n[MDNS_TABLE_MAX_AXES];                // knots per axis
 	int axis_at[MDNS_TABLE_MAX_AXES];          // where axis a begins in `axes`
 	long long stride[MDNS_TABLE_MAX_AXES];     // doubles between neighbouring knots of axis a in `table`
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kTableTile) void k_table_curves(const TableView tv,
 	__shared__ int s_nan;
 	const int b = blockIdx.x, tid = threadIdx.x, d = tv.d;
 	if (b >= B) return;                                                   // (uniform over the workgroup)
-	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	const double *__restrict__ p = params + (size_t) b * tv.pstride;
 	if (tid < d) {
 		const double *__restrict__ axis = tv.axes + tv.axis_at[tid];
 		const int n = tv.n[tid];
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(kTableTile) void k_table_los_gather(const TableView
 	__shared__ int s_nan;
 	const int b = blockIdx.x, tid = threadIdx.x, d = tv.d;
 	if (b >= B) return;                                                   // (uniform over the workgroup)
-	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	const double *__restrict__ p = params + (size_t) b * tv.pstride;
 	los_corners(tv, lv, p, s_f, s_i, s_w, s_off, &s_nan);
 	const int j = blockIdx.y * kTableTile + tid;
 	if (j >= tv.nx) return;
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(kTableTile) void k_table_los_blend(const TableView 
 	__shared__ int s_nan;
 	const int b = blockIdx.x;
 	if (b >= B) return;                                                   // (uniform over the workgroup)
-	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	const double *__restrict__ p = params + (size_t) b * tv.pstride;
 	los_corners(tv, lv, p, s_f, s_i, s_w, s_off, &s_nan);
 	const int m = blockIdx.y * kTableTile + threadIdx.x;
 	if (m >= tv.nw || s_nan) return;
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(kTableTile) void k_table_los_broaden(const TableVie
 {
 	const int b = blockIdx.x, m = blockIdx.y * kTableTile + threadIdx.x, nw = tv.nw;
 	if (b >= B || m >= nw) return;
-	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	const double *__restrict__ p = params + (size_t) b * tv.pstride;
 	if (los_row_is_nan(tv, lv, p)) return;
 	const double *__restrict__ Sb = S + (size_t) b * nw;
 	const double s = p[lv.at_s];
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(kTableTile) void k_table_los_resample(const TableVi
 {
 	const int b = blockIdx.x, j = blockIdx.y * kTableTile + threadIdx.x;
 	if (b >= B || j >= tv.nx) return;
-	const double *__restrict__ p = params + (size_t) b * tv.ndim;
+	const double *__restrict__ p = params + (size_t) b * tv.pstride;
 	double *__restrict__ o = out + (size_t) b * ldc + j;
 	if (los_row_is_nan(tv, lv, p)) { *o = __builtin_nan(""); return; }
 	double u = tv.x[j];
@@ -282,11 +283,11 @@ __global__ __launch_bounds__(kTableTile) void k_table_los_resample(const TableVi
 	*o = acc;
 }
 
-static TableView table_view(const mdns_table *t)
+static TableView table_view(const mdns_table *t, int pstride)
 {
 	TableView tv = {};
 	tv.x = t->d_x.get(); tv.axes = t->d_axes.get(); tv.grid = t->d_grid.get(); tv.table = t->d_table.get();
-	tv.nx = t->nx; tv.d = t->d; tv.nw = t->nw; tv.ndim = t->ndim; tv.flags = t->flags;
+	tv.nx = t->nx; tv.d = t->d; tv.nw = t->nw; tv.ndim = t->ndim; tv.flags = t->flags; tv.pstride = pstride;
 	int at = 0;
 	for (int a = 0; a < t->d; a++) { tv.n[a] = t->n[a]; tv.axis_at[a] = at; at += t->n[a]; }
 	long long stride = t->nw;
@@ -306,18 +307,19 @@ static LosView los_view(const mdns_table *t)
 }
 
 // the one place that chooses the route: neither new flag k_table_curves, extinction alone the gather with two knots,
-// broadening the three stages through the handle's grow-only S and R
-bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc)
+// broadening the three stages through the handle's grow-only S and R.  pstride: doubles between the rows of two
+// candidates (>= t->ndim; a sum model hands over a slice of wider rows, mdns_sum.hip); no value depends on it
+bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc, int pstride)
 {
 	Context *c = ctx();
 	if (!c) return false;
 	if (B <= 0) return true;
 	const dim3 grid((unsigned) B, (unsigned) ((t->nx + kTableTile - 1) / kTableTile));
+	const TableView tv = table_view(t, pstride);
 	if (!(t->flags & (MDNS_TABLE_EXTINCTION | MDNS_TABLE_BROADEN))) {
-		hipLaunchKernelGGL(k_table_curves, grid, dim3(kTableTile), 0, c->stream, table_view(t), d_params, B, d_out, ldc);
+		hipLaunchKernelGGL(k_table_curves, grid, dim3(kTableTile), 0, c->stream, tv, d_params, B, d_out, ldc);
 		return launched("k_table_curves");
 	}
-	const TableView tv = table_view(t);
 	const LosView lv = los_view(t);
 	if (!(t->flags & MDNS_TABLE_BROADEN)) {
 		hipLaunchKernelGGL(k_table_los_gather, grid, dim3(kTableTile), 0, c->stream, tv, lv, d_params, B, d_out, ldc);
@@ -333,6 +335,11 @@ bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d
 	if (!launched("k_table_los_broaden")) return false;
 	hipLaunchKernelGGL(k_table_los_resample, grid, dim3(kTableTile), 0, c->stream, tv, lv, d_params, B, t->d_R.get(), d_out, ldc);
 	return launched("k_table_los_resample");
+}
+
+bool launch_table_curves(mdns_table *t, const double *d_params, int B, double *d_out, int ldc)
+{
+	return launch_table_curves(t, d_params, B, d_out, ldc, t->ndim);
 }
 
 }  // namespace mdns
@@ -357,9 +364,9 @@ static bool knots_ok(const char *who, const double *knots, int n, const char *wh
 	return true;
 }
 
-// both create entries: `known` the flag bits `who` takes, `ext` null for mdns_table_create.  Every rule of the statement,
-// on the host copies, before the device is asked for anything
-static mdns_table *table_create(const char *who, int known, const double *x, int nx, int d, const int *n, const double *axes, int nw,
+// every create entry (mdns_sum_add_table of mdns_sum.hip too): `known` the flag bits `who` takes, `ext` null for
+// mdns_table_create.  Every rule of the statement, on the host copies, before the device is asked for anything
+mdns_table *mdns::table_create(const char *who, int known, const double *x, int nx, int d, const int *n, const double *axes, int nw,
                                 const double *grid, const double *table, int flags, const double *ext)
 {
 	if (!x || !n || !axes || !grid || !table) { set_error("%s: null argument", who); return nullptr; }

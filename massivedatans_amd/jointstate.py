@@ -528,8 +528,9 @@ class CurveJointState(DeviceJointState):
     fixed-scale one with per-pixel variances (mdns_curve_chi2_batch), over a
     :class:`massivedatans_amd.like.CountSpectra` the Poisson one (mdns_curve_poisson_batch; with a background the W
     statistic, mdns_curve_wstat_batch).  ``nparams`` is the model's ``ndim``: what the first
-    ``init`` is given, or ``ndim=``.  With ``table=`` (a :class:`massivedatans_amd.tablemodel.DeviceTable`) the curves
-    are made on the device from the parameters and ``model`` is not called.
+    ``init`` is given, or ``ndim=``.  With ``table=`` (a :class:`massivedatans_amd.tablemodel.DeviceTable`, or a
+    :class:`massivedatans_amd.summodel.DeviceSum`, which names its two entries) the curves are made on the device from the
+    parameters and ``model`` is not called.
 
     A native constrainer reaches this state through ``constrainer.python_backend``, whose chunks end in
     :meth:`draw_params`.  A curve chunk does not count its point into ``shelf_n``: whoever drives the draws
@@ -550,6 +551,9 @@ class CurveJointState(DeviceJointState):
             if self.nparams is not None and self.nparams != table.ndim:
                 raise ValueError("ndim = %d, the table model takes %d parameters" % (self.nparams, table.ndim))
             self.nparams = int(table.ndim)
+        # the two entries that take the device model's handle: the object's own (summodel.DeviceSum), or the table's
+        self._init_entry = getattr(table, "init_entry", "mdns_joint_init_table")
+        self._draw_entry = getattr(table, "draw_entry", "mdns_backend_draw_table")
         self._d_jitter, self._d_jitter_bytes = None, 0
         self._n32 = numpy.zeros(self.ndata, dtype=numpy.int32)
 
@@ -588,8 +592,8 @@ class CurveJointState(DeviceJointState):
         jitter = self._init_jitter(jitter)
         if self.table is not None:
             xs = _lib.as_f64(xs)
-            self._check(self._lib.mdns_joint_init_table(self._h, self.table.handle, _lib.ptr(xs), self.noise_level, _lib.opt(jitter)),
-                        "mdns_joint_init_table")
+            init = getattr(self._lib, self._init_entry)
+            self._check(init(self._h, self.table.handle, _lib.ptr(xs), self.noise_level, _lib.opt(jitter)), self._init_entry)
         else:
             address, ld, on_device, keep = self._curves(xs)
             if on_device:                                     # (once per run: through the host)
@@ -625,8 +629,8 @@ class CurveJointState(DeviceJointState):
         self._check(self._lib.mdns_backend_draw_begin(self._h, _lib.opt(rows), M), "mdns_backend_draw_begin")
         out = (C.addressof(self._accepted), _lib.ptr(self._bits), C.addressof(self._nscored))
         if self.table is not None:
-            self._check(self._lib.mdns_backend_draw_table(self._h, self.table.handle, _lib.ptr(params), B, _lib.opt(jitter), *out),
-                        "mdns_backend_draw_table")
+            draw = getattr(self._lib, self._draw_entry)
+            self._check(draw(self._h, self.table.handle, _lib.ptr(params), B, _lib.opt(jitter), *out), self._draw_entry)
         elif on_device:
             self._check(self._lib.mdns_backend_draw_curves_dev(self._h, address, ld, B, self._jitter_to_device(jitter), *out),
                         "mdns_backend_draw_curves_dev")

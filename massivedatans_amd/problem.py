@@ -99,7 +99,10 @@ class CurveProblem(object):
     likelihood above: the device then interpolates the table per candidate and scores the curves where they lie --
     draws and the initial points hand over parameters (``mdns_backend_draw_table``, ``mdns_joint_init_table``) and no
     curve is made in Python; ``multi_loglikelihood[_batch]`` fetch the device's curves and score them like any other.
-    Over a ``backend`` that is not on the device the model is ``TableModel.statement``.
+    Over a ``backend`` that is not on the device the model is ``TableModel.statement``.  A
+    :class:`massivedatans_amd.summodel.SumModel` -- a sum of tables, power laws and Gaussian lines with an optional common
+    attenuation (include/mdns.h Part 14) -- is taken in the same way (``mdns_backend_draw_sum``, ``mdns_joint_init_sum``;
+    elsewhere ``SumModel.statement``).
 
     ``response`` (a :class:`massivedatans_amd.response.Response` of ``nx`` channels; works with every likelihood above):
     the instrument response between the model and the data.  ``model`` then returns ``[B, response.n_in]``, on the
@@ -162,14 +165,17 @@ class CurveProblem(object):
         if not 1 <= int(ndim) <= MAX_DIM:
             raise ValueError("ndim = %r: 1 to %d parameters" % (ndim, MAX_DIM))
         self.nparams = int(ndim)
+        from .summodel import SumModel
         from .tablemodel import TableModel
-        table_model = model if isinstance(model, TableModel) else None
+        # (a sum model, massivedatans_amd.summodel, is treated exactly like a table model: bound to the device, or its statement)
+        table_model = model if isinstance(model, (TableModel, SumModel)) else None
+        kind = "sum" if isinstance(model, SumModel) else "table"
         if table_model is not None and table_model.ndim != self.nparams:
-            raise ValueError("ndim = %d, the table model takes %d parameters" % (self.nparams, table_model.ndim))
+            raise ValueError("ndim = %d, the %s model takes %d parameters" % (self.nparams, kind, table_model.ndim))
         if table_model is not None and response is not None and response.x_in is None:
-            raise ValueError("a table model under a response is evaluated on the response's model bins: the response needs x_in")
+            raise ValueError("a %s model under a response is evaluated on the response's model bins: the response needs x_in" % kind)
         model_x = self.x if response is None else response.x_in     # the abscissa a table model is bound to
-        self.table = None                            # a table model on the device (tablemodel.DeviceTable)
+        self.table = None                            # a table model on the device (tablemodel.DeviceTable, summodel.DeviceSum)
         self.model = model
         self.priortransform_batch = priortransform_batch
         self.noise_level = float(noise_level)

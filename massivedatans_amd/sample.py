@@ -243,7 +243,8 @@ def run_model(problem, nlive_points=400, nsuperset_draws=10, use_graph=False, ma
 
 def load_model(path):
     """A ``MDNS_MODEL`` file: Python that defines ``model(xs[B, ndim]) -> curves[B, nx]`` (or ``model = TableModel(...)``,
-    massivedatans_amd.tablemodel: ``ndim`` must then be the table model's),
+    massivedatans_amd.tablemodel, or ``model = SumModel(...)``, massivedatans_amd.summodel: ``ndim`` must then be that
+    model's),
     ``priortransform_batch(us[B, ndim]) -> xs[B, ndim]`` and ``ndim``, optionally ``noise_level`` and
     ``marginalise_scale`` (default True; False: the fixed-scale likelihood of problem.CurveProblem, which needs
     variances ``v`` in the data file) and ``poisson`` (default False; True: ``y`` of the data file holds photon counts,
@@ -266,15 +267,18 @@ def load_model(path):
         if not hasattr(module, name):
             raise ValueError("%s does not define `%s`" % (path, name))
         out[name] = getattr(module, name)
+    from .summodel import SumModel
     from .tablemodel import TableModel
-    if isinstance(out["model"], TableModel):
-        # a tabulated template grid (massivedatans_amd.tablemodel): the device interpolates it, no model function runs
+    if isinstance(out["model"], (TableModel, SumModel)):
+        # a tabulated template grid (massivedatans_amd.tablemodel), or a sum of components (massivedatans_amd.summodel):
+        # the device evaluates it, no model function runs
+        kind = "sum" if isinstance(out["model"], SumModel) else "table"
         try:
             given = int(out["ndim"])
         except (TypeError, ValueError):
             raise ValueError("%s: `ndim` = %r is not a number of parameters" % (path, out["ndim"]))
         if given != out["model"].ndim:
-            raise ValueError("%s: `ndim` = %d, but its table model takes %d parameters" % (path, given, out["model"].ndim))
+            raise ValueError("%s: `ndim` = %d, but its %s model takes %d parameters" % (path, given, kind, out["model"].ndim))
     out["noise_level"] = float(getattr(module, "noise_level", noise_level))
     out["marginalise_scale"] = bool(getattr(module, "marginalise_scale", True))
     out["poisson"] = bool(getattr(module, "poisson", False))
